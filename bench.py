@@ -17,6 +17,7 @@ Rank 0 prints ONE JSON line on stdout: a COMPACT record (< 2 KB: metric, value, 
 driver parses).  Everything else this script can measure (per-stage table, the issue roofline with its sources, the
 backward-only figure, and -- with --extra-configs -- the other BASELINE configurations, each with a CPU baseline of its own)
 goes to a side file (--extras-out, default gpurun_out/bench_extras.json), never to stdout.
+--dump-outputs DIR writes what the headline's last timed step computed (dump_outputs) for output-for-output comparisons.
 """
 import argparse
 import json
@@ -258,6 +259,32 @@ def compact_record(full):
     return line
 
 
+DUMP_LIMIT = 64 * 10 ** 6  # bytes: everything --dump-outputs writes (files, .npy headers included)
+
+
+def dump_outputs(out_dir, g, cost, limit=DUMP_LIMIT, seed=0):
+    """--dump-outputs: what a caller of the timed path receives after its last step, as out_dir/<name>.npy (float64, the
+    ABI's result type): cost.npy [B_global] (the gathered costs), and xs.npy [S][T+1][nx], us.npy [S][T][nu],
+    k_feedforward.npy [S][T][nu], K_feedback.npy [S][T][nu][nx] of this rank's trajectories.  S = every trajectory when
+    they fit in `limit` bytes with the costs, otherwise a fixed sample drawn with `seed` (sorted indices), so that two
+    builds run with the same arguments write arrays of the same trajectories.  Returns {name: shape}."""
+    cost = np.asarray(cost, dtype=np.float64)
+    per_traj = 8 * ((g.T + 1) * g.nx + 2 * g.T * g.nu + g.T * g.nu * g.nx)
+    n = min(g.B, (limit - cost.nbytes - 5 * 128) // per_traj)  # (128: the header of a .npy file of a plain array)
+    if n < 1:
+        raise ValueError("--dump-outputs: not one trajectory fits in %d bytes" % limit)
+    idx = np.arange(g.B) if n == g.B else np.sort(np.random.default_rng(seed).choice(g.B, n, replace=False))
+    xs, us = g.trajectory()
+    k, K = g.gains()
+    arrays = {"cost": cost, "xs": xs[idx], "us": us[idx], "k_feedforward": k[idx], "K_feedback": K[idx]}
+    os.makedirs(out_dir, exist_ok=True)
+    paths = [os.path.join(out_dir, name + ".npy") for name in arrays]
+    for path, a in zip(paths, arrays.values()):
+        np.save(path, np.ascontiguousarray(a, dtype=np.float64))
+    assert sum(os.path.getsize(p) for p in paths) <= limit
+    return {name: a.shape for name, a in arrays.items()}
+
+
 def lq_mats(n, m, seed=7):
     """SURVEY.md 8(d) cfg 5: A = -I + 0.1 N(0,1)/sqrt(n), B = N(0,1)/sqrt(n), Q = I, R = 0.1 I."""
     rng = np.random.default_rng(seed)
@@ -289,27 +316,41 @@ def main():
                     "this torch.distributed backend (gloo) instead of nccl = RCCL, every rank on the device LOCAL_RANK modulo the visible ones, the one "
                     "collective on host tensors.  A line produced this way says so (collective_backend) and is no measurement")
     ap.add_argument("--route", type=int, default=0, help="enum ilqr_route for the headline handle (A/B runs of equivalent kernels)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the headline's last step computed "
+                    "(costs, trajectories, gains; a fixed sample of the trajectories when all would exceed 64 MB) as DIR/<name>.npy, for "
+                    "comparing two builds output for output")
     args = ap.parse_args()
     args.no_extra_configs = not args.extra_configs
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+
+    if "WORLD_SIZE" not in os.environ and args.gpus > 1:
+        # started as plain `python bench.py --gpus N`: run the N-rank job (one process per GPU) as a child instead of quietly
+        # measuring one GPU.  This process never opens the GPU: the devices are counted by a child that has exited before
+        # the ranks start.
+        import socket
+        import subprocess
+        probe = subprocess.run([sys.executable, "-c", "import torch; print('devices', torch.cuda.device_count() if torch.cuda.is_available() else 0)"],
+                               capture_output=True, text=True, timeout=300)
+        have = [int(ln.split()[1]) for ln in probe.stdout.splitlines() if ln.startswith("devices ")]
+        if probe.returncode != 0 or not have:
+            raise SystemExit("bench.py --gpus %d: could not count the HIP devices: %s" % (args.gpus, probe.stderr[-500:]))
+        if have[0] == 0:
+            raise SystemExit("bench.py needs a GPU: the HIP path has no CPU fallback")
+        if have[0] < args.gpus:
+            raise SystemExit("bench.py --gpus %d: only %d HIP device(s) visible" % (args.gpus, have[0]))
+        with socket.socket() as sk:
+            sk.bind(("127.0.0.1", 0))
+            port = sk.getsockname()[1]
+        sys.exit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
+                                  "--nproc-per-node=%d" % args.gpus, "--master-addr", "127.0.0.1",
+                                  "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]))
 
     import torch
     import torch.distributed as dist
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU: the HIP path has no CPU fallback")
-    if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        # started as plain `python bench.py --gpus N`: become the N-rank job (one process per GPU) instead
-        # of quietly measuring one GPU
-        have = torch.cuda.device_count()
-        if have < args.gpus:
-            raise SystemExit("bench.py --gpus %d: only %d HIP device(s) visible" % (args.gpus, have))
-        import socket
-        with socket.socket() as sk:
-            sk.bind(("127.0.0.1", 0))
-            port = sk.getsockname()[1]
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
-                                  "--nproc-per-node=%d" % args.gpus, "--master-addr", "127.0.0.1",
-                                  "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
 
     from ilqr_amd import BatchILQR, capi
     from ilqr_amd import dist as D
@@ -426,6 +467,8 @@ def main():
     B, lim, steps = args.batch, args.limit, args.steps
     s_bytes = 8 if args.dtype == "f64" else 4
     g, elapsed, prof, gathered = acrobot_run(args.dtype, B, lim, steps, args.warmup, args.flags)
+    if args.dump_outputs and rank == 0:  # (before the backward-only passes below overwrite the gains)
+        dump_outputs(args.dump_outputs, g, gathered.cpu().numpy())
 
     # backward-pass-only figure of the north star (outside the timed region): the stand-alone quad
     # kernel, one pass at the current lambda, on the derivative records of the final nominal trajectory

@@ -43,6 +43,33 @@ ILQR_HD float recip(float a) {
   return 1.0f / a;
 #endif
 }
+// recip() for the box-QP's factors of Quu + lambda, whose lambda reaches inf when fixed-work iterations go on past lambda_max:
+// v_div_fixup (one instruction; a quotient of a finite, non-zero a passes unchanged) gives the division's special cases -- +-0
+// for an infinite a, where the Newton steps alone make inf * 0 = NaN (and with it NaN gains); inf for a = 0, where they make NaN.
+ILQR_HD double recip_reg(double a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_div_fixup(recip(a), a, 1.0);
+#else
+  return 1.0 / a;
+#endif
+}
+ILQR_HD float recip_reg(float a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_div_fixupf(recip(a), a, 1.0f);
+#else
+  return 1.0f / a;
+#endif
+}
+// The adjugate inverse of a positive definite free block [a00 a10; a10 a11] (det = a00 a11 - a10^2).  An infinite det -- lambda
+// = inf on the diagonal -- gives the limit, 0, where a11 / det as a11 * (1/det) would be inf * 0 = NaN.
+template <class real>
+ILQR_HD void inv2_pd(real a00, real a10, real a11, real det, real& m00, real& m01, real& m11) {
+  const real rd = recip_reg(det);
+  const bool big = __builtin_isinf(det);
+  m00 = big ? real(0) : a11 * rd;
+  m01 = big ? real(0) : -a10 * rd;
+  m11 = big ? real(0) : a00 * rd;
+}
 // 1/sqrt(a) and sqrt(a) for a normal-range a > 0: v_rsq_f64 + two Newton steps, then one correction of the root (each
 // <= 1 ulp; 11 instructions for the pair instead of ~20 for the IEEE square root plus ~12 per IEEE division by it).
 ILQR_HD void rsqrt_and_sqrt(double a, double& rs, double& s) {
@@ -514,12 +541,9 @@ ILQR_HD void box_qp2_loop(const real* Q, const real* c, const real* x0, const re
       nfR = both ? 2 : 1;
       if (__builtin_expect(pd, 1)) {
         if (both) {
-          const real rd = recip(det);
-          m00 = a11 * rd;
-          m01 = -a10 * rd;
-          m11 = a00 * rd;
+          inv2_pd(a00, a10, a11, det, m00, m01, m11);
         } else {
-          m00 = recip(a00);
+          m00 = recip_reg(a00);
           m01 = m11 = 0;
         }
       } else {  // Eigen's partial factor, literally
@@ -607,10 +631,12 @@ ILQR_HD void box_qp2(const real* Q, const real* c, const real* x0, const real* l
     const real a00 = f0 ? q00 : q11, a10 = f.both ? q10 : real(0), a11 = f.both ? q11 : real(0);
     const real det = a00 * a11 - a10 * a10;
     f.pd = p_and(a00 > real(0), p_or(!f.both, det > real(0)));
-    const real rd = recip(f.both ? det : a00);
-    f.m00 = f.both ? a11 * rd : rd;
-    f.m01 = f.both ? -a10 * rd : real(0);
-    f.m11 = f.both ? a00 * rd : real(0);
+    if (f.both) {
+      inv2_pd(a00, a10, a11, det, f.m00, f.m01, f.m11);
+    } else {
+      f.m00 = recip_reg(a00);
+      f.m01 = f.m11 = real(0);
+    }
     return f;
   };
   // ---- iteration 0
@@ -812,7 +838,7 @@ ILQR_HD void qp1_begin(real Q, real c, real x0, real lo, real hi, QP1StateT<real
   q.val0 = (q.x * Q) * q.x + q.x * c;  // boxqp.cpp:36 (no 1/2)
   q.g0 = Q * q.x + c;
   const real den = (Q > real(0)) ? Q : Q * Q;
-  q.minv = recip(den);
+  q.minv = recip_reg(den);
   // (p_and / p_or: no short-circuit branches in the wavefront's instruction stream, no integer arithmetic on promoted bools)
   q.clA = p_or(p_and(abs_of(q.x - lo) < real(kClampTol), q.g0 > 0), p_and(abs_of(q.x - hi) < real(kClampTol), q.g0 < 0));
   q.exB = abs_of(q.g0) < real(kMinGrad);

@@ -5,6 +5,9 @@
                           finite-difference arrays of random knot points and box-QP solutions.
   stages_<model>.npz      stage-by-stage outputs of the CPU oracle for a small batch (the oracle is
                           pinned to the reference by tests/test_oracle_*.py).
+  ref_answers.npz         the REAL reference's answers to every case of tests/test_oracle_vs_ref.py
+                          (box-QP, line search, model evaluations, finite differences), so that those
+                          tests run where the reference shim cannot be built.
 Only data (inputs + expected outputs) is written; no reference source is stored."""
 import os
 import sys
@@ -89,9 +92,19 @@ def stages(name):
     np.savez_compressed(os.path.join(OUT, "stages_%s.npz" % name), **d)
 
 
+def ref_answers():
+    assert O.ref_available(), "needs the reference shim (oracle/_ref: the build container)"
+    from tests.test_oracle_vs_ref import record
+    np.savez_compressed(os.path.join(OUT, "ref_answers.npz"), **record(O))
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["ref_answers"]:  # (the other files stay as they are)
+        ref_answers()
+        sys.exit(0)
     ref_pieces()
     stages("acrobot")
     stages("integrator")
+    ref_answers()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))

@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
@@ -131,3 +133,75 @@ def test_multi_gpu_request_on_a_box_without_them_fails_loudly():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0"], capture_output=True, text=True, timeout=600)
     assert p.returncode != 0 and p.stdout.strip() == ""
     assert ("HIP device(s) visible" in p.stderr) or ("needs a GPU" in p.stderr)
+
+
+class _FakeHandle:
+    """What dump_outputs reads of a BatchILQR: sizes, trajectory(), gains() (shapes and layouts of ilqr_amd/batch.py)."""
+
+    def __init__(self, B, T, nx, nu):
+        self.B, self.T, self.nx, self.nu = B, T, nx, nu
+        r = np.random.default_rng(5)
+        self.xs, self.us = r.normal(size=(B, T + 1, nx)), r.normal(size=(B, T, nu))
+        self.k, self.K = r.normal(size=(B, T, nu)), r.normal(size=(B, T, nu, nx))
+
+    def trajectory(self):
+        return self.xs.copy(), self.us.copy()
+
+    def gains(self):
+        return self.k.copy(), self.K.copy()
+
+
+def test_dump_outputs_writes_every_result_when_it_fits(tmp_path):
+    g = _FakeHandle(8, 5, 4, 1)
+    cost = np.arange(8.0)
+    shapes = bench.dump_outputs(str(tmp_path), g, cost)
+    assert shapes == {"cost": (8,), "xs": (8, 6, 4), "us": (8, 5, 1), "k_feedforward": (8, 5, 1), "K_feedback": (8, 5, 1, 4)}
+    for name, want in (("cost", cost), ("xs", g.xs), ("us", g.us), ("k_feedforward", g.k), ("K_feedback", g.K)):
+        a = np.load(tmp_path / (name + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, want), name
+
+
+def test_dump_outputs_samples_the_same_trajectories_under_its_size_limit(tmp_path):
+    """The headline's results are 164 MB: a fixed sample of trajectories goes out, the same one on every run, within the limit."""
+    g = _FakeHandle(64, 7, 4, 1)
+    cost = np.linspace(1, 2, 64)
+    per_traj = 8 * (8 * 4 + 2 * 7 + 7 * 4)
+    limit = cost.nbytes + 5 * 128 + 10 * per_traj + 5
+    bench.dump_outputs(str(tmp_path / "a"), g, cost, limit=limit)
+    bench.dump_outputs(str(tmp_path / "b"), g, cost, limit=limit)
+    total = 0
+    for name in ("cost", "xs", "us", "k_feedforward", "K_feedback"):
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert np.array_equal(a, b), name
+        total += os.path.getsize(tmp_path / "a" / (name + ".npy"))
+    assert total <= limit
+    xs = np.load(tmp_path / "a" / "xs.npy")
+    assert np.array_equal(np.load(tmp_path / "a" / "cost.npy"), cost) and xs.shape == (10, 8, 4)
+    rows = [int(np.flatnonzero((g.xs == x).all(axis=(1, 2)))[0]) for x in xs]  # which trajectories: distinct, in order
+    assert rows == sorted(set(rows))
+    assert np.array_equal(np.load(tmp_path / "a" / "K_feedback.npy"), g.K[rows])
+
+
+def test_bench_rejects_a_run_without_timed_steps():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert p.returncode != 0 and p.stdout.strip() == "" and "--steps" in p.stderr
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_the_headline_run(tmp_path):
+    """bench.py --dump-outputs: the sampled results of the headline's last step -- real trajectories of the bench's own inputs,
+    the costs whose mean the extras file reports -- in at most 64 MB of float64 files."""
+    from tests.util import acrobot_x0
+    extras, out = tmp_path / "extras.json", tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "1", "--no-cpu-baseline",
+                        "--extras-out", str(extras), "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = {name: np.load(out / (name + ".npy")) for name in ("cost", "xs", "us", "k_feedforward", "K_feedback")}
+    assert sum(os.path.getsize(out / (name + ".npy")) for name in d) <= 64 * 10 ** 6 and all(a.dtype == np.float64 for a in d.values())
+    assert all(np.isfinite(d[name]).all() for name in ("cost", "xs", "us"))
+    S = d["xs"].shape[0]
+    assert d["cost"].shape == (4096,) and 1000 < S < 4096
+    assert d["xs"].shape == (S, 500, 4) and d["us"].shape == d["k_feedforward"].shape == (S, 499, 1) and d["K_feedback"].shape == (S, 499, 1, 4)
+    assert abs(d["cost"].mean() - json.load(open(extras))["final_cost_mean"]) <= 1e-12 * abs(d["cost"].mean())
+    x0 = {tuple(r) for r in acrobot_x0(4096)}
+    assert all(tuple(r) in x0 for r in d["xs"][:, 0])

@@ -142,3 +142,33 @@ def test_trajectory_getter_fills_caller_arrays():
     with pytest.raises(ValueError):
         g.trajectory(out=(oxs.astype(np.float32), ous))
     g.close()
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("name", ["acrobot", "integrator"])
+def test_gains_stay_finite_once_lambda_overflows(name, dtype):
+    """Fixed-work iterations go on past lambda_max (bench.py's workload): a trajectory whose searches keep failing has its lambda
+    grow until it is inf.  The box-QP's inverse of Quu + lambda is then 0, as the oracle's division and factorisation give, so the
+    gains stay finite -- the device's reciprocal once made it inf * 0 = NaN there (nu = 1: 1 / Quu; nu = 2: the adjugate's
+    a11 / det as well) and every K of such a trajectory came back NaN."""
+    from ilqr_amd import BatchILQR, capi
+    steps = 300
+    if name == "acrobot":
+        B, T, nu = 4096, 499, 1
+        g = BatchILQR("acrobot", B, T, DT, u_min=-1.5, u_max=1.5, dtype=dtype, flags=capi.FLAG_FIXED_WORK, params=dict(max_iter=steps + 6))
+        x0 = acrobot_x0(B)
+    else:
+        B, T, nu = 4096, 100, 2
+        g = BatchILQR("integrator", B, T, DT, u_min=-0.5, u_max=0.5, goal=[1, .5, 0, 0], dtype=dtype, flags=capi.FLAG_FIXED_WORK,
+                      params=dict(max_iter=steps + 6))
+        x0 = integrator_x0(B)
+    g.init_traj(x0, np.zeros((B, T, nu)))
+    g.iterate(5)
+    g.iterate(steps)
+    lam, _ = g.lambdas()
+    assert np.isinf(lam).sum() > B // 8  # (the case this test is about)
+    xs, us = g.trajectory()
+    k, K = g.gains()
+    for what, a in (("xs", xs), ("us", us), ("k", k), ("K", K), ("cost", g.cost())):
+        assert np.isfinite(a).all(), what
+    g.close()
