@@ -190,7 +190,10 @@ def _pi(a):
 class Model:
     """A Model plugin instance (include/model.h) on the oracle side, in the flavour current at construction."""
 
-    def __init__(self, kind, goal=None, lq=None, u_lim=None, chain=None):
+    def __init__(self, kind, goal=None, lq=None, u_lim=None, chain=None, u_min=None, u_max=None):
+        """u_lim: the box [-u_lim, u_lim] for every control; u_min / u_max (scalars or one value per control, given together)
+        set each control's own box and take precedence over u_lim."""
+        assert (u_min is None) == (u_max is None), "u_min and u_max go together"
         self.flavour = _cur
         _Model, _ = _structs()
         self.m = _Model()
@@ -221,14 +224,15 @@ class Model:
         self.kind, self.goal_arg, self.lq_arg, self.lim_arg = kind, goal, lq, u_lim
         if u_lim is not None:
             self.set_limits(-abs(u_lim), abs(u_lim))
+        if u_min is not None:
+            self.set_limits(u_min, u_max)
 
     def twin(self, name):
-        """The same model in another arithmetic flavour (constructed there from the same arguments)."""
+        """The same model in another arithmetic flavour (constructed there from the same arguments), with this model's
+        limits as they stand now -- also those given to set_limits after construction, whatever the kind."""
         with flavour(name):
             m = Model(self.kind, goal=self.goal_arg, lq=[np.asarray(a, dtype=np.float64) for a in self.lq_arg] if self.lq_arg is not None else None,
-                      u_lim=self.lim_arg, chain=self.chain_arg)
-            if self.kind in ("lq", MODEL_LQ, "chain"):
-                m.set_limits(np.asarray(self.u_min, dtype=np.float64), np.asarray(self.u_max, dtype=np.float64))
+                      chain=self.chain_arg, u_min=self.u_min, u_max=self.u_max)
         return m
 
     def set_limits(self, lo, hi):

@@ -65,7 +65,9 @@ def gains_knot_err(k, K, ko, Ko, us):
 def first_gain_mismatch_is_knife_edge(k, K, ko, Ko, us, lo, hi, tol=TOL):
     """One trajectory ([T][...]).  True if the first (largest-t) knot whose gains differ per-knot is a
     box-QP clamp tie: a component of k sits inside the 1e-4 band of a bound on one side or the other and
-    the two k differ by no more than the band (see module docstring).  False when nothing differs."""
+    the two k differ by no more than the band (see module docstring).  False when nothing differs.
+    A component whose box is narrower than the band (hi - lo < 3e-4: a pinned control, lo == hi) sits "on the band"
+    at every knot without deciding anything -- it cannot tie, so it never excuses a mismatch."""
     ek, eK = gains_knot_errs(k[None], K[None], ko[None], Ko[None], us[None])
     bad = np.flatnonzero((ek[0] > tol) | (eK[0] > tol))
     if bad.size == 0:
@@ -73,9 +75,10 @@ def first_gain_mismatch_is_knife_edge(k, K, ko, Ko, us, lo, hi, tol=TOL):
     def on_edge(t):
         if np.abs(k[t] - ko[t]).max() > 2e-4:
             return False
+        wide = (hi[t] - lo[t]) >= 3e-4
         band = np.minimum(np.abs(ko[t] - lo[t]), np.abs(ko[t] - hi[t]))
         band_g = np.minimum(np.abs(k[t] - lo[t]), np.abs(k[t] - hi[t]))
-        return bool(np.any(band < 1.5e-4) or np.any(band_g < 1.5e-4))
+        return bool(np.any(wide & (band < 1.5e-4)) or np.any(wide & (band_g < 1.5e-4)))
 
     t = bad.max()
     if on_edge(t):

@@ -268,3 +268,192 @@ def test_finish_predicates_equal_the_result_code(dev):
         for det in (0, 1):
             r = dev.devfn_qp1_finish_flavours_agree(Q, c, x0, lo, hi, det)
             assert r == 0, (r, Q, c, x0, lo, hi, det)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Boxes a real solve hands the box-QP (the box is [u_min - u, u_max - u], src/ilqr_core.cpp:369, and the forward pass does not clamp):
+# an edge exactly 0 (u sits on a limit), boxes that exclude 0 (feedback or the caller's u0 put u outside its limits), pinned
+# controls (lo == hi), unbounded controls (+-inf) and huge finite ones (+-1e300); and warm starts outside the box.
+# ---------------------------------------------------------------------------------------------------------------------------------
+SHAPES = ("excludes_0_above", "excludes_0_below", "edge_at_0", "pinned", "infinite", "huge", "x0_outside")
+
+
+def _box(rng, shape, m):
+    a, b = rng.uniform(0.05, 1.2, size=m), rng.uniform(0.05, 1.5, size=m)
+    if shape == "excludes_0_above":
+        lo, hi = a, a + b
+    elif shape == "excludes_0_below":
+        lo, hi = -a - b, -a
+    elif shape == "edge_at_0":
+        up = rng.uniform(size=m) < 0.5
+        lo, hi = np.where(up, 0.0, -a), np.where(up, b, 0.0)
+    elif shape == "pinned":
+        v = np.where(rng.uniform(size=m) < 0.3, 0.0, rng.uniform(-1, 1, size=m))
+        lo, hi = v, v.copy()
+    elif shape == "infinite":
+        lo, hi = np.full(m, -np.inf), np.full(m, np.inf)
+    elif shape == "huge":
+        lo, hi = np.full(m, -1e300), np.full(m, 1e300)
+    else:
+        lo, hi = -a, b
+    if shape not in ("x0_outside",) and m > 1 and rng.uniform() < 0.5:  # half the problems mix this shape with ordinary boxes
+        keep = rng.uniform(size=m) < 0.5
+        lo, hi = np.where(keep, lo, -a), np.where(keep, hi, b)
+    return lo, hi
+
+
+def _x0(rng, shape, lo, hi):
+    m = len(lo)
+    if shape == "x0_outside":
+        side = rng.uniform(size=m) < 0.5
+        return np.where(side, lo - rng.uniform(0.01, 2, size=m), hi + rng.uniform(0.01, 2, size=m))
+    x0 = rng.normal(size=m)
+    pick = rng.uniform(size=m)
+    fin = np.isfinite(lo) & (np.abs(lo) < 1e100)
+    return np.where((pick < 0.25) & fin, lo, np.where((pick < 0.5) & fin, hi, x0))
+
+
+def _problems(seed, m, N, indefinite_every=5):
+    """N problems of dimension m, cycling through SHAPES; every `indefinite_every`-th Q indefinite (Eigen's unchecked factor)."""
+    rng = np.random.default_rng(seed)
+    for t in range(N):
+        shape = SHAPES[t % len(SHAPES)]
+        A = rng.normal(size=(m, m))
+        Q = A @ A.T + (-0.3 if indefinite_every and t % indefinite_every == 0 else 0.05) * np.eye(m)
+        c = rng.normal(size=m) * 2
+        lo, hi = _box(rng, shape, m)
+        yield t, shape, Q, c, _x0(rng, shape, lo, hi), lo, hi
+
+
+def _same_x(x, xo, rtol, atol):
+    return np.allclose(x, xo, rtol=rtol, atol=atol, equal_nan=True)
+
+
+def _in_box(x, lo, hi):
+    return bool(np.all((x >= lo) & (x <= hi)))
+
+
+def _kkt_residual(Q, c, x, lo, hi):
+    """Projected gradient of 1/2 x'Qx + c'x at x in extended precision: | x - clip(x - g, lo, hi) | per component, scaled by |g| + 1."""
+    L = np.longdouble
+    Ql, cl, xl = np.asarray(Q, dtype=L), np.asarray(c, dtype=L), np.asarray(x, dtype=L)
+    g = Ql @ xl + cl
+    pg = np.abs(xl - np.clip(xl - g, np.asarray(lo, dtype=L), np.asarray(hi, dtype=L)))
+    return float((pg / (np.abs(g) + 1)).max())
+
+
+KKT_TOL = 1e-7  # (result 5: the free gradient is below 1e-8; result 6: every clamped x sits exactly on its bound)
+
+
+def _check_invariants(Q, x, r, lo, hi, c, what):
+    if r >= 1 and np.all(lo <= hi):
+        assert _in_box(x, lo, hi), (what, x, lo, hi)
+    if r in (5, 6) and np.linalg.eigvalsh(0.5 * (Q + Q.T)).min() > 1e-2:
+        res = _kkt_residual(Q, c, x, lo, hi)
+        assert res <= KKT_TOL, (what, r, res, x, lo, hi)
+        return 1
+    return 0
+
+
+@pytest.mark.parametrize("m", [1, 2, 3, 4])
+def test_generic_solver_on_solve_shaped_boxes(oracle, dev, m):
+    """box_qp<m> on every box shape against the oracle: same result code, free set and x (1e-9), rounding ties counted with
+    the budget of test_generic_device_boxqp; x in its box and, for a clearly positive definite Q, KKT at exits 5 / 6."""
+    N, n_tie, n_kkt, seen = 2100, 0, 0, set()
+    for t, shape, Q, c, x0, lo, hi in _problems(140 + m, m, N):
+        ro = oracle.boxqp(Q, c, x0, lo, hi)
+        r, x, vf = _generic(dev, Q, c, x0, lo, hi)
+        same = r == ro["result"] and np.array_equal(vf, ro["v_free"]) and _same_x(x, ro["x_opt"], 1e-9, 1e-12)
+        if not same:
+            assert r >= 1 and ro["result"] >= 1, (t, shape, r, ro["result"])
+            n_tie += 1
+        n_kkt += _check_invariants(Q, x, r, lo, hi, c, (t, shape))
+        seen.add((shape, int(r)))
+    assert n_tie <= N // 200, n_tie
+    assert n_kkt > N // 3, n_kkt
+    assert {s for s, _ in seen} == set(SHAPES)
+
+
+def test_m2_solver_on_solve_shaped_boxes(oracle, dev):
+    """box_qp2 (the double integrator's solver) on every box shape against the oracle and the generic solver."""
+    N, n_tie, n_kkt = 7000, 0, 0
+    for t, shape, Q, c, x0, lo, hi in _problems(240, 2, N):
+        ro = oracle.boxqp(Q, c, x0, lo, hi)
+        r, x, vf, mi, nf = _qp2(dev, Q, c, x0, lo, hi)
+        rg, xg, vfg = _generic(dev, Q, c, x0, lo, hi)
+        for rr, xx, vv in ((ro["result"], ro["x_opt"], ro["v_free"]), (rg, xg, vfg)):
+            same = (r == rr or {int(r), int(rr)} == {2, 4}) and np.array_equal(vf, vv) and _same_x(x, xx, 1e-9, 1e-12)
+            if not same:
+                assert r >= 1 and rr >= 1, (t, shape, r, rr)
+                n_tie += 1
+        n_kkt += _check_invariants(Q, x, r, lo, hi, c, (t, shape))
+    assert n_tie <= N // 150, n_tie
+    assert n_kkt > N // 3, n_kkt
+
+
+def test_scalar_solvers_on_solve_shaped_boxes(oracle, dev):
+    """box_qp_scalar and its straight-line fast path (the acrobot's solver) on every box shape against the oracle."""
+    N, n_tie, n_kkt = 7000, 0, 0
+    for t, shape, Q, c, x0, lo, hi in _problems(340, 1, N, indefinite_every=7):
+        ro = oracle.boxqp(Q, c, x0, lo, hi)
+        q = float(Q[0, 0])
+        for fn in (dev.devfn_box_qp_scalar, dev.devfn_box_qp_scalar_fast):
+            x, fr, mv = C.c_double(), C.c_int(), C.c_double()
+            r = fn(q, float(c[0]), float(x0[0]), float(lo[0]), float(hi[0]), C.byref(x), C.byref(fr), C.byref(mv))
+            assert r >= 0
+            xo = ro["x_opt"][0]
+            ok = fr.value == ro["v_free"][0] and (x.value == xo or abs(x.value - xo) <= 1e-12 * max(1, abs(x.value)))
+            code_ok = r == ro["result"] or (q <= 0 and {r, ro["result"]} == {2, 4})
+            if not (ok and code_ok):
+                assert r >= 1 and ro["result"] >= 1, (t, shape, r, ro["result"])
+                n_tie += 1
+            n_kkt += _check_invariants(Q, np.array([x.value]), r, lo, hi, c, (t, shape))
+    assert n_tie <= 4, n_tie
+    assert n_kkt > N // 2, n_kkt
+
+
+def test_float_solvers_on_solve_shaped_boxes(oracle, dev):
+    """The float instantiations (box_qp<1..4>, box_qp2, the scalar solver and its fast path) on every box shape (+-1e300 becomes
+    +-inf in float, as a float handle's limits do) against the oracle's float build, with the tie budget of
+    test_float_instantiation_against_the_fp32_oracle; x in its box whatever the shape.  One more kind of tie is counted apart:
+    same x and free set, but exit 5 (free gradient below 1e-8: in float that means exactly zero) on one side and 2 (no
+    improvement) on the other -- an unclamped minimum, common in unbounded boxes, where FMA contraction decides whether
+    Q x + c rounds to exactly 0."""
+    fp = C.POINTER(C.c_float)
+    for f in (dev.devfn_box_qp_scalar_f32, dev.devfn_box_qp_scalar_fast_f32):
+        f.argtypes = [C.c_float] * 5 + [fp, ip, fp]
+    N, n_tie, n_exit_tie = 0, 0, 0
+    f32 = lambda v: np.ascontiguousarray(v, dtype=np.float32)
+    with oracle.flavour("f32"):
+        for m in (1, 2, 3, 4):
+            for t, shape, Q, c, x0, lo, hi in _problems(440 + m, m, 1400, indefinite_every=0):
+                N += 1
+                with np.errstate(over="ignore"):
+                    Q, c, x0, lo, hi = f32(Q + 0.15 * np.eye(m)), f32(c), f32(x0), f32(lo), f32(hi)
+                ro = oracle.boxqp(Q, c, x0, lo, hi)
+                q = np.ascontiguousarray(Q.T).ravel()
+                x = np.zeros(m, dtype=np.float32)
+                vf = np.zeros(m, dtype=np.int32)
+                ptr = lambda a: a.ctypes.data_as(fp)
+                r = dev.devfn_box_qp_f32(m, ptr(q), ptr(c), ptr(x0), ptr(lo), ptr(hi), ptr(x), vf.ctypes.data_as(ip))
+                outs = [(r, x, vf)]
+                if m == 2:
+                    x2, vf2 = np.zeros(2, dtype=np.float32), np.zeros(2, dtype=np.int32)
+                    r2 = dev.devfn_box_qp2_f32(ptr(q), ptr(c), ptr(x0), ptr(lo), ptr(hi), ptr(x2), vf2.ctypes.data_as(ip))
+                    outs.append((r2, x2, vf2))
+                if m == 1:
+                    for fn in (dev.devfn_box_qp_scalar_f32, dev.devfn_box_qp_scalar_fast_f32):
+                        xs, fr, mv = C.c_float(), C.c_int(), C.c_float()
+                        rs = fn(float(Q[0, 0]), float(c[0]), float(x0[0]), float(lo[0]), float(hi[0]), C.byref(xs), C.byref(fr), C.byref(mv))
+                        outs.append((rs, np.array([xs.value], dtype=np.float32), np.array([fr.value], dtype=np.int32)))
+                for rr, xx, vv in outs:
+                    assert rr >= 1, (m, t, shape, rr)
+                    assert _in_box(xx, lo, hi), (m, t, shape, xx, lo, hi)
+                    same = np.array_equal(vv, ro["v_free"]) and _same_x(xx, ro["x_opt"], 2e-4, 2e-5)
+                    if same and {int(rr), int(ro["result"])} == {2, 5}:
+                        n_exit_tie += 1
+                    elif not same or (rr != ro["result"] and {int(rr), int(ro["result"])} != {2, 4}):
+                        assert ro["result"] >= 1, (m, t, shape, ro["result"])
+                        n_tie += 1
+    assert n_tie <= N // 100, (n_tie, N)
+    assert n_exit_tie <= N // 10, (n_exit_tie, N)

@@ -98,3 +98,30 @@ def test_full_solve_in_distribution(oracle, chain_lib):
     assert np.abs(it - ro["iters"]).max() <= 2
     assert np.median(rel) < 1e-6 and (rel < 1e-4).mean() >= 0.9, rel
     g.close()
+
+
+def test_a_box_per_control_walked_against_the_oracle_twin(oracle, chain_lib):
+    """Four controls with four different boxes -- asymmetric, pinned, an edge at 0, one excluding 0 -- on the generic kernels (k_backward_w3's
+    masked 4 x 4 box-QP, k_rollout_g): every pass's gains in the box of the trajectory it saw (tests/test_gpu_control_limits.py), and
+    iterations walked against the oracle twin with the same limits, both drives."""
+    from ilqr_amd import BatchILQR, capi
+    from tests.parity import walk_iterations
+    from tests.test_gpu_control_limits import Invariants, stepwise
+    B, T = 21, 60
+    lo, hi = np.array([-0.7, 0.4, 0.0, 0.2]), np.array([1.6, 0.4, 1.1, 0.9])
+    g = BatchILQR("user", B, T, DT, u_min=lo, u_max=hi, lib=chain_lib, nx=2 * NL, nu=NL // 2, user_params=PARAMS)
+    assert g.lib.ilqr_stage_kernel_name(g.h, capi.STAGE_NAMES.index("backward")) == b"k_backward_w3"
+    om = oracle.Model("chain", chain=(NL, PARAMS), u_min=lo, u_max=hi)
+    x0 = chain_x0(B, seed=12)
+    u0 = np.zeros((B, T, NL // 2))
+    inv = Invariants(lo, hi, "f64")
+    g.init_traj(x0, u0)
+    stepwise(g, 4, inv)
+    inv.done(min_checked=B)
+    for drive in ("oracle", "gpu"):
+        r = walk_iterations(oracle, om, g, x0, u0, DT, 4, drive=drive)
+        assert r["checked"] >= 3 * B, r["checked"]
+        ties = r["ties_backward"] + r["ties_search"] + r["ties_stop"]
+        assert ties <= max(2, r["checked"] // 10), r
+        assert r["cond_over10"] <= max(1, r["checked"] // 20) and r["unresolved"] == 0, r
+    g.close()

@@ -225,3 +225,35 @@ def test_generic_user_model_analytic_record(user6_lib, route):
     assert np.all(ex["fx"][:, T] == 0) and np.all(ex["cu"][:, T] == 0)
     rel = np.abs(out["fd"]["cost"] - out["exact"]["cost"]) / np.abs(out["exact"]["cost"])
     assert (rel < 1e-6).mean() > 0.9 and rel.max() < 1e-2, rel  # (a clamp tie on one side moves a trajectory: counted, not hidden)
+
+
+@pytest.mark.parametrize("route", ROUTES6)
+def test_user_twin_with_a_box_per_control(user6_lib, oracle, route):
+    """The n = 6, m = 2 twin with two different asymmetric boxes, one of them excluding 0 (k_backward_t's and the generic kernels' per-control
+    limits): every pass's gains in the box of the trajectory it saw (tests/test_gpu_control_limits.py), iterations walked against the
+    oracle's LQ model with the same limits, and the fp32 mode of the tiled kernels likewise checked for its boxes."""
+    from ilqr_amd import BatchILQR
+    from tests.parity import walk_iterations
+    from tests.test_gpu_control_limits import Invariants, stepwise
+    from tests.test_gpu_lq_end_to_end import dense_mats
+    n, m, B, T = 6, 2, 29, 50
+    lo, hi = np.array([-0.25, 0.05]), np.array([0.6, 0.45])
+    mats = dense_mats(n, m, seed=5)
+    params = np.concatenate([np.ascontiguousarray(a).ravel() for a in mats])
+    rng = np.random.default_rng(7)
+    x0 = rng.uniform(-1, 1, (B, n))
+    u0 = rng.normal(size=(B, T, m)) * 0.1
+    dtypes = ("f64", "f32") if route == "thread" else ("f64",)
+    for dtype in dtypes:
+        g = BatchILQR("user", B, T, DT, u_min=lo, u_max=hi, lib=user6_lib, nx=n, nu=m, user_params=params, route=_route6(route), dtype=dtype)
+        _kernels6(g, route)
+        inv = Invariants(lo, hi, dtype)
+        g.init_traj(x0, u0)
+        stepwise(g, 4, inv)
+        inv.done(min_checked=B)
+        if dtype == "f64":
+            om = oracle.Model("lq", lq=mats, u_min=lo, u_max=hi)
+            for drive in ("oracle", "gpu"):
+                r = walk_iterations(oracle, om, g, x0, u0, DT, 5, drive=drive)
+                assert r["checked"] >= 3 * B and len(r["tied"]) <= B // 8, r
+        g.close()
