@@ -90,7 +90,11 @@ USER_EXAMPLE6_LIB = os.path.join(PKG, "lib", "libilqr_amd_user_linear6.so")
 # a user twin that is neither small nor linear-quadratic (n = 16, m = 4: a chain of coupled pendulums): the generic kernels, point-by-point finite differences
 USER_CHAIN_HEADER = os.path.join(os.path.dirname(PKG), "examples", "user_model_pendulum_chain.hpp")
 USER_CHAIN_LIB = os.path.join(PKG, "lib", "libilqr_amd_user_chain.so")
-USER_BUILDS = ((USER_EXAMPLE_HEADER, USER_EXAMPLE_LIB), (USER_EXAMPLE6_HEADER, USER_EXAMPLE6_LIB), (USER_CHAIN_HEADER, USER_CHAIN_LIB))
+# a user twin with more than 16 controls (n = 24, m = 20): the generic kernels with the two-control-tile backward pass
+USER_WIDE_HEADER = os.path.join(os.path.dirname(PKG), "examples", "user_model_linear_wide.hpp")
+USER_WIDE_LIB = os.path.join(PKG, "lib", "libilqr_amd_user_linear_wide.so")
+USER_BUILDS = ((USER_EXAMPLE_HEADER, USER_EXAMPLE_LIB), (USER_EXAMPLE6_HEADER, USER_EXAMPLE6_LIB), (USER_CHAIN_HEADER, USER_CHAIN_LIB),
+               (USER_WIDE_HEADER, USER_WIDE_LIB))
 
 
 def build_all(verbose=False):

@@ -34,6 +34,10 @@ namespace ilqr {
 constexpr int WN = 32, WM = 16;   // maximum dimensions of this kernel
 constexpr int LDN = WN + 1;       // leading dimension of LDS matrices with up to 32 rows
 constexpr int LDM = WM + 1;       // ... with up to 16 rows
+// Handles with 16 < nu <= 32 (two 16-column control tiles: k_backward_w3w, backward_wave3.hpp) use a layout of their own; the
+// constants above, and every kernel sized by them, are what nu <= 16 runs
+constexpr int WMW = 32;           // controls of the two-tile layout
+constexpr int LDMW = WMW + 1;     // leading dimension of its m x m / m x n LDS matrices
 
 // Matrices share storage with ones that are dead by the time they are written, which brings a
 // wavefront's LDS from 68 KB to 39.6 KB, i.e. from two to FOUR wavefronts per CU (160 KB; one per
@@ -171,6 +175,13 @@ __device__ __forceinline__ double wave_sum_row0(double v) {
   const double r0 = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 0), __builtin_amdgcn_readlane(__double2loint(v), 0));
   return (r0 + 0.0) + 0.0;
 }
+// the sum of a value indexed by a control of a W-wide layout (zero outside lanes 0..W-1): W = 16 fetches row 0 only (wave_sum_row0),
+// W = 32 all four rows in wave_sum's fixed order (rows 2 and 3 total +0.0)
+template <int W>
+__device__ __forceinline__ double wave_sum_ctrl(double v) {
+  static_assert(W == WM || W == WMW, "16 or 32 controls");
+  if constexpr (W == WM) return wave_sum_row0(v); else return wave_sum(v);
+}
 __device__ __forceinline__ void lds_sync() {
   // One wavefront per block: the LDS pipeline executes a wavefront's DS instructions in issue
   // order, so a ds_read after a ds_write sees it whichever lane wrote.  Only the COMPILER has to be
@@ -220,21 +231,26 @@ __device__ __forceinline__ double dot_padded(FA a, FB b) {
   return s;
 }
 
-// 0.5 x'Qx + x.c with Q m x m (ld LDM), include/boxqp.h:53-55, evaluated ((0.5 x')Q) x + x.c
+// 0.5 x'Qx + x.c with Q m x m (ld W + 1), include/boxqp.h:53-55, evaluated ((0.5 x')Q) x + x.c
+template <int W = WM>
 __device__ __forceinline__ double w_quad_cost(int m, const double* Q, const double* c, const double* x, int lane) {
+  constexpr int LD = W + 1;
   double part = 0, lin = 0;
   if (lane < m) {
-    const double r = dot_padded([&](int i) { return 0.5 * x[i]; }, [&](int i) { return Q[i + LDM * lane]; });
+    const double r = dot_padded<W>([&](int i) { return 0.5 * x[i]; }, [&](int i) { return Q[i + LD * lane]; });
     part = r * x[lane];
     lin = x[lane] * c[lane];
   }
-  return wave_sum_row0(part) + wave_sum_row0(lin);
+  return wave_sum_ctrl<W>(part) + wave_sum_ctrl<W>(lin);
 }
 
 // src/boxqp.cpp:26-139 for one trajectory per wavefront.  Inputs in LDS: QuuF (Q), Qu (c), kprev
-// (x0), lo, hi.  Outputs: L.x (solution), L.vfree, L.Minv (R^-1 R^-T of the last factor, ld LDM), nfR.
-template <class LDS>
+// (x0), lo, hi.  Outputs: L.x (solution), L.vfree, L.Minv (R^-1 R^-T of the last factor, ld W + 1), nfR.
+// W: the control width of the layout (WM = 16, or WMW = 32 for the two-tile kernel k_backward_w3w); m <= W.
+template <class LDS, int W = WM>
 __device__ int w_box_qp(int m, LDS& L, int lane, int& nfR_out ILQR_W2CLOCK_ARG, int* nfact_out = nullptr, int fixes = 0) {
+  static_assert(W == WM || W == WMW, "16 or 32 controls");
+  constexpr int LD = W + 1;
   ILQR_QCOUNT(0)
   const double* Q = L.QuuF();
   const double* c = L.Qu;
@@ -251,11 +267,11 @@ __device__ int w_box_qp(int m, LDS& L, int lane, int& nfR_out ILQR_W2CLOCK_ARG, 
   {
     double part = 0, lin = 0;
     if (lane < m) {
-      const double r = dot_padded([&](int i) { return L.x[i]; }, [&](int i) { return Q[i + LDM * lane]; });
+      const double r = dot_padded<W>([&](int i) { return L.x[i]; }, [&](int i) { return Q[i + LD * lane]; });
       part = r * L.x[lane];
       lin = L.x[lane] * c[lane];
     }
-    val = wave_sum_row0(part) + wave_sum_row0(lin);
+    val = wave_sum_ctrl<W>(part) + wave_sum_ctrl<W>(lin);
   }
   double oldvalue = 0;
   int result = 0, nfR = 0;
@@ -270,7 +286,7 @@ __device__ int w_box_qp(int m, LDS& L, int lane, int& nfR_out ILQR_W2CLOCK_ARG, 
     int cl = 1;
     double dd = 0;
     if (lane < m) {
-      const double s = dot_padded([&](int j) { return Q[lane + LDM * j]; }, [&](int j) { return L.x[j]; });
+      const double s = dot_padded<W>([&](int j) { return Q[lane + LD * j]; }, [&](int j) { return L.x[j]; });
       const double g = s + c[lane];
       L.grad[lane] = g;
       const double oldcl = L.clamped[lane];  // (lane-local: first pass reads the 0 written above)
@@ -283,7 +299,7 @@ __device__ int w_box_qp(int m, LDS& L, int lane, int& nfR_out ILQR_W2CLOCK_ARG, 
     oldvalue = val;
     const unsigned long long free_mask = __ballot(lane < m && !cl);
     const int nf = __popcll(free_mask);
-    const double dsum = wave_sum_row0(dd);
+    const double dsum = wave_sum_ctrl<W>(dd);
     if (nf == 0) {  // :74-77
       result = 6;
       break;
@@ -301,11 +317,11 @@ __device__ int w_box_qp(int m, LDS& L, int lane, int& nfR_out ILQR_W2CLOCK_ARG, 
       auto bcast = [&](double v, int l) {
         return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
       };
-      double row[WM];
+      double row[W];
       {
         const int gi = L.idx[(lane < nf) ? lane : 0];
 #pragma unroll
-        for (int j = 0; j < WM; j++) row[j] = (lane < nf && j < nf) ? Q[gi + LDM * L.idx[(j < nf) ? j : 0]] : 0.0;
+        for (int j = 0; j < W; j++) row[j] = (lane < nf && j < nf) ? Q[gi + LD * L.idx[(j < nf) ? j : 0]] : 0.0;
       }
       // Eigen llt_inplace<Lower>::unblocked (Cholesky/LLT.h:302-325); stops at a non-positive pivot
       // and leaves the rest of the lower triangle as it was.
@@ -317,9 +333,9 @@ __device__ int w_box_qp(int m, LDS& L, int lane, int& nfR_out ILQR_W2CLOCK_ARG, 
       {
         bool stopped = false;
 #pragma unroll
-        for (int k = 0; k < WM; k++) {
+        for (int k = 0; k < W; k++) {
           if (k < nf && !stopped) {
-            double rk[WM];
+            double rk[W];
             double sq = 0;
 #pragma unroll
             for (int j = 0; j < k; j++) {
@@ -358,41 +374,51 @@ __device__ int w_box_qp(int m, LDS& L, int lane, int& nfR_out ILQR_W2CLOCK_ARG, 
       // is computed here and kept (same values) -- for the iterations that reuse a stale factor and
       // for the caller's K.  R(i, l2) = L(l2, i) = lane l2's row[i].
       {
-        double ri[WM];
+        double ri[W];
 #pragma unroll
-        for (int i = 0; i < WM; i++) ri[i] = 0.0;
+        for (int i = 0; i < W; i++) ri[i] = 0.0;
 #pragma unroll
-        for (int i = WM - 1; i >= 0; i--) {
+        for (int i = W - 1; i >= 0; i--) {
           if (i < nfR) {
             // 1 / R(i, i): kept from the factorisation; a pivot the factorisation stopped before (Eigen's partial factor: its
             // "root" is the unmodified entry) gets a reciprocal of its own
             const double inv_rii = (i < n_fact) ? bcast(my_inv, i) : recip(bcast(row[i], i));
             double s = 0;
 #pragma unroll
-            for (int l2 = i + 1; l2 < WM; l2++) s = __builtin_fma(bcast(row[i], l2), ri[l2], s);
+            for (int l2 = i + 1; l2 < W; l2++) s = __builtin_fma(bcast(row[i], l2), ri[l2], s);
             const double off = -s * inv_rii;
             ri[i] = (lane >= nfR) ? 0.0 : ((lane == i) ? inv_rii : ((lane > i) ? off : 0.0));
           }
         }
-        if (lane < WM) {
+        if (lane < W) {
 #pragma unroll
-          for (int i = 0; i < WM; i++) L.Ri()[i + LDM * lane] = ri[i];
+          for (int i = 0; i < W; i++) L.Ri()[i + LD * lane] = ri[i];
         }
       }
       lds_sync();
-      {
-        const double4_t acc = mfma_tile<WM / 4>([&](int i, int k) { return L.Ri()[i + LDM * k]; },
-                                                [&](int k, int j) { return L.Ri()[j + LDM * k]; }, lane);
+      if constexpr (W == WM) {
+        const double4_t acc = mfma_tile<WM / 4>([&](int i, int k) { return L.Ri()[i + LD * k]; },
+                                                [&](int k, int j) { return L.Ri()[j + LD * k]; }, lane);
         const int col = lane & 15, r0 = lane >> 4;
 #pragma unroll
-        for (int r = 0; r < 4; r++) L.Minv()[(r0 + 4 * r) + LDM * col] = acc[r];
+        for (int r = 0; r < 4; r++) L.Minv()[(r0 + 4 * r) + LD * col] = acc[r];
+      } else {  // 2 x 2 output tiles of 16 x 16, eight k-steps each
+        static_for<W / 16>([&](auto ti) {
+          static_for<W / 16>([&](auto tj) {
+            const double4_t acc = mfma_tile<W / 4>([&](int i, int k) { return L.Ri()[16 * ti + i + LD * k]; },
+                                                   [&](int k, int j) { return L.Ri()[16 * tj + j + LD * k]; }, lane);
+            const int col = lane & 15, r0 = lane >> 4;
+#pragma unroll
+            for (int r = 0; r < 4; r++) L.Minv()[(16 * ti + r0 + 4 * r) + LD * (16 * tj + col)] = acc[r];
+          });
+        });
       }
       lds_sync();
       ILQR_QMARK(2)
     }
     // :93-97
     {
-      const double gn2 = wave_sum_row0((lane < m && !cl) ? L.grad[lane] * L.grad[lane] : 0.0);
+      const double gn2 = wave_sum_ctrl<W>((lane < m && !cl) ? L.grad[lane] * L.grad[lane] : 0.0);
       if (grad_norm_below_min(gn2)) {  // sqrt(gn2) < minGrad, boxqp.hpp
         result = 5;
         break;
@@ -402,7 +428,7 @@ __device__ int w_box_qp(int m, LDS& L, int lane, int& nfR_out ILQR_W2CLOCK_ARG, 
     if (lane < m) L.tmp[lane] = L.x[lane] * L.clamped[lane];
     lds_sync();
     if (lane < m) {
-      const double s = dot_padded([&](int j) { return Q[lane + LDM * j]; }, [&](int j) { return L.tmp[j]; });
+      const double s = dot_padded<W>([&](int j) { return Q[lane + LD * j]; }, [&](int j) { return L.tmp[j]; });
       L.gc[lane] = s + c[lane];
     }
     lds_sync();
@@ -417,7 +443,7 @@ __device__ int w_box_qp(int m, LDS& L, int lane, int& nfR_out ILQR_W2CLOCK_ARG, 
     lds_sync();
     // :103-119 search(free) = -(R^-1 R^-T) gc(free) - x(free)   (a stale factor of equal size is used as is)
     if (lane < nfR && lane < nf) {
-      const double s = dot_masked(0, (nfR < nf) ? nfR : nf, [&](int l2) { return -L.Minv()[lane + LDM * l2]; }, [&](int l2) { return L.gfree[l2]; });
+      const double s = dot_masked<W>(0, (nfR < nf) ? nfR : nf, [&](int l2) { return -L.Minv()[lane + LD * l2]; }, [&](int l2) { return L.gfree[l2]; });
       L.search[L.idx[lane]] = s - L.xfree[lane];
     }
     lds_sync();
@@ -428,10 +454,10 @@ __device__ int w_box_qp(int m, LDS& L, int lane, int& nfR_out ILQR_W2CLOCK_ARG, 
     {
       double sl = 0;
       if (lane < m) {
-        const double s = dot_padded([&](int j) { return Q[lane + LDM * j]; }, [&](int j) { return L.x[j]; });
+        const double s = dot_padded<W>([&](int j) { return Q[lane + LD * j]; }, [&](int j) { return L.x[j]; });
         sl = L.search[lane] * (s + c[lane]);
       }
-      const double slope = wave_sum_row0(sl);
+      const double slope = wave_sum_ctrl<W>(sl);
       if (slope >= 0) {
         failed = true;
       } else {
@@ -442,8 +468,8 @@ __device__ int w_box_qp(int m, LDS& L, int lane, int& nfR_out ILQR_W2CLOCK_ARG, 
           L.xc[lane] = (L.hi[lane] < a) ? L.hi[lane] : a;
         }
         lds_sync();
-        v = w_quad_cost(m, Q, c, L.xc, lane);
-        const double old_v = w_quad_cost(m, Q, c, L.x, lane);
+        v = w_quad_cost<W>(m, Q, c, L.xc, lane);
+        const double old_v = w_quad_cost<W>(m, Q, c, L.x, lane);
         while ((v - old_v) > kArmijo * (step * slope)) {  // (the reference's quotient test without the division: step * slope < 0 here; boxqp.hpp)
           step *= kStepDec;
           ILQR_QCOUNT(3)
@@ -454,7 +480,7 @@ __device__ int w_box_qp(int m, LDS& L, int lane, int& nfR_out ILQR_W2CLOCK_ARG, 
             L.xc[lane] = (L.hi[lane] < a) ? L.hi[lane] : a;
           }
           lds_sync();
-          v = w_quad_cost(m, Q, c, L.xc, lane);
+          v = w_quad_cost<W>(m, Q, c, L.xc, lane);
           if (step < kMinStep) {
             failed = true;
             break;

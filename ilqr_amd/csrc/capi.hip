@@ -16,6 +16,7 @@
 #include "backward_wave.hpp"
 #include "backward_wave2.hpp"
 #include "backward_wave3.hpp"
+#include "backward_wave3w.hpp"
 #include "generic.hpp"
 #include "kernels_wide.hpp"
 #include "kernels_wide2.hpp"
@@ -100,12 +101,14 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
   h->route.unfused = false;
   h->route.backward_w2 = (d->route & ILQR_ROUTE_BACKWARD_W2) != 0;
   h->route.lq_dense_fd = (d->route & ILQR_ROUTE_LQ_DENSE_FD) != 0;
-  h->route.lq_thread_rollout = (d->route & ILQR_ROUTE_LQ_THREAD_ROLLOUT) != 0;
+  h->lq_wide = d->model == ILQR_MODEL_LQ && d->nu > WM;  // the LQ twin beyond 16 controls: LqModelW on the generic kernels
+  h->route.lq_thread_rollout = (d->route & ILQR_ROUTE_LQ_THREAD_ROLLOUT) != 0 || h->lq_wide;  // (k_rollout_lq is written for 32 x 16)
   h->route.full_records = (d->route & ILQR_ROUTE_FULL_RECORDS) != 0;
   h->route.no_compaction = (d->route & ILQR_ROUTE_NO_COMPACTION) != 0;
   h->route.quad_chain = (d->route & ILQR_ROUTE_QUAD_CHAIN) != 0;
   h->route.fused = d->route & 3;
   h->route.wide_occ = (d->route & ILQR_ROUTE_WIDE_ONE_PER_CU) ? 1 : (d->route & ILQR_ROUTE_WIDE_TWO_PER_CU) ? 2 : 0;
+  h->route.two_control_tiles = d->nu > WM || (d->route & ILQR_ROUTE_TWO_CONTROL_TILES) != 0;  // (generic handles only: the nx = 4 kernels ignore it)
   if (d->assume_cus > 0) h->num_cus = d->assume_cus;
   h->device = d->device;
   if (d->stream) {
@@ -117,6 +120,15 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
   h->model = d->model;
   h->dtype = d->dtype;
   if (d->dtype != ILQR_DTYPE_F64 && d->dtype != ILQR_DTYPE_F32) return fail(ILQR_ERR_INVALID, "dtype %d: ILQR_DTYPE_F64 or ILQR_DTYPE_F32", d->dtype);
+  if (d->nu > WM) {  // 16 < nu <= 32: the generic backward pass with two control tiles (k_backward_w3w); what is not widened says so
+    const char* what = (d->dtype == ILQR_DTYPE_F32) ? "fp32" : (d->route & ILQR_ROUTE_BACKWARD_W2) ? "ILQR_ROUTE_BACKWARD_W2" : (d->route & ILQR_ROUTE_LQ_DENSE_FD) ? "ILQR_ROUTE_LQ_DENSE_FD"
+                       : (d->flags & ILQR_FLAG_REGULARIZE_VXX) ? "ILQR_FLAG_REGULARIZE_VXX" : nullptr;
+    if (what) return fail(ILQR_ERR_UNSUPPORTED, "%s supports at most %d controls (nu = %d)", what, WM, d->nu);
+  }
+  if ((d->route & ILQR_ROUTE_TWO_CONTROL_TILES) && (d->route & ILQR_ROUTE_BACKWARD_W2))
+    return fail(ILQR_ERR_UNSUPPORTED, "ILQR_ROUTE_TWO_CONTROL_TILES and ILQR_ROUTE_BACKWARD_W2 name two different backward kernels");
+  if ((d->route & ILQR_ROUTE_TWO_CONTROL_TILES) && (d->flags & ILQR_FLAG_REGULARIZE_VXX))
+    return fail(ILQR_ERR_UNSUPPORTED, "ILQR_FLAG_REGULARIZE_VXX is implemented in k_backward_w3 (at most 16 controls): drop ILQR_ROUTE_TWO_CONTROL_TILES");
   if (d->dtype == ILQR_DTYPE_F32 && d->model != ILQR_MODEL_ACROBOT && d->model != ILQR_MODEL_DOUBLE_INTEGRATOR && d->model != ILQR_MODEL_USER)
     return fail(ILQR_ERR_UNSUPPORTED, "fp32 is available for the nx = 4 device models (acrobot, double integrator); the generic nx <= 32 path is fp64");
   h->nx = d->nx;
@@ -196,7 +208,7 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
     // Generic dimensions: trajectory-contiguous layout, one wavefront per trajectory in the backward
     // pass.  Host-evaluated models receive their derivatives through ilqr_set_derivatives; the LQ
     // model has a device twin (generic.hpp) and runs end to end.
-    REQUIRE(d->nx <= WN && d->nu <= WM, "generic kernels: nx <= %d, nu <= %d", WN, WM);
+    REQUIRE(d->nx <= WN && d->nu <= WMW, "generic kernels: nx <= %d, nu <= %d", WN, WMW);
     REQUIRE(d->u_min && d->u_max, "generic handles need u_min/u_max (Model::u_min/u_max, include/model.h:17)");
     if (d->model == ILQR_MODEL_LQ)
       REQUIRE(d->lq_A && d->lq_B && d->lq_Q && d->lq_R && d->lq_Qf, "ILQR_MODEL_LQ needs lq_A, lq_B, lq_Q, lq_R, lq_Qf");
@@ -244,9 +256,10 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
     }
     rc |= dev_alloc(h, &v.cost_c, (size_t)NALPHA * Bp);  // the 11 candidate costs (device or caller-evaluated)
     if (d->model == ILQR_MODEL_LQ) {
-      // zero-padded copies of the model matrices at the kernels' maximum dimensions
+      // zero-padded copies of the model matrices at the kernels' maximum dimensions (B, R: GM columns, or GMW for the wide twin)
       double* pad = nullptr;
-      const size_t nA = GN * GN, nB = GN * GM, nR = GM * GM, tot = 3 * nA + nB + nR;
+      const size_t GMC = h->lq_wide ? GMW : GM;
+      const size_t nA = GN * GN, nB = GN * GMC, nR = GMC * GMC, tot = 3 * nA + nB + nR;
       rc |= dev_alloc(h, &pad, tot);
       if (!rc) {
         std::vector<double> hp(tot, 0.0);
@@ -257,10 +270,10 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
             pQ[i * GN + j] = d->lq_Q[i * nx + j];
             pQf[i * GN + j] = d->lq_Qf[i * nx + j];
           }
-          for (size_t j = 0; j < nu; j++) pB[i * GM + j] = d->lq_B[i * nu + j];
+          for (size_t j = 0; j < nu; j++) pB[i * GMC + j] = d->lq_B[i * nu + j];
         }
         for (size_t i = 0; i < nu; i++)
-          for (size_t j = 0; j < nu; j++) pR[i * GM + j] = d->lq_R[i * nu + j];
+          for (size_t j = 0; j < nu; j++) pR[i * GMC + j] = d->lq_R[i * nu + j];
         // on the handle's stream, behind dev_alloc's zero fill of the same buffer (a copy on the null
         // stream could be overtaken by it: the stream is non-blocking); hp must outlive the copy
         if (hipMemcpyAsync(pad, hp.data(), tot * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
@@ -275,6 +288,15 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
         h->lq.Qf = pad + 2 * nA + nB + nR;
         h->lq.umin = h->d_umin;
         h->lq.umax = h->d_umax;
+        h->lq_w.nx = (int)nx;
+        h->lq_w.nu = (int)nu;
+        h->lq_w.A = h->lq.A;
+        h->lq_w.Bm = h->lq.Bm;
+        h->lq_w.Q = h->lq.Q;
+        h->lq_w.R = h->lq.R;
+        h->lq_w.Qf = h->lq.Qf;
+        h->lq_w.umin = h->d_umin;
+        h->lq_w.umax = h->d_umax;
       }
     }
     if (!rc) {
@@ -335,7 +357,7 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
   hipLaunchKernelGGL(k_reset_state<double>, dim3((h->Bp + 255) / 256), dim3(256), 0, h->stream, h->v, h->params.lambda_init,
                      h->params.dlambda_init);
   HIPCHK(hipGetLastError());
-  h->lq_fused = h->model == ILQR_MODEL_LQ && v.analytic && !h->route.full_records && !h->route.backward_w2 && !(h->sp.fixes & 4);
+  h->lq_fused = h->model == ILQR_MODEL_LQ && v.analytic && !h->route.full_records && !h->route.backward_w2 && !(h->sp.fixes & 4) && !h->route.two_control_tiles;
   if (h->lq_fused) {  // both constant records, once (what = 3)
     hipLaunchKernelGGL(k_analytic_lq, dim3(1), dim3(64), 0, h->stream, h->v, h->lq, 1, 3, h->const_rec, kAnalyticChunk);
     HIPCHK(hipGetLastError());
@@ -349,7 +371,7 @@ int ilqr_create(const ilqr_desc* d, ilqr_batch** out) {
   *out = nullptr;
   REQUIRE(d->abi_version == ILQR_AMD_ABI_VERSION, "ABI version %d, library is %d", d->abi_version, ILQR_AMD_ABI_VERSION);
   REQUIRE(d->B >= 1 && d->T >= 1 && d->nx >= 1 && d->nu >= 1, "B, T, nx, nu must be positive");
-  REQUIRE(d->nx <= MAXN && d->nu <= MAXM, "nx <= %d and nu <= %d", MAXN, MAXM);
+  REQUIRE(d->nx <= MAXN && d->nu <= kMaxControls, "nx <= %d and nu <= %d", MAXN, kMaxControls);
   REQUIRE(d->dt > 0, "dt must be positive");
   if (d->route & 128)  // (ILQR_ROUTE_BACKWARD_LDS of ABI <= 4)
     return fail(ILQR_ERR_UNSUPPORTED, "route bit 128 (round 1's LDS kernel k_backward_w) was retired in ABI 5: ILQR_ROUTE_BACKWARD_W2 gives the same bits");

@@ -218,6 +218,84 @@ struct LqModel {
   }
 };
 
+// The LQ twin with 16 < nu <= 32 (GMW = 32 columns of B, a 32 x 32 R): the same model, run by the generic kernels only --
+// thread-per-rollout k_rollout_g (the accepted rollout re-run to commit it), point-by-point finite differences k_derivatives_g, and
+// k_backward_w3w on whole per-knot records.  It promises no structure to the sweep (the matrix-core LQ kernels are written for 32 x 16);
+// its sums are LqModel's (left to right over the column index, padding adding exact zeros at the end).
+constexpr int GMW = 32;
+struct LqModelW {
+  using real = double;
+  static constexpr int NX = GN, NU = GMW;
+  int nx, nu;
+  const double *A, *Bm, *Q, *R, *Qf;  // device: [GN][GN], [GN][GMW], [GN][GN], [GMW][GMW], [GN][GN]
+  const double *umin = nullptr, *umax = nullptr;
+  static constexpr bool kSeparableCost = false, kQuadraticCostX = false, kLinearDynamics = false, kHasAnalyticRecord = true;
+  __device__ __forceinline__ double limit_lo(int j) const { return umin[j]; }
+  __device__ __forceinline__ double limit_hi(int j) const { return umax[j]; }
+  __device__ __forceinline__ void dynamics(const double* x, const double* u, double* dx) const {
+    cmem_d* a = (cmem_d*)A;
+    cmem_d* bm = (cmem_d*)Bm;
+#pragma unroll
+    for (int i = 0; i < GN; i += 4) {
+      double acc[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int j = 0; j < GN; j++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) acc[q] += a[(i + q) * GN + j] * x[j];
+#pragma unroll
+      for (int j = 0; j < GMW; j++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) acc[q] += bm[(i + q) * GMW + j] * u[j];
+#pragma unroll
+      for (int q = 0; q < 4; q++) dx[i + q] = acc[q];
+    }
+  }
+  __device__ __forceinline__ double cost_x(const double* x) const { return LqModel::quad<GN>((cmem_d*)Q, x); }
+  __device__ __forceinline__ double cost_u(const double* u) const { return LqModel::quad<GMW>((cmem_d*)R, u); }
+  static __device__ __forceinline__ double cost_from_parts(double qx, double qu) { return 0.5 * (qx + qu); }
+  __device__ __forceinline__ double cost(const double* x, const double* u) const { return cost_from_parts(cost_x(x), cost_u(u)); }
+  __device__ __forceinline__ void cost2(const double* xa, const double* ua, const double* xb, const double* ub, double& fa, double& fb) const {
+    double qa, qb, ra, rb;
+    LqModel::quad2<GN>((cmem_d*)Q, xa, xb, qa, qb);
+    LqModel::quad2<GMW>((cmem_d*)R, ua, ub, ra, rb);
+    fa = cost_from_parts(qa, ra);
+    fb = cost_from_parts(qb, rb);
+  }
+  __device__ __forceinline__ double final_cost(const double* x) const { return 0.5 * LqModel::quad<GN>((cmem_d*)Qf, x); }
+  // LqModel::analytic_record with B's and R's leading dimension GMW
+  __device__ __forceinline__ void analytic_record(const double* __restrict__ x, const double* __restrict__ u, double dt, bool last,
+                                                  double* __restrict__ D, int lane) const {
+    const int oFX = 0, oFU = oFX + nx * nx, oCX = oFU + nx * nu, oCXX = oCX + nx, oCXU = oCXX + nx * nx, oCU = oCXU + nx * nu,
+              oCUU = oCU + nu;
+    const double* Wx = last ? Qf : Q;
+    for (int e = lane; e < nx * nx; e += 64) {
+      const int r = e % nx, c = e / nx;
+      D[oFX + e] = last ? 0.0 : ((r == c) ? 1.0 : 0.0) + dt * A[r * GN + c];
+      D[oCXX + e] = 0.5 * (Wx[r * GN + c] + Wx[c * GN + r]);
+    }
+    for (int e = lane; e < nx * nu; e += 64) {
+      const int r = e % nx, c = e / nx;
+      D[oFU + e] = last ? 0.0 : dt * Bm[r * GMW + c];
+      D[oCXU + e] = 0.0;
+    }
+    for (int e = lane; e < nu * nu; e += 64) {
+      const int r = e % nu, c = e / nu;
+      D[oCUU + e] = 0.5 * (R[r * GMW + c] + R[c * GMW + r]);
+    }
+    for (int i = lane; i < nx; i += 64) {
+      double acc = 0;
+      for (int j = 0; j < nx; j++) acc += 0.5 * (Wx[i * GN + j] + Wx[j * GN + i]) * x[j];
+      D[oCX + i] = acc;
+    }
+    for (int i = lane; i < nu; i += 64) {
+      double acc = 0;
+      if (!last)
+        for (int j = 0; j < nu; j++) acc += 0.5 * (R[i * GMW + j] + R[j * GMW + i]) * u[j];
+      D[oCU + i] = acc;
+    }
+  }
+};
+
 // ------------------------------------------------------------------------------------------
 // forward rollout
 // ------------------------------------------------------------------------------------------

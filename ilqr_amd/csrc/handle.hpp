@@ -45,6 +45,8 @@ struct ilqr_batch {
   AcrobotModelT<float> acrobot_f;          // fp32 handle: what the rollouts integrate
   DoubleIntegratorModelT<float> dint_f;
   LqModel lq;                   // ILQR_MODEL_LQ: padded matrices on the device
+  LqModelW lq_w;                // ... with 16 < nu <= 32 (lq_wide): B and R padded to 32 columns, the generic kernels only
+  bool lq_wide = false;
 #ifdef ILQR_HAVE_USER_MODEL
   UserModelT<double> user;      // ILQR_MODEL_USER: the build's user device twin (fp32 handle: the twin the finite differences are taken in)
   GenericModelOf<UserModelT<double>> user_g;  // ... as the generic kernels take it (any NX <= 32, NU <= 16 that is not a tiled nx = 4 shape)
@@ -102,6 +104,7 @@ struct ilqr_batch {
     bool staged = false, unfused = false, backward_w2 = false, lq_dense_fd = false, lq_thread_rollout = false, full_records = false, no_compaction = false, quad_chain = false;
     int fused = 0;  // 0 = by batch size
     int wide_occ = 0;  // wide tiles per CU: 0 = by batch size
+    bool two_control_tiles = false;  // generic backward pass: k_backward_w3w (two 16-column control tiles) -- what nu > 16 always runs
   } route;
   StageTimer timers[ILQR_NUM_STAGES];
   std::vector<hipEvent_t> event_pool;

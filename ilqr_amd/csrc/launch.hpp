@@ -36,7 +36,7 @@ static bool generic_twin(const ilqr_batch* h) {
 // f(model) for the handle's generic device twin
 template <class F>
 static int with_generic_model(ilqr_batch* h, F&& f) {
-  if (h->model == ILQR_MODEL_LQ) return f(h->lq);
+  if (h->model == ILQR_MODEL_LQ) return h->lq_wide ? f(h->lq_w) : f(h->lq);
 #ifdef ILQR_HAVE_USER_MODEL
   if constexpr (kUserGeneric)
     if (h->model == ILQR_MODEL_USER) return f(h->user_g);
@@ -160,14 +160,14 @@ static int launch_derivatives(ilqr_batch* h, int force) {
   dim3 grid((h->T + 1 + 15) / 16, h->ntiles), block(256);
   const int* ci = h->commit_pending ? h->commit_idx : nullptr;
   if (generic_twin(h)) {
-    if (h->v.analytic && h->model == ILQR_MODEL_LQ) {
+    if (h->v.analytic && h->model == ILQR_MODEL_LQ && !h->lq_wide) {
       const int what = h->route.full_records ? 0 : 1;  // (A/B runs and the bit-identity test)
       const int chunk = (what == 1) ? 4 * kAnalyticChunk : kAnalyticChunk;
       const int nchunk = (h->T + 1 + chunk - 1) / chunk;
       hipLaunchKernelGGL(k_analytic_lq, dim3(h->B * nchunk), dim3(64), 0, h->stream, h->v, h->lq, force, what, h->const_rec, chunk);
       h->records_partial = (what == 1);
     } else {
-      if (h->model == ILQR_MODEL_LQ && !h->route.lq_dense_fd) {
+      if (h->model == ILQR_MODEL_LQ && !h->route.lq_dense_fd && !h->lq_wide) {
         // the LQ twin: every perturbed point of the knots t < T evaluated by what moved (k_derivatives_lq), knot T by the generic sweep
         const int nchunk = (h->T + kLqKnotsPerWave - 1) / kLqKnotsPerWave;
         hipLaunchKernelGGL(k_derivatives_lq, dim3(h->B * nchunk), dim3(64), 0, h->stream, h->v, h->lq, force);
@@ -214,7 +214,12 @@ static int launch_backward(ilqr_batch* h, int mode) {
     const dim3 grid(h->B), block(64);
     const bool full = h->nu == WM && (h->nx == 16 || h->nx == 32);
 #define ILQR_W3(NT_, FULL_, LQF_) hipLaunchKernelGGL((k_backward_w3<NT_, FULL_, LQF_>), grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec)
-    if (h->route.backward_w2 && h->nx > 16)
+    if (h->route.two_control_tiles) {  // nu > 16, or ILQR_ROUTE_TWO_CONTROL_TILES (ilqr_create keeps lq_fused, W2 and REGULARIZE_VXX off here)
+      if (h->nx > 16)
+        hipLaunchKernelGGL(k_backward_w3w<2>, grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec);
+      else
+        hipLaunchKernelGGL(k_backward_w3w<1>, grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec);
+    } else if (h->route.backward_w2 && h->nx > 16)
       hipLaunchKernelGGL(k_backward_w2<2>, grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec);
     else if (h->route.backward_w2)
       hipLaunchKernelGGL(k_backward_w2<1>, grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec);

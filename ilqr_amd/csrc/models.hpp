@@ -371,7 +371,7 @@ struct has_analytic_record<M, std::void_t<decltype(std::declval<const M&>().anal
 //     template <class real_> struct UserModelT {
 //       using real = real_;
 //       static constexpr int NX = 4;             // state dimension, <= 32
-//       static constexpr int NU = 1;             // control dimension, <= 16
+//       static constexpr int NU = 1;             // control dimension, <= 32 (more than 16: the backward pass k_backward_w3w, fp64)
 //       real u_min[NU], u_max[NU];               // filled by ilqr_create from ilqr_desc.u_min / u_max
 //       ... its own parameters (plain data) ...
 //       void set_params(const double* p, int n);                                  // host: ilqr_desc.user_params
@@ -383,7 +383,7 @@ struct has_analytic_record<M, std::void_t<decltype(std::declval<const M&>().anal
 //
 // It may use what this file offers (sincos_shared, Rec<>).  NX = 4 with NU = 1 or 2 runs in the tiled lane-quad kernels (the
 // persistent routes of the shipped acrobot / double integrator; both arithmetic flavours are instantiated: fp32 handles take
-// their finite differences in UserModelT<double>) -- examples/user_model_acrobot.hpp.  Any other NX <= 32, NU <= 16 runs in
+// their finite differences in UserModelT<double>) -- examples/user_model_acrobot.hpp.  Any other NX <= 32, NU <= 32 runs in
 // the generic kernels (generic.hpp: thread-per-rollout k_rollout_g, wavefront-per-knot finite differences k_derivatives_g,
 // the matrix-core backward pass k_backward_w3; fp64; an analytic_record, if the model has one, is called by one lane per knot under
 // ILQR_FLAG_ANALYTIC_DERIVATIVES) -- examples/user_model_linear6.hpp.  A SMALL twin (even NX <= 8, NU <= 4) is compiled into both and
@@ -394,8 +394,8 @@ struct has_analytic_record<M, std::void_t<decltype(std::declval<const M&>().anal
 #ifdef ILQR_USER_MODEL_HEADER
 namespace ilqr {
 #include ILQR_USER_MODEL_HEADER
-static_assert(UserModelT<double>::NX >= 1 && UserModelT<double>::NX <= MAXN && UserModelT<double>::NU >= 1 && UserModelT<double>::NU <= MAXM,
-              "user device models: 1 <= NX <= 32, 1 <= NU <= 16");
+static_assert(UserModelT<double>::NX >= 1 && UserModelT<double>::NX <= MAXN && UserModelT<double>::NU >= 1 && UserModelT<double>::NU <= kMaxControls,
+              "user device models: 1 <= NX <= 32, 1 <= NU <= 32");
 // which kernels the build's user model runs in
 constexpr bool kUserQuad = UserModelT<double>::NX == 4 && (UserModelT<double>::NU == 1 || UserModelT<double>::NU == 2);  // lane-quad kernels, persistent routes
 constexpr bool kUserSmall = !kUserQuad && UserModelT<double>::NX % 2 == 0 && UserModelT<double>::NX <= 8 && UserModelT<double>::NU <= 4;  // tiled thread kernels

@@ -59,15 +59,17 @@ enum ilqr_model_id {
   ILQR_MODEL_ACROBOT = 0,           /* include/acrobot.h            nx=4 nu=1 */
   ILQR_MODEL_DOUBLE_INTEGRATOR = 1, /* include/double_integrator.h  nx=4 nu=2 */
   ILQR_MODEL_LQ = 2,                /* synthetic LQ (BASELINE.json configs[4]): xdot = A x + B u, cost .5(x'Qx + u'Ru),
-                                       final .5 x'Qf x, nx<=32 nu<=16; device twin, runs end to end (lq_* of the desc) */
-  ILQR_MODEL_HOST = 3,              /* a Model that exists only as host code, nx<=32 nu<=16: the caller evaluates its
+                                       final .5 x'Qf x, nx<=32 nu<=32 (more than 16: generic thread-per-rollout and point-by-point kernels); device twin, runs end to end (lq_* of the desc) */
+  ILQR_MODEL_HOST = 3,              /* a Model that exists only as host code, nx<=32 nu<=32 (at exactly 32 free controls the box-QP factors
+                                       with Eigen's UNBLOCKED LLT, as below 32; Eigen 3.3.4 itself switches to its blocked LLT there: rounding,
+                                       and the partial factor of an indefinite block, may differ from the reference's): the caller evaluates its
                                        rollouts and finite differences (ilqr_set_trajectory, ilqr_set_derivatives,
                                        ilqr_accept_candidates), the backward pass / box-QPs / accept logic run on the
                                        device; rollout and finite-difference entry points return ILQR_ERR_UNSUPPORTED */
-  ILQR_MODEL_USER = 4               /* the caller's OWN device twin (nx=4, nu in {1,2}), compiled into a build of this
+  ILQR_MODEL_USER = 4               /* the caller's OWN device twin (nx<=32 nu<=32; nx = 4 with nu in {1,2} runs every kernel of the
+                                       nx = 4 path, both dtypes; other sizes the generic fp64 kernels), compiled into a build of this
                                        library from a header that is not part of it: -DILQR_USER_MODEL_HEADER='"file.hpp"'
-                                       (ilqr_amd/csrc/models.hpp states the contract, INTEGRATION.md 5 the recipe).  Runs
-                                       every kernel of the nx = 4 path, both dtypes.  A build without such a header
+                                       (ilqr_amd/csrc/models.hpp states the contract, INTEGRATION.md 5 the recipe).  A build without such a header
                                        answers ILQR_ERR_UNSUPPORTED; ilqr_has_user_model() tells which one is loaded. */
 };
 
@@ -127,7 +129,8 @@ enum ilqr_flags {
    * where the reference adds lambda I to Quu and notes "regularization is different" (src/ilqr_core.cpp:365-367).
    * The value update keeps the unregularised Quu, Qux as in the reference.  Every model: the nx = 4 kernels, the
    * tiled kernels of a small twin, and k_backward_w3 on the generic path (n <= 32, m <= 16; host-evaluated models
-   * included: the backward pass is what they run on the device) -- not with ILQR_ROUTE_BACKWARD_W2. */
+   * included: the backward pass is what they run on the device) -- not with ILQR_ROUTE_BACKWARD_W2, nor with more than
+   * 16 controls (ILQR_ERR_UNSUPPORTED). */
   ILQR_FLAG_REGULARIZE_VXX = 128
 };
 
@@ -172,7 +175,7 @@ typedef struct ilqr_desc {
 enum ilqr_route {
   /* What ILQR_ROUTE_AUTO means for the arithmetic: on the nx = 4 path every route computes every element by the same expression in the
    * same order (bit-identical, tests/test_gpu_fused_sweep.py).  On the GENERIC path (n <= 32, m <= 16: LQ model, larger user twins,
-   * host-evaluated models) the default backward kernel k_backward_w3 does NOT follow the reference's operation order: the box-QP's
+   * host-evaluated models; 16 < m <= 32: host-evaluated models, on k_backward_w3w with the literal box-QP in every step) the default backward kernel k_backward_w3 does NOT follow the reference's operation order: the box-QP's
    * inverse comes from a Newton-Schulz refinement of the previous knot's inverse (the literal Cholesky of src/boxqp.cpp:80-119 is its
    * fallback), the upper Vxx tile is the transpose of the lower one, matrix-vector products are per-lane sums.  Its gains equal the
    * reference-order kernel's and the oracle's to rounding (1e-9 on well-conditioned steps; the 1e-6 per-knot tolerance is what is
@@ -196,9 +199,12 @@ enum ilqr_route {
                                        (k_derivatives_g) instead of by what moved (k_derivatives_lq: Q p = Q x + delta_i Q[:,i] + delta_j Q[:,j]) */
   ILQR_ROUTE_WAVE_PER_TRAJECTORY = 4096, /* a small user twin (even nx <= 8, nu <= 4): the generic wavefront-per-trajectory kernels instead of the tiled
                                             thread-per-trajectory ones it runs in by default (cross-check; fp64 only) */
-  ILQR_ROUTE_BACKWARD_W2 = 1024     /* generic path: round 2's register kernel k_backward_w2 (literal Cholesky in every box-QP, per-knot cx / cu records)
+  ILQR_ROUTE_BACKWARD_W2 = 1024,    /* generic path: round 2's register kernel k_backward_w2 (literal Cholesky in every box-QP, per-knot cx / cu records)
                                        instead of k_backward_w3 (matrix-core refinement of the previous knot's inverse; LQ model with exact
                                        derivatives: no record array at all) */
+  ILQR_ROUTE_TWO_CONTROL_TILES = 8192 /* generic path, nu <= 16: the backward kernel of 16 < nu <= 32, k_backward_w3w (two 16-column control tiles,
+                                       the literal box-QP in every step), instead of k_backward_w3 (cross-check; not with ILQR_ROUTE_BACKWARD_W2 or
+                                       ILQR_FLAG_REGULARIZE_VXX) */
 };
 
 const char* ilqr_last_error(void);

@@ -15,7 +15,7 @@
 // (device_model_id() == ILQR_MODEL_HOST, the default: a user's subclass compiled unchanged) is
 // evaluated where it lives -- its rollouts and finite differences call those virtuals on the host --
 // while the backward pass, its box-QPs and the accept / lambda / termination logic run on the
-// device (nx <= 32, nu <= 16).  Nothing here works without a GPU: ilqr_create fails loudly.
+// device (nx <= 32, nu <= 16; host-evaluated models nu <= 32).  Nothing here works without a GPU: ilqr_create fails loudly.
 #ifndef ILQR_AMD_HPP_
 #define ILQR_AMD_HPP_
 
@@ -263,7 +263,7 @@ class BatchILQR {
     // rollouts and finite differences are evaluated HERE by calling those virtuals (that is the
     // plugin, not a substitute for a kernel), and everything that does not need the model --
     // the backward pass with its box-QPs, the lambda retries, the accept / lambda schedule /
-    // termination logic -- still runs on the device (ILQR_MODEL_HOST handle; nx <= 32, nu <= 16).
+    // termination logic -- still runs on the device (ILQR_MODEL_HOST handle; nx <= 32, nu <= 32).
     // There is still no path without a GPU.
     host_ = (model->device_model_id() == ILQR_MODEL_HOST);
     std::vector<double> lo(m_), hi(m_);
