@@ -1,7 +1,7 @@
 // A user's device twin with more than 16 controls (ILQR_MODEL_USER, NX <= 32, NU <= 32): a 24-state, 20-control linear-quadratic
 // model -- xdot = A x + B u, cost 0.5 (x'Qx + u'Ru), final cost 0.5 x'Qf x -- written as plain loops like user_model_linear6.hpp,
 // with the same user_params layout.  It runs in the generic kernels: thread-per-rollout forward passes, wavefront-per-knot finite
-// differences through dynamics() / cost() / final_cost(), and the two-control-tile backward pass k_backward_w3w.
+// differences through dynamics() / cost() / final_cost(), and k_backward_w3's two-control-tile backward pass.
 //   user_params: A [24][24], B [24][20], Q [24][24], R [20][20], Qf [24][24], row-major (2608 doubles), optionally followed by wb: the
 //   weight of a soft penalty wb sum_j (u_j / u_max_j)^2 on the controls
 template <class real_>

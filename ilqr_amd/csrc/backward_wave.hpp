@@ -34,7 +34,7 @@ namespace ilqr {
 constexpr int WN = 32, WM = 16;   // maximum dimensions of this kernel
 constexpr int LDN = WN + 1;       // leading dimension of LDS matrices with up to 32 rows
 constexpr int LDM = WM + 1;       // ... with up to 16 rows
-// Handles with 16 < nu <= 32 (two 16-column control tiles: k_backward_w3w, backward_wave3.hpp) use a layout of their own; the
+// Handles with 16 < nu <= 32 (k_backward_w3 with two 16-column control tiles, backward_wave3.hpp) use a layout of their own; the
 // constants above, and every kernel sized by them, are what nu <= 16 runs
 constexpr int WMW = 32;           // controls of the two-tile layout
 constexpr int LDMW = WMW + 1;     // leading dimension of its m x m / m x n LDS matrices
@@ -246,7 +246,7 @@ __device__ __forceinline__ double w_quad_cost(int m, const double* Q, const doub
 
 // src/boxqp.cpp:26-139 for one trajectory per wavefront.  Inputs in LDS: QuuF (Q), Qu (c), kprev
 // (x0), lo, hi.  Outputs: L.x (solution), L.vfree, L.Minv (R^-1 R^-T of the last factor, ld W + 1), nfR.
-// W: the control width of the layout (WM = 16, or WMW = 32 for the two-tile kernel k_backward_w3w); m <= W.
+// W: the control width of the layout (WM = 16, or WMW = 32 for k_backward_w3's two control tiles); m <= W.
 template <class LDS, int W = WM>
 __device__ int w_box_qp(int m, LDS& L, int lane, int& nfR_out ILQR_W2CLOCK_ARG, int* nfact_out = nullptr, int fixes = 0) {
   static_assert(W == WM || W == WMW, "16 or 32 controls");

@@ -1,4 +1,4 @@
-// backward_wave3.hpp -- the generic backward pass (n <= 32, m <= 16, one wavefront per trajectory) with the fp64 pipe's
+// backward_wave3.hpp -- the generic backward pass (n <= 32, m <= 32; one wavefront per trajectory) with the fp64 pipe's
 // cycles counted: k_backward_w2's register layout, minus the work that layout does not need.
 //
 // What bounds k_backward_w2 (profiles/r05a_w2_sections.txt, scripts/ubench/coissue.hip): on gfx950 a v_mfma_f64_16x16x4_f64
@@ -28,7 +28,15 @@
 //     kernel runs; knot T's cxx (= sym(Qf)) is a second constant record.
 // Everything else (operand maps, transposed products, the symmetrisation through LDS, the lambda-retry loop, the gradient
 // norm) is k_backward_w2's; gains agree with it to rounding, not to the bit (tests/test_gpu_generic_backward.py).
+//
+// 16 < m <= 32 (and ILQR_ROUTE_TWO_CONTROL_TILES on m <= 16; the handle reports the stage as "k_backward_w3w"): the same step with
+// MT = 2 control tiles -- fu, A2', Qux, K, T1', cxu in two 16-row tiles, cuu / Quu as 2 x 2 tiles, everything indexed by a control
+// reduced over lanes 0..31.  Its box-QP is the literal one in every step, w_box_qp<., 32>: the refinement's contraction test
+// 16 x max|I - M X| < 1/2 would need a bound of its own at m = 32, and the literal QP is the reference's algorithm.  A free set of
+// 32 controls is a full 32-bit word, so that route never forms `(1u << m) - 1u` (only the refinement does).  Its LDS is Wave3WLds.
 #pragma once
+#include <type_traits>
+
 #include "backward_wave2.hpp"
 
 namespace ilqr {
@@ -327,30 +335,68 @@ __device__ __forceinline__ int w3_box_qp_small(int m, LDS& L, int lane, int& nfR
   return result;
 }
 
-// n <= 16 NT, m <= 16.  Arguments as k_backward_w2; LQF: const_rec holds TWO records (the constant blocks of the knots t < T,
+// ILQR_TILES(v) ... ILQR_TILES_END(v): the statements between, for the control tiles v = 0 .. MT - 1 (unrolled).  At MT = 1 the front
+// end emits them once, v the constant 0: no loop reaches the optimiser, not even one of a single trip, which LICM and SROA would see
+// before unrolling it -- that moved the register allocation of every single-tile instantiation.  So MT = 1 compiles instruction for
+// instruction as the step did before it had control tiles.
+#define ILQR_TILES(v) { int v##_it = 0; _Pragma("unroll") do { const int v = (MT == 1) ? 0 : v##_it;
+#define ILQR_TILES_END(v) } while (MT > 1 && ++v##_it < MT); }
+
+// The LDS of the two-tile step (MT = 2), <= 40 KB so that four wavefronts -- one per SIMD -- fit a CU.  S has room for QuuF | Minv
+// (32 x 33 each) but not for Quu beside them, so Quu waits in Kbuf behind the first reduction's partial sums, from the products to dV,
+// and the stale-factor path writes K into QuuF's place, dead once the box-QP has returned.
+template <int NT>  // NT = 16-row tiles covering n: 1 (n <= 16) or 2 (n <= 32)
+struct Wave3WLds {
+  static constexpr int N = 16 * NT, LD = N + 1;
+  static constexpr int S_LEN = (LD * N > 2 * LDMW * WMW) ? LD * N : 2 * LDMW * WMW;
+  static constexpr int RED = 4 * (N + WMW);  // the partial sums of Qx, Qu
+  double S[S_LEN];                // QuuF (K on the stale-factor path) | Minv (m x m, ld LDMW) until the gains; then Vn (ld LD)
+  double Kbuf[RED + LDMW * WMW];  // reduction scratch; Quu (ld LDMW) behind the first reduction's sums until dV
+  double Tbuf[LDMW * WMW];        // Ri / the scattered Minv (m x m, ld LDMW); Qux (m x n) for the stale-factor path
+  __device__ __forceinline__ double* K() { return S; }
+  __device__ __forceinline__ double* Quu() { return Kbuf + RED; }
+  __device__ __forceinline__ double* QuuF() { return S; }
+  __device__ __forceinline__ double* Minv() { return S + LDMW * WMW; }
+  __device__ __forceinline__ double* Qf() { return Tbuf; }
+  __device__ __forceinline__ double* Ri() { return Tbuf; }
+  double Vx[N], cx[N], Qx[N];
+  double Qu[WMW], x[WMW], grad[WMW], gc[WMW], search[WMW], lo[WMW], hi[WMW], clamped[WMW], xc[WMW], tmp[WMW], kprev[WMW],
+      gfree[WMW], xfree[WMW];
+  int vfree[WMW], idx[WMW];
+};
+static_assert(sizeof(Wave3WLds<2>) <= 40 * 1024, "one wavefront on every SIMD: 4 x LDS <= 160 KB");
+
+// n <= 16 NT, m <= 16 MT.  Arguments as k_backward_w2; LQF: const_rec holds TWO records (the constant blocks of the knots t < T,
 // then knot T's) and v.D is not touched.
 // REGV (ILQR_FLAG_REGULARIZE_VXX, opt-in): lambda regularises Vxx' ([Tassa 2012] eq. 10) instead of Quu -- QuuF = Quu + lambda fu'fu and the
 // gains' Qux_reg = Qux + lambda fu'fx, two more transposed products per 16-column block on the operands the step holds anyway; the value
 // update keeps Quu, Qux (as backward_thread.hpp does for the tiled kernels).  Instantiated without FULL / LQF.
+// MT = 2 (16 < m <= 32, and ILQR_ROUTE_TWO_CONTROL_TILES): the control-indexed blocks -- fu, A2', Qux, K, T1', cxu -- in two 16-row tiles,
+// cuu / Quu as 2 x 2 tiles, everything indexed by a control reduced over lanes 0..31; the LDS is Wave3WLds.  Instantiated without
+// FULL / LQF / REGV.
 // Wavefronts per SIMD.  n <= 16 (NT = 1): TWO since round 6 -- at three (168 registers) the kernel kept 308 bytes of scratch per lane and its
 // step went through memory: the pendulum chain's pass (n = 16, m = 4, B = 4096) 7.4 -> 4.8 ms with 254 registers and no scratch (four: the
 // compiler gives up on the bound).  n > 16 (NT = 2): two, 256 registers and 170-260 bytes of scratch; one wavefront per SIMD with the
-// accumulation registers as spill space was measured too (ILQR_W3_NT2_WAVES=1: profiles/README.md, round 6).
+// accumulation registers as spill space was measured too (ILQR_W3_NT2_WAVES=1: profiles/README.md, round 6).  MT = 2: one (its LDS).
 #ifndef ILQR_W3_NT1_WAVES
 #define ILQR_W3_NT1_WAVES 2
 #endif
 #ifndef ILQR_W3_NT2_WAVES
 #define ILQR_W3_NT2_WAVES 2
 #endif
-template <int NT, bool FULL, bool LQF, bool REGV = false>
-__global__ __launch_bounds__(64, NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES) void k_backward_w3(BatchView v, int n, int m, const double* __restrict__ u_min,
+template <int NT, bool FULL, bool LQF, bool REGV = false, int MT = 1>
+__global__ __launch_bounds__(64, MT == 2 ? 1 : NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES) void k_backward_w3(BatchView v, int n, int m, const double* __restrict__ u_min,
                                                                     const double* __restrict__ u_max, SolverParams sp, int mode,
                                                                     const double* __restrict__ const_rec) {
-  __shared__ Wave2Lds<NT> L;
+  static_assert(MT == 1 || (MT == 2 && !FULL && !LQF && !REGV), "two control tiles: whole records, the bounds-checked step");
+  using Lds = std::conditional_t<MT == 1, Wave2Lds<NT>, Wave3WLds<NT>>;
+  __shared__ Lds L;
   constexpr int N = 16 * NT;
-  constexpr int LDX = Wave2Lds<NT>::LD;
-  constexpr int RS = N + 16;  // stride of one row group's partial sums in the reduction scratch
-  static_assert(4 * RS <= LDM * N && 3 * 4 * N <= LDM * N, "reduction scratch lives in Kbuf");
+  constexpr int W = 16 * MT;   // controls the layout holds
+  constexpr int LDW = W + 1;   // ... and the leading dimension of its m x m / m x n LDS matrices
+  constexpr int LDX = Lds::LD;
+  constexpr int RS = N + W;  // stride of one row group's partial sums in the reduction scratch
+  static_assert(4 * RS <= sizeof(Lds::Kbuf) / sizeof(double) && 3 * 4 * N <= sizeof(Lds::Kbuf) / sizeof(double), "reduction scratch lives in Kbuf");
   static_assert(256 <= LDM * N, "the inverse's warm start lives in Tbuf");
   const int lane = threadIdx.x;
   const int b = blockIdx.x;
@@ -370,18 +416,18 @@ __global__ __launch_bounds__(64, NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES
   const int g = lane >> 4, p = lane & 15;
   {
     double* z = reinterpret_cast<double*>(&L);
-    const int nz = (int)(sizeof(Wave2Lds<NT>) / sizeof(double));
+    const int nz = (int)(sizeof(Lds) / sizeof(double));
     for (int e = lane; e < nz; e += 64) z[e] = 0.0;
   }
   lds_sync();
-  double* const red = L.Kbuf;  // partial sums of the matrix-vector products, [row group][column]
-  double* const Xw = L.Tbuf;   // the inverse's warm start, natural layout [r][lane]
+  double* const red = L.Kbuf;    // partial sums of the matrix-vector products, [row group][column]
+  double* const Xw = L.Tbuf;    // the inverse's warm start, natural layout [r][lane]
 
   auto mfma = [](double a, double b2, double4_t c) __attribute__((always_inline)) {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b2, c, 0, 0, 0);
   };
   const double4_t zero4 = {0.0, 0.0, 0.0, 0.0};
-  // natural registers: X[ti][tj][r] = X(16 ti + 4 r + g, 16 tj + p)
+  // natural registers: X[ti][tj][r] = X(16 ti + 4 r + g, 16 tj + p); control-indexed blocks carry the control tile mt first
   unsigned lb_nn = (unsigned)(g + n * p);
   unsigned lb_tn = (unsigned)(p + n * g);
   unsigned lb_mm = (unsigned)(g + m * p);
@@ -392,8 +438,9 @@ __global__ __launch_bounds__(64, NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES
   };
   auto row_in = [&](int a0) __attribute__((always_inline)) { return FULL || a0 + g < n; };
   auto col_in = [&](int tj) __attribute__((always_inline)) { return FULL || 16 * tj + p < n; };
-  auto mrow_in = [&](int rr) __attribute__((always_inline)) { return FULL || 4 * rr + g < m; };
-  const bool mcol_in = FULL || p < m;
+  auto mrow_in = [&](int mt, int rr) __attribute__((always_inline)) { return FULL || 16 * mt + 4 * rr + g < m; };
+  const bool mcol0 = FULL || p < m;  // (formed once: what the single-tile step has always done)
+  auto mcol_in = [&](int mt) __attribute__((always_inline)) { return mt == 0 ? mcol0 : FULL || 16 * mt + p < m; };
 
   // the four-way sum over the row groups of one column of the reduction scratch, group 0 first
   auto red4 = [&](int col) __attribute__((always_inline)) { return ((red[col] + red[RS + col]) + red[2 * RS + col]) + red[3 * RS + col]; };
@@ -446,7 +493,7 @@ __global__ __launch_bounds__(64, NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES
       ILQR_W2MARK(7)
       const double* rk = LQF ? const_rec : Db + (size_t)i * REC;        // this knot's record (cx, cu, and the matrices unless const_rec has them)
       const double* rm = (LQF || const_rec) ? const_rec : rk;           // ... its matrix blocks
-      double fx[NT][NT][4], fu[NT][4];
+      double fx[NT][NT][4], fu[NT][MT][4];
       double kx = 0, ku = 0;  // non-LQF: cx on lanes < n, cu on lanes N .. N + m - 1
       {
         asm volatile("" : "+v"(lb_nn));
@@ -458,7 +505,7 @@ __global__ __launch_bounds__(64, NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES
             const bool ain = row_in(a0);
 #pragma unroll
             for (int tj = 0; tj < NT; tj++) fx[ti][tj][rr] = ldm(rm, ain && col_in(tj), lb_nn + (unsigned)(oFX + a0 + n * 16 * tj));
-            fu[ti][rr] = ldm(rm, ain && mcol_in, lb_nn + (unsigned)(oFU + a0));
+            ILQR_TILES(mt) fu[ti][mt][rr] = ldm(rm, ain && mcol_in(mt), lb_nn + (unsigned)(oFU + a0 + n * 16 * mt)); ILQR_TILES_END(mt)
           }
         const double us_l = (lane < m) ? usb[(size_t)i * m + lane] : 0.0;
         if (LQF) {
@@ -476,7 +523,7 @@ __global__ __launch_bounds__(64, NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES
       }
       lds_sync();
       // :359-360 the partial sums of fx'Vx and fu'Vx over this lane's rows (16 ti + 4 r + g); reduced over g below
-      double px[NT], pu = 0;
+      double px[NT], pu[MT];
       {
         double vxr[NT][4];
 #pragma unroll
@@ -485,21 +532,22 @@ __global__ __launch_bounds__(64, NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES
           for (int rr = 0; rr < 4; rr++) vxr[ti][rr] = L.Vx[16 * ti + 4 * rr + g];
 #pragma unroll
         for (int tj = 0; tj < NT; tj++) px[tj] = 0;
+        ILQR_TILES(mt) pu[mt] = 0; ILQR_TILES_END(mt)
 #pragma unroll
         for (int ti = 0; ti < NT; ti++)
 #pragma unroll
           for (int rr = 0; rr < 4; rr++) {
 #pragma unroll
             for (int tj = 0; tj < NT; tj++) px[tj] = __builtin_fma(fx[ti][tj][rr], vxr[ti][rr], px[tj]);
-            pu = __builtin_fma(fu[ti][rr], vxr[ti][rr], pu);
+            ILQR_TILES(mt) pu[mt] = __builtin_fma(fu[ti][mt][rr], vxr[ti][rr], pu[mt]); ILQR_TILES_END(mt)
           }
       }
       ILQR_W2MARK(0)
       // A1' = Vxx' fx (n x n), A2' = Vxx' fu (n x m)
-      double4_t a1t[NT][NT], a2t[NT];
+      double4_t a1t[NT][NT], a2t[NT][MT];
 #pragma unroll
       for (int ti = 0; ti < NT; ti++) {
-        a2t[ti] = zero4;
+        ILQR_TILES(mt) a2t[ti][mt] = zero4; ILQR_TILES_END(mt)
 #pragma unroll
         for (int tj = 0; tj < NT; tj++) a1t[ti][tj] = zero4;
       }
@@ -509,17 +557,17 @@ __global__ __launch_bounds__(64, NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES
         for (int ti = 0; ti < NT; ti++) {
 #pragma unroll
           for (int tj = 0; tj < NT; tj++) a1t[ti][tj] = mfma(Vxx[ks >> 2][ti][ks & 3], fx[ks >> 2][tj][ks & 3], a1t[ti][tj]);
-          a2t[ti] = mfma(Vxx[ks >> 2][ti][ks & 3], fu[ks >> 2][ks & 3], a2t[ti]);
+          ILQR_TILES(mt) a2t[ti][mt] = mfma(Vxx[ks >> 2][ti][ks & 3], fu[ks >> 2][mt][ks & 3], a2t[ti][mt]); ILQR_TILES_END(mt)
         }
       }
       // :361 Qxx = cxx + A1 fx ; :362 Qux = cxu' + A2 fx ; :363/:367 Quu, QuuF = cuu (+ lambda I) + A2 fu
       ILQR_W2MARK(1)
-      double Qxx[NT][NT][4], Qux[NT][4], quu_nat[4];
+      double Qxx[NT][NT][4], Qux[MT][NT][4], quu_nat[MT][MT][4];
       double Quxr[REGV ? NT : 1][4];  // REGV: Qux + lambda fu'fx, what the gains are solved from
 #pragma unroll
       for (int tj = 0; tj < NT; tj++) {  // one 16-column block of the outputs at a time (registers)
         __builtin_amdgcn_sched_barrier(0);
-        double cxx[NT][4], cxu[4], cuu[4];
+        double cxx[NT][4], cxu[MT][4], cuu[MT][MT][4];
         {
           asm volatile("" : "+v"(lb_nn), "+v"(lb_tn), "+v"(lb_mm));
 #pragma unroll
@@ -529,12 +577,19 @@ __global__ __launch_bounds__(64, NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES
               const int a0 = 16 * ti + 4 * rr;
               cxx[ti][rr] = ldm(rm, row_in(a0) && col_in(tj), lb_nn + (unsigned)(oCXX + a0 + n * 16 * tj));
             }
+          ILQR_TILES(mt)
 #pragma unroll
-          for (int rr = 0; rr < 4; rr++)  // Qux(a, c) starts from cxu(c, a): offset c + n a   (LQ: cxu = 0)
-            cxu[rr] = LQF ? 0.0 : ldm(rm, mrow_in(rr) && col_in(tj), lb_tn + (unsigned)(oCXU + 16 * tj + n * 4 * rr));
+            for (int rr = 0; rr < 4; rr++)  // Qux(a, c) starts from cxu(c, a): offset c + n a   (LQ: cxu = 0)
+              cxu[mt][rr] = LQF ? 0.0 : ldm(rm, mrow_in(mt, rr) && col_in(tj), lb_tn + (unsigned)(oCXU + 16 * tj + n * 16 * mt + n * 4 * rr));
+          ILQR_TILES_END(mt)
           if (tj == 0) {
+            ILQR_TILES(mi)
+              ILQR_TILES(mj)
 #pragma unroll
-            for (int rr = 0; rr < 4; rr++) cuu[rr] = ldm(rm, mrow_in(rr) && mcol_in, lb_mm + (unsigned)(oCUU + 4 * rr));
+                for (int rr = 0; rr < 4; rr++)
+                  cuu[mi][mj][rr] = ldm(rm, mrow_in(mi, rr) && mcol_in(mj), lb_mm + (unsigned)(oCUU + 16 * mi + 4 * rr + m * 16 * mj));
+              ILQR_TILES_END(mj)
+            ILQR_TILES_END(mi)
           }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -545,18 +600,26 @@ __global__ __launch_bounds__(64, NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES
             for (int rr = 0; rr < 4; rr++) px[tj] = __builtin_fma(cxx[ti][rr], L.cx[16 * ti + 4 * rr + g], px[tj]);
           if (tj == 0) {
 #pragma unroll
-            for (int rr = 0; rr < 4; rr++) pu = __builtin_fma(cuu[rr], L.tmp[4 * rr + g], pu);
+            for (int rr = 0; rr < 4; rr++) pu[0] = __builtin_fma(cuu[0][0][rr], L.tmp[4 * rr + g], pu[0]);
           }
         }
-        double4_t qxx[NT], qux = zero4, quu = zero4;
+        double4_t qxx[NT], qux[MT], quu[MT][MT];
 #pragma unroll
         for (int ti = 0; ti < NT; ti++) qxx[ti] = zero4;
+        ILQR_TILES(mi)
+          qux[mi] = zero4;
+          ILQR_TILES(mj) quu[mi][mj] = zero4; ILQR_TILES_END(mj)
+        ILQR_TILES_END(mi)
 #pragma unroll
         for (int ks = 0; ks < 4 * NT; ks++) {
 #pragma unroll
           for (int ti = tj; ti < NT; ti++) qxx[ti] = mfma(a1t[ks >> 2][ti][ks & 3], fx[ks >> 2][tj][ks & 3], qxx[ti]);  // (tiles on and below the diagonal: see Vn)
-          qux = mfma(a2t[ks >> 2][ks & 3], fx[ks >> 2][tj][ks & 3], qux);
-          if (tj == 0) quu = mfma(a2t[ks >> 2][ks & 3], fu[ks >> 2][ks & 3], quu);
+          ILQR_TILES(mt) qux[mt] = mfma(a2t[ks >> 2][mt][ks & 3], fx[ks >> 2][tj][ks & 3], qux[mt]); ILQR_TILES_END(mt)
+          if (tj == 0) {
+            ILQR_TILES(mi)
+              ILQR_TILES(mj) quu[mi][mj] = mfma(a2t[ks >> 2][mi][ks & 3], fu[ks >> 2][mj][ks & 3], quu[mi][mj]); ILQR_TILES_END(mj)
+            ILQR_TILES_END(mi)
+          }
         }
 #pragma unroll
         for (int ti = tj; ti < NT; ti++)
@@ -566,47 +629,53 @@ __global__ __launch_bounds__(64, NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES
             Qxx[ti][tj][rr] = (FULL || (row_in(16 * ti + 4 * rr) && col_in(tj))) ? val : 0.0;
             asm volatile("" : "+v"(Qxx[ti][tj][rr]));  // (computed HERE: sunk below the box-QP, both addends stay live across it)
           }
+        ILQR_TILES(mt)
 #pragma unroll
-        for (int rr = 0; rr < 4; rr++) {
-          const double val = LQF ? qux[rr] : cxu[rr] + qux[rr];
-          Qux[tj][rr] = (FULL || (mrow_in(rr) && col_in(tj))) ? val : 0.0;
-          asm volatile("" : "+v"(Qux[tj][rr]));
-        }
+          for (int rr = 0; rr < 4; rr++) {
+            const double val = LQF ? qux[mt][rr] : cxu[mt][rr] + qux[mt][rr];
+            Qux[mt][tj][rr] = (FULL || (mrow_in(mt, rr) && col_in(tj))) ? val : 0.0;
+            asm volatile("" : "+v"(Qux[mt][tj][rr]));
+          }
+        ILQR_TILES_END(mt)
         double4_t fufu = zero4;
         if constexpr (REGV) {  // fu'fx, fu'fu: rows and columns outside the model are zero in fu, fx already
           double4_t fufx = zero4;
 #pragma unroll
           for (int ks = 0; ks < 4 * NT; ks++) {
-            fufx = mfma(fu[ks >> 2][ks & 3], fx[ks >> 2][tj][ks & 3], fufx);
-            if (tj == 0) fufu = mfma(fu[ks >> 2][ks & 3], fu[ks >> 2][ks & 3], fufu);
+            fufx = mfma(fu[ks >> 2][0][ks & 3], fx[ks >> 2][tj][ks & 3], fufx);
+            if (tj == 0) fufu = mfma(fu[ks >> 2][0][ks & 3], fu[ks >> 2][0][ks & 3], fufu);
           }
 #pragma unroll
-          for (int rr = 0; rr < 4; rr++) Quxr[tj][rr] = Qux[tj][rr] + lambda * fufx[rr];
+          for (int rr = 0; rr < 4; rr++) Quxr[tj][rr] = Qux[0][tj][rr] + lambda * fufx[rr];
         }
         if (tj == 0) {
+          ILQR_TILES(mi)
+            ILQR_TILES(mj)
 #pragma unroll
-          for (int rr = 0; rr < 4; rr++) {
-            const int a = 4 * rr + g, c = p;
-            const bool in = FULL || (mrow_in(rr) && mcol_in);
-            const double cu2 = in ? cuu[rr] : 0.0;
-            quu_nat[rr] = in ? cu2 + quu[rr] : 0.0;
-            L.Quu()[a + LDM * c] = quu_nat[rr];
-            if constexpr (REGV)
-              L.QuuF()[a + LDM * c] = in ? quu_nat[rr] + lambda * fufu[rr] : 0.0;
-            else
-              L.QuuF()[a + LDM * c] = in ? (cu2 + ((a == c) ? lambda : 0.0)) + quu[rr] : 0.0;
-          }
+              for (int rr = 0; rr < 4; rr++) {
+                const int a = 16 * mi + 4 * rr + g, c = 16 * mj + p;
+                const bool in = FULL || (mrow_in(mi, rr) && mcol_in(mj));
+                const double cu2 = in ? cuu[mi][mj][rr] : 0.0;
+                quu_nat[mi][mj][rr] = in ? cu2 + quu[mi][mj][rr] : 0.0;
+                L.Quu()[a + LDW * c] = quu_nat[mi][mj][rr];
+                if constexpr (REGV)
+                  L.QuuF()[a + LDW * c] = in ? quu_nat[mi][mj][rr] + lambda * fufu[rr] : 0.0;
+                else
+                  L.QuuF()[a + LDW * c] = in ? (cu2 + ((a == c) ? lambda : 0.0)) + quu[mi][mj][rr] : 0.0;
+              }
+            ILQR_TILES_END(mj)
+          ILQR_TILES_END(mi)
         }
       }
       // Qx = cx + fx'Vx, Qu = cu + fu'Vx: the four row groups' partial sums through the scratch
 #pragma unroll
       for (int tj = 0; tj < NT; tj++) red[g * RS + 16 * tj + p] = px[tj];
-      red[g * RS + N + p] = pu;
+      ILQR_TILES(mt) red[g * RS + N + 16 * mt + p] = pu[mt]; ILQR_TILES_END(mt)
       lds_sync();
       if (lane < N) {
         const double s = red4(lane);
         L.Qx[lane] = (FULL || lane < n) ? (LQF ? s : kx + s) : 0.0;
-      } else if (lane < N + 16) {
+      } else if (lane < N + W) {
         const double s = red4(lane);
         L.Qu[lane - N] = (lane - N < m) ? (LQF ? s : ku + s) : 0.0;
       }
@@ -617,7 +686,13 @@ __global__ __launch_bounds__(64, NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES
       int nfR = 0, nfact = 0;
       bool slow = false;
       int result;
-      if (!FULL && m <= 2) {  // one or two controls: the scalar solvers (w3_box_qp_small); K by the literal path's code below
+      if constexpr (MT == 2) {  // two control tiles: the literal QP, 32 lanes wide, in every step (the refinement's contraction bound is
+        // for 16 x 16 blocks); K by the literal path's code below
+        slow = true;
+        nfact = -1;  // (no warm start is kept on this route)
+        result = w_box_qp<Lds, W>(m, L, lane, nfR ILQR_W2CLOCK_PASS, nullptr, sp.fixes);
+        free_mask = (unsigned)__ballot(lane < m && L.vfree[lane]);
+      } else if (!FULL && m <= 2) {  // one or two controls: the scalar solvers (w3_box_qp_small); K by the literal path's code below
         slow = true;
         nfact = -1;  // (no warm start for the matrix-core refinement is kept on this route)
         result = w3_box_qp_small(m, L, lane, nfR, sp.fixes);
@@ -636,22 +711,22 @@ __global__ __launch_bounds__(64, NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES
         diverge = i;
         break;
       }
-      // :373-385  K rows of free dims, natural registers K[tj][r] = K(4 r + g, 16 tj + p)
-      double K[NT][4];
+      // :373-385  K rows of free dims, natural registers K[mt][tj][r] = K(16 mt + 4 r + g, 16 tj + p)
+      double K[MT][NT][4];
       const int nf = __popc(free_mask);
-      auto quxk = [&](int tj, int rr) -> double {  // what the gains are solved from
-        if constexpr (REGV) return Quxr[tj][rr]; else return Qux[tj][rr];
+      auto quxk = [&](int mt, int tj, int rr) -> double {  // what the gains are solved from
+        if constexpr (REGV) return Quxr[tj][rr]; else return Qux[mt][tj][rr];
       };
       if (!slow) {
         // K = -(masked inverse) Qux: clamped rows of the inverse are zero, so those rows of K are, and its zero columns add
-        // exact zeros to the k-ordered sums over the free dims
+        // exact zeros to the k-ordered sums over the free dims.  (MT = 1: the refinement's inverse is one 16 x 16 tile.)
 #pragma unroll
         for (int tj = 0; tj < NT; tj++) {
           double4_t acc = zero4;
 #pragma unroll
-          for (int ks = 0; ks < WM / 4; ks++) acc = mfma(Xm[ks], quxk(tj, ks), acc);
+          for (int ks = 0; ks < WM / 4; ks++) acc = mfma(Xm[ks], quxk(0, tj, ks), acc);
 #pragma unroll
-          for (int rr = 0; rr < 4; rr++) K[tj][rr] = -acc[rr];
+          for (int rr = 0; rr < 4; rr++) K[0][tj][rr] = -acc[rr];
         }
       } else {
         const unsigned long long fm64 = free_mask;
@@ -661,46 +736,56 @@ __global__ __launch_bounds__(64, NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES
             MF = L.Minv();
           } else {
             if (lane < m && L.vfree[lane]) L.idx[__popcll(fm64 & ((1ull << lane) - 1ull))] = lane;
-            for (int e = lane; e < LDM * WM; e += 64) MF[e] = 0.0;
+            for (int e = lane; e < LDW * W; e += 64) MF[e] = 0.0;
             lds_sync();
             for (int e = lane; e < nf * nf; e += 64) {
               const int a = e % nf, b2 = e / nf;
-              MF[L.idx[a] + LDM * L.idx[b2]] = L.Minv()[a + LDM * b2];
+              MF[L.idx[a] + LDW * L.idx[b2]] = L.Minv()[a + LDW * b2];
             }
             lds_sync();
           }
-          double aM[WM / 4];
-          ld_operand<WM / 4>([&](int i2, int k) { return MF[i2 + LDM * k]; }, lane, aM);
+          // K = -MF Qux: MF symmetric, tile (mt, kt) as the A operand; zero rows / columns outside the free set add exact zeros
+          ILQR_TILES(mt)
+            double aM[MT][4];
+            ILQR_TILES(kt) ld_operand<4>([&](int i2, int k) { return MF[(16 * mt + i2) + LDW * (16 * kt + k)]; }, lane, aM[kt]); ILQR_TILES_END(kt)
 #pragma unroll
-          for (int tj = 0; tj < NT; tj++) {
-            double4_t acc = zero4;
+            for (int tj = 0; tj < NT; tj++) {
+              double4_t acc = zero4;
+              ILQR_TILES(kt)
 #pragma unroll
-            for (int ks = 0; ks < WM / 4; ks++) acc = mfma(aM[ks], quxk(tj, ks), acc);
+                for (int ks = 0; ks < 4; ks++) acc = mfma(aM[kt][ks], quxk(kt, tj, ks), acc);
+              ILQR_TILES_END(kt)
 #pragma unroll
-            for (int rr = 0; rr < 4; rr++) K[tj][rr] = -acc[rr];
-          }
+              for (int rr = 0; rr < 4; rr++) K[mt][tj][rr] = -acc[rr];
+            }
+          ILQR_TILES_END(mt)
         } else {  // nothing free, or a stale factor of another size (:80): through LDS, as k_backward_w does
           if (lane < m && L.vfree[lane]) L.idx[__popcll(fm64 & ((1ull << lane) - 1ull))] = lane;
-          for (int c = lane >> 4; c < n; c += 4) L.K()[(lane & 15) + LDM * c] = 0;
+          // (MT = 1: the columns < n, the rest of Kbuf being reduction sums that reach K's padding only; MT = 2: all of them, QuuF's place)
+          for (int c = lane >> (3 + MT); c < (MT == 1 ? n : N); c += 64 / W) L.K()[(lane & (W - 1)) + LDW * c] = 0;
+          ILQR_TILES(mt)
 #pragma unroll
-          for (int tj = 0; tj < NT; tj++)
+            for (int tj = 0; tj < NT; tj++)
 #pragma unroll
-            for (int rr = 0; rr < 4; rr++) L.Tbuf[(4 * rr + g) + LDM * (16 * tj + p)] = quxk(tj, rr);
+              for (int rr = 0; rr < 4; rr++) L.Tbuf[(16 * mt + 4 * rr + g) + LDW * (16 * tj + p)] = quxk(mt, tj, rr);
+          ILQR_TILES_END(mt)
           lds_sync();
           if (nf > 0) {
             const int nuse = (nf < nfR) ? nf : nfR;
             for (int e = lane; e < nuse * n; e += 64) {
               const int rr = e % nuse, c = e / nuse;
               double acc = 0;
-              for (int l2 = 0; l2 < nuse; l2++) acc += -L.Minv()[rr + LDM * l2] * L.Tbuf[L.idx[l2] + LDM * c];
-              L.K()[L.idx[rr] + LDM * c] = acc;
+              for (int l2 = 0; l2 < nuse; l2++) acc += -L.Minv()[rr + LDW * l2] * L.Tbuf[L.idx[l2] + LDW * c];
+              L.K()[L.idx[rr] + LDW * c] = acc;
             }
           }
           lds_sync();
+          ILQR_TILES(mt)
 #pragma unroll
-          for (int tj = 0; tj < NT; tj++)
+            for (int tj = 0; tj < NT; tj++)
 #pragma unroll
-            for (int rr = 0; rr < 4; rr++) K[tj][rr] = L.K()[(4 * rr + g) + LDM * (16 * tj + p)];
+              for (int rr = 0; rr < 4; rr++) K[mt][tj][rr] = L.K()[(16 * mt + 4 * rr + g) + LDW * (16 * tj + p)];
+          ILQR_TILES_END(mt)
         }
         // re-seed the inverse's warm start from the literal factor, if that was a complete one for this free set:
         // X = R^-1 R^-T scattered to the free rows / columns, the identity elsewhere
@@ -724,40 +809,48 @@ __global__ __launch_bounds__(64, NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES
       ILQR_W2MARK(4)
       // :388-389
       {
-        const double d0 = wave_sum_row0(lane < m ? L.x[lane] * L.Qu[lane] : 0.0);
+        const double d0 = wave_sum_ctrl<W>(lane < m ? L.x[lane] * L.Qu[lane] : 0.0);
         double part = 0;
         if (lane < m) {
-          const double rr = dot_padded([&](int a) { return 0.5 * L.x[a]; }, [&](int a) { return L.Quu()[a + LDM * lane]; });
+          const double rr = dot_padded<W>([&](int a) { return 0.5 * L.x[a]; }, [&](int a) { return L.Quu()[a + LDW * lane]; });
           part = rr * L.x[lane];
         }
         dV0 += d0;
-        dV1 += wave_sum_row0(part);
+        dV1 += wave_sum_ctrl<W>(part);
       }
       // T1' = Quu' K (m x n): Quu's natural registers are its A operand
-      double4_t t1t[NT];
+      double4_t t1t[MT][NT];
+      ILQR_TILES(mt)
 #pragma unroll
-      for (int tj = 0; tj < NT; tj++) {
-        t1t[tj] = zero4;
+        for (int tj = 0; tj < NT; tj++) {
+          t1t[mt][tj] = zero4;
+          ILQR_TILES(kt)
 #pragma unroll
-        for (int ks = 0; ks < WM / 4; ks++) t1t[tj] = mfma(quu_nat[ks], K[tj][ks], t1t[tj]);
-      }
-      // :391 Vx = ((Qx + T1 k) + K'Qu) + Qux'k: per-lane partial sums over the rows 4 r + g, three sums kept apart
-      {
-        double xq[4], qq[4];
-#pragma unroll
-        for (int rr = 0; rr < 4; rr++) {
-          xq[rr] = L.x[4 * rr + g];
-          qq[rr] = L.Qu[4 * rr + g];
+            for (int ks = 0; ks < 4; ks++) t1t[mt][tj] = mfma(quu_nat[kt][mt][ks], K[kt][tj][ks], t1t[mt][tj]);
+          ILQR_TILES_END(kt)
         }
+      ILQR_TILES_END(mt)
+      // :391 Vx = ((Qx + T1 k) + K'Qu) + Qux'k: per-lane partial sums over the rows 16 mt + 4 r + g, three sums kept apart
+      {
+        double xq[MT][4], qq[MT][4];
+        ILQR_TILES(mt)
+#pragma unroll
+          for (int rr = 0; rr < 4; rr++) {
+            xq[mt][rr] = L.x[16 * mt + 4 * rr + g];
+            qq[mt][rr] = L.Qu[16 * mt + 4 * rr + g];
+          }
+        ILQR_TILES_END(mt)
 #pragma unroll
         for (int tj = 0; tj < NT; tj++) {
           double s1 = 0, s2 = 0, s3 = 0;
+          ILQR_TILES(mt)
 #pragma unroll
-          for (int rr = 0; rr < 4; rr++) {
-            s1 = __builtin_fma(t1t[tj][rr], xq[rr], s1);
-            s2 = __builtin_fma(K[tj][rr], qq[rr], s2);
-            s3 = __builtin_fma(Qux[tj][rr], xq[rr], s3);
-          }
+            for (int rr = 0; rr < 4; rr++) {
+              s1 = __builtin_fma(t1t[mt][tj][rr], xq[mt][rr], s1);
+              s2 = __builtin_fma(K[mt][tj][rr], qq[mt][rr], s2);
+              s3 = __builtin_fma(Qux[mt][tj][rr], xq[mt][rr], s3);
+            }
+          ILQR_TILES_END(mt)
           red[(0 * 4 + g) * N + 16 * tj + p] = s1;
           red[(1 * 4 + g) * N + 16 * tj + p] = s2;
           red[(2 * 4 + g) * N + 16 * tj + p] = s3;
@@ -782,12 +875,14 @@ __global__ __launch_bounds__(64, NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES
 #pragma unroll
         for (int tj = 0; tj <= ti; tj++) {
           double4_t p1 = zero4, p2 = zero4, p3 = zero4;
+          ILQR_TILES(kt)
 #pragma unroll
-          for (int ks = 0; ks < WM / 4; ks++) {
-            p1 = mfma(t1t[ti][ks], K[tj][ks], p1);
-            p2 = mfma(K[ti][ks], Qux[tj][ks], p2);
-            p3 = mfma(Qux[ti][ks], K[tj][ks], p3);
-          }
+            for (int ks = 0; ks < 4; ks++) {
+              p1 = mfma(t1t[kt][ti][ks], K[kt][tj][ks], p1);
+              p2 = mfma(K[kt][ti][ks], Qux[kt][tj][ks], p2);
+              p3 = mfma(Qux[kt][ti][ks], K[kt][tj][ks], p3);
+            }
+          ILQR_TILES_END(kt)
 #pragma unroll
           for (int rr = 0; rr < 4; rr++) {
             const double vn = ((Qxx[ti][tj][rr] + p1[rr]) + p2[rr]) + p3[rr];
@@ -811,12 +906,14 @@ __global__ __launch_bounds__(64, NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES
         kb[(size_t)i * m + lane] = L.x[lane];
         L.kprev[lane] = L.x[lane];
       }
+      ILQR_TILES(mt)
 #pragma unroll
-      for (int tj = 0; tj < NT; tj++)
+        for (int tj = 0; tj < NT; tj++)
 #pragma unroll
-        for (int rr = 0; rr < 4; rr++) {
-          if (FULL || (mrow_in(rr) && col_in(tj))) Kb[(size_t)i * m * n + (4 * rr + g) + m * (16 * tj + p)] = K[tj][rr];
-        }
+          for (int rr = 0; rr < 4; rr++) {
+            if (FULL || (mrow_in(mt, rr) && col_in(tj))) Kb[(size_t)i * m * n + (16 * mt + 4 * rr + g) + m * (16 * tj + p)] = K[mt][tj][rr];
+          }
+      ILQR_TILES_END(mt)
       lds_sync();
       ILQR_W2MARK(6)
     }
@@ -836,7 +933,7 @@ __global__ __launch_bounds__(64, NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES
 #ifdef ILQR_W2_TIMING
   clk.flush();
 #endif
-  // :153 / :405-412 gradient norm: mean_t max_j |k_j| / (|u_j| + 1), ascending t
+  // :153 / :405-412 gradient norm: mean_t max_j |k_j| / (|u_j| + 1), ascending t -- the max over the layout's W control lanes
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_s_waitcnt(0);
   double acc = 0;
@@ -844,7 +941,7 @@ __global__ __launch_bounds__(64, NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES
     double val = -1.0;
     if (lane < m) val = fabs(kb[(size_t)t * m + lane]) / (fabs(usb[(size_t)t * m + lane]) + 1);
 #pragma unroll
-    for (int off = 8; off >= 1; off >>= 1) val = fmax(val, __shfl_xor(val, off, 64));
+    for (int off = W / 2; off >= 1; off >>= 1) val = fmax(val, __shfl_xor(val, off, 64));
     acc += __shfl(val, 0, 64);
   }
   const double gnorm = acc / T;
@@ -864,5 +961,8 @@ __global__ __launch_bounds__(64, NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES
     }
   }
 }
+
+#undef ILQR_TILES
+#undef ILQR_TILES_END
 
 }  // namespace ilqr

@@ -16,7 +16,6 @@
 #include "backward_wave.hpp"
 #include "backward_wave2.hpp"
 #include "backward_wave3.hpp"
-#include "backward_wave3w.hpp"
 #include "generic.hpp"
 #include "kernels_wide.hpp"
 #include "kernels_wide2.hpp"
@@ -120,7 +119,7 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
   h->model = d->model;
   h->dtype = d->dtype;
   if (d->dtype != ILQR_DTYPE_F64 && d->dtype != ILQR_DTYPE_F32) return fail(ILQR_ERR_INVALID, "dtype %d: ILQR_DTYPE_F64 or ILQR_DTYPE_F32", d->dtype);
-  if (d->nu > WM) {  // 16 < nu <= 32: the generic backward pass with two control tiles (k_backward_w3w); what is not widened says so
+  if (d->nu > WM) {  // 16 < nu <= 32: the generic backward pass with two control tiles (k_backward_w3, MT = 2); what is not widened says so
     const char* what = (d->dtype == ILQR_DTYPE_F32) ? "fp32" : (d->route & ILQR_ROUTE_BACKWARD_W2) ? "ILQR_ROUTE_BACKWARD_W2" : (d->route & ILQR_ROUTE_LQ_DENSE_FD) ? "ILQR_ROUTE_LQ_DENSE_FD"
                        : (d->flags & ILQR_FLAG_REGULARIZE_VXX) ? "ILQR_FLAG_REGULARIZE_VXX" : nullptr;
     if (what) return fail(ILQR_ERR_UNSUPPORTED, "%s supports at most %d controls (nu = %d)", what, WM, d->nu);

@@ -18,7 +18,7 @@ constexpr int TW = 16;       // trajectories per tile (16 x 8 B = one 128-B line
 constexpr int NALPHA = 11;   // include/ilqr.h:24
 constexpr int MAXN = 32;
 constexpr int MAXM = 16;          // controls of the fixed-size layouts (tiled kernels, the LQ twin, user twins)
-constexpr int kMaxControls = 32;  // controls a handle may have: 16 < nu <= 32 on the host-evaluated model's generic path (k_backward_w3w)
+constexpr int kMaxControls = 32;  // controls a handle may have: 16 < nu <= 32 on the host-evaluated model's generic path (k_backward_w3, two control tiles)
 
 // include/ilqr.h:24 -- the rounded literals, not 10^linspace(0,-3,11)
 __device__ __constant__ const double kAlpha[NALPHA] = {1.0000, 0.5012, 0.2512, 0.1259, 0.0631, 0.0316,

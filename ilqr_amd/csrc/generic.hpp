@@ -220,7 +220,7 @@ struct LqModel {
 
 // The LQ twin with 16 < nu <= 32 (GMW = 32 columns of B, a 32 x 32 R): the same model, run by the generic kernels only --
 // thread-per-rollout k_rollout_g (the accepted rollout re-run to commit it), point-by-point finite differences k_derivatives_g, and
-// k_backward_w3w on whole per-knot records.  It promises no structure to the sweep (the matrix-core LQ kernels are written for 32 x 16);
+// k_backward_w3 with two control tiles on whole per-knot records.  It promises no structure to the sweep (the matrix-core LQ kernels are written for 32 x 16);
 // its sums are LqModel's (left to right over the column index, padding adding exact zeros at the end).
 constexpr int GMW = 32;
 struct LqModelW {

@@ -104,7 +104,7 @@ struct ilqr_batch {
     bool staged = false, unfused = false, backward_w2 = false, lq_dense_fd = false, lq_thread_rollout = false, full_records = false, no_compaction = false, quad_chain = false;
     int fused = 0;  // 0 = by batch size
     int wide_occ = 0;  // wide tiles per CU: 0 = by batch size
-    bool two_control_tiles = false;  // generic backward pass: k_backward_w3w (two 16-column control tiles) -- what nu > 16 always runs
+    bool two_control_tiles = false;  // generic backward pass: k_backward_w3 with two 16-column control tiles (stage name "k_backward_w3w") -- what nu > 16 always runs
   } route;
   StageTimer timers[ILQR_NUM_STAGES];
   std::vector<hipEvent_t> event_pool;

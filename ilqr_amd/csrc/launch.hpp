@@ -213,21 +213,15 @@ static int launch_backward(ilqr_batch* h, int mode) {
     const double* crec = (fused || h->records_partial) ? h->const_rec : nullptr;
     const dim3 grid(h->B), block(64);
     const bool full = h->nu == WM && (h->nx == 16 || h->nx == 32);
-#define ILQR_W3(NT_, FULL_, LQF_) hipLaunchKernelGGL((k_backward_w3<NT_, FULL_, LQF_>), grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec)
+#define ILQR_W3(...) hipLaunchKernelGGL((k_backward_w3<__VA_ARGS__>), grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec)
     if (h->route.two_control_tiles) {  // nu > 16, or ILQR_ROUTE_TWO_CONTROL_TILES (ilqr_create keeps lq_fused, W2 and REGULARIZE_VXX off here)
-      if (h->nx > 16)
-        hipLaunchKernelGGL(k_backward_w3w<2>, grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec);
-      else
-        hipLaunchKernelGGL(k_backward_w3w<1>, grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec);
+      if (h->nx > 16) ILQR_W3(2, false, false, false, 2); else ILQR_W3(1, false, false, false, 2);
     } else if (h->route.backward_w2 && h->nx > 16)
       hipLaunchKernelGGL(k_backward_w2<2>, grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec);
     else if (h->route.backward_w2)
       hipLaunchKernelGGL(k_backward_w2<1>, grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec);
     else if (h->sp.fixes & 4) {  // ILQR_FLAG_REGULARIZE_VXX: the bounds-checked instantiations on whole records (ilqr_create keeps lq_fused off)
-      if (h->nx > 16)
-        hipLaunchKernelGGL((k_backward_w3<2, false, false, true>), grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec);
-      else
-        hipLaunchKernelGGL((k_backward_w3<1, false, false, true>), grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec);
+      if (h->nx > 16) ILQR_W3(2, false, false, true); else ILQR_W3(1, false, false, true);
     } else if (h->nx > 16) {
       if (fused) { if (full) ILQR_W3(2, true, true); else ILQR_W3(2, false, true); }
       else { if (full) ILQR_W3(2, true, false); else ILQR_W3(2, false, false); }

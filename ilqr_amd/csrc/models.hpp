@@ -371,7 +371,7 @@ struct has_analytic_record<M, std::void_t<decltype(std::declval<const M&>().anal
 //     template <class real_> struct UserModelT {
 //       using real = real_;
 //       static constexpr int NX = 4;             // state dimension, <= 32
-//       static constexpr int NU = 1;             // control dimension, <= 32 (more than 16: the backward pass k_backward_w3w, fp64)
+//       static constexpr int NU = 1;             // control dimension, <= 32 (more than 16: k_backward_w3 with two control tiles, fp64)
 //       real u_min[NU], u_max[NU];               // filled by ilqr_create from ilqr_desc.u_min / u_max
 //       ... its own parameters (plain data) ...
 //       void set_params(const double* p, int n);                                  // host: ilqr_desc.user_params

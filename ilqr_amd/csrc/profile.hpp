@@ -67,7 +67,7 @@ int ilqr_profile_shader_clock(ilqr_batch* h, double* mhz_out) {
 const char* ilqr_stage_kernel_name(ilqr_batch* h, int stage) {
   switch (stage) {
     case ILQR_STAGE_DERIVATIVES: return (h && h->aos) ? (h->lq_fused ? "" : (h->v.analytic && h->model == ILQR_MODEL_LQ && !h->lq_wide) ? "k_analytic_lq" : (h->model == ILQR_MODEL_LQ && !h->route.lq_dense_fd && !h->lq_wide) ? "k_derivatives_lq" : "k_derivatives_g") : "k_derivatives";
-    case ILQR_STAGE_BACKWARD:
+    case ILQR_STAGE_BACKWARD:  // ("k_backward_w3w": k_backward_w3 with two control tiles, MT = 2)
       if (h && h->aos) return h->route.two_control_tiles ? "k_backward_w3w" : h->route.backward_w2 ? "k_backward_w2" : "k_backward_w3";
       if (h && use_fused_sweep(h)) return "k_sweep_backward";  // what ilqr_iterate launches
       return (h && use_quad_backward(h)) ? "k_backward_q" : "k_backward_t";

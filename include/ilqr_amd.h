@@ -175,7 +175,7 @@ typedef struct ilqr_desc {
 enum ilqr_route {
   /* What ILQR_ROUTE_AUTO means for the arithmetic: on the nx = 4 path every route computes every element by the same expression in the
    * same order (bit-identical, tests/test_gpu_fused_sweep.py).  On the GENERIC path (n <= 32, m <= 16: LQ model, larger user twins,
-   * host-evaluated models; 16 < m <= 32: host-evaluated models, on k_backward_w3w with the literal box-QP in every step) the default backward kernel k_backward_w3 does NOT follow the reference's operation order: the box-QP's
+   * host-evaluated models; 16 < m <= 32: host-evaluated models, on k_backward_w3 with two control tiles and the literal box-QP in every step) the default backward kernel k_backward_w3 does NOT follow the reference's operation order: the box-QP's
    * inverse comes from a Newton-Schulz refinement of the previous knot's inverse (the literal Cholesky of src/boxqp.cpp:80-119 is its
    * fallback), the upper Vxx tile is the transpose of the lower one, matrix-vector products are per-lane sums.  Its gains equal the
    * reference-order kernel's and the oracle's to rounding (1e-9 on well-conditioned steps; the 1e-6 per-knot tolerance is what is
@@ -202,9 +202,9 @@ enum ilqr_route {
   ILQR_ROUTE_BACKWARD_W2 = 1024,    /* generic path: round 2's register kernel k_backward_w2 (literal Cholesky in every box-QP, per-knot cx / cu records)
                                        instead of k_backward_w3 (matrix-core refinement of the previous knot's inverse; LQ model with exact
                                        derivatives: no record array at all) */
-  ILQR_ROUTE_TWO_CONTROL_TILES = 8192 /* generic path, nu <= 16: the backward kernel of 16 < nu <= 32, k_backward_w3w (two 16-column control tiles,
-                                       the literal box-QP in every step), instead of k_backward_w3 (cross-check; not with ILQR_ROUTE_BACKWARD_W2 or
-                                       ILQR_FLAG_REGULARIZE_VXX) */
+  ILQR_ROUTE_TWO_CONTROL_TILES = 8192 /* generic path, nu <= 16: the backward kernel of 16 < nu <= 32, k_backward_w3 with two 16-column control
+                                       tiles and the literal box-QP in every step (stage name k_backward_w3w), instead of its one-tile step
+                                       (cross-check; not with ILQR_ROUTE_BACKWARD_W2 or ILQR_FLAG_REGULARIZE_VXX) */
 };
 
 const char* ilqr_last_error(void);
