@@ -1,5 +1,5 @@
 // capi.hip -- the entry points of the C ABI of include/ilqr_amd.h (creation, whole solves, stage calls, state exchange) on top of the
-// HIP kernels.  The handle and its helpers: handle.hpp; kernel launchers and route logic: launch.hpp; shard groups (RCCL):
+// HIP kernels.  The handle and its helpers: handle.hpp; which kernels a handle runs: route.hpp; kernel launchers: launch.hpp; shard groups (RCCL):
 // group.hpp; measurement: profile.hpp -- one translation unit (every kernel template is instantiated where it is launched).
 // No CPU compute path exists: every entry point either launches kernels or moves bytes.
 #include "../../include/ilqr_amd.h"
@@ -23,6 +23,7 @@
 
 using namespace ilqr;
 
+#include "route.hpp"
 #include "handle.hpp"
 #include "launch.hpp"
 
@@ -96,19 +97,12 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, d->device) == hipSuccess && khz > 0) h->wall_clock_khz = khz;
   }
   // route choices come with the descriptor (ilqr_desc.route, include/ilqr_amd.h): the library reads no environment
-  h->route.staged = false;
-  h->route.unfused = false;
-  h->route.backward_w2 = (d->route & ILQR_ROUTE_BACKWARD_W2) != 0;
-  h->route.lq_dense_fd = (d->route & ILQR_ROUTE_LQ_DENSE_FD) != 0;
   h->lq_wide = d->model == ILQR_MODEL_LQ && d->nu > WM;  // the LQ twin beyond 16 controls: LqModelW on the generic kernels
-  h->route.lq_thread_rollout = (d->route & ILQR_ROUTE_LQ_THREAD_ROLLOUT) != 0 || h->lq_wide;  // (k_rollout_lq is written for 32 x 16)
   h->route.full_records = (d->route & ILQR_ROUTE_FULL_RECORDS) != 0;
   h->route.no_compaction = (d->route & ILQR_ROUTE_NO_COMPACTION) != 0;
-  h->route.quad_chain = (d->route & ILQR_ROUTE_QUAD_CHAIN) != 0;
-  h->route.fused = d->route & 3;
   h->route.wide_occ = (d->route & ILQR_ROUTE_WIDE_ONE_PER_CU) ? 1 : (d->route & ILQR_ROUTE_WIDE_TWO_PER_CU) ? 2 : 0;
-  h->route.two_control_tiles = d->nu > WM || (d->route & ILQR_ROUTE_TWO_CONTROL_TILES) != 0;  // (generic handles only: the nx = 4 kernels ignore it)
   if (d->assume_cus > 0) h->num_cus = d->assume_cus;
+  h->aos = generic_layout(d->model, d->route, kUserTiled, kUserSmall);
   h->device = d->device;
   if (d->stream) {
     h->stream = (hipStream_t)d->stream;
@@ -181,10 +175,7 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
     REQUIRE(d->u_min && d->u_max, "ILQR_MODEL_USER needs u_min/u_max (Model::u_min/u_max, include/model.h:17)");
     REQUIRE(!(d->flags & ILQR_FLAG_ANALYTIC_DERIVATIVES) || has_analytic_record<UM>::value, "this user model has no analytic_record()");
     // not a tiled shape -- or a small one asked to take the generic route: the generic kernels (fp64), trajectory-contiguous layout like the LQ model's
-    if (!kUserTiled || (kUserSmall && (d->route & ILQR_ROUTE_WAVE_PER_TRAJECTORY))) {
-      REQUIRE(d->dtype == ILQR_DTYPE_F64, "the generic nx <= 32 path is fp64");
-      h->aos = true;
-    }
+    if (h->aos) REQUIRE(d->dtype == ILQR_DTYPE_F64, "the generic nx <= 32 path is fp64");
     REQUIRE(d->n_user_params >= 0 && (d->n_user_params == 0 || d->user_params), "ILQR_MODEL_USER: n_user_params = %d with user_params = %p", d->n_user_params, (const void*)d->user_params);
     h->user_f.set_params(d->user_params, d->n_user_params);
     if (h->dtype == ILQR_DTYPE_F32) {  // the twin the finite differences are taken in: built from the parameters' FLOAT values, like the shipped models'
@@ -211,7 +202,6 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
     REQUIRE(d->u_min && d->u_max, "generic handles need u_min/u_max (Model::u_min/u_max, include/model.h:17)");
     if (d->model == ILQR_MODEL_LQ)
       REQUIRE(d->lq_A && d->lq_B && d->lq_Q && d->lq_R && d->lq_Qf, "ILQR_MODEL_LQ needs lq_A, lq_B, lq_Q, lq_R, lq_Qf");
-    h->aos = true;
   } else {
     return fail(ILQR_ERR_UNSUPPORTED, "model id %d is not available in this build", d->model);
   }
@@ -239,7 +229,7 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
     rc |= dev_alloc(h, &h->d_umax, nu);
     v.cand_u = nullptr;
     v.cand_x = nullptr;
-    if (d->model == ILQR_MODEL_LQ && !h->route.lq_thread_rollout && !(d->route & ILQR_ROUTE_LQ_RECOMMIT)) {
+    if (lq_matrix_core_search(d->model, d->nu, d->route) && !(d->route & ILQR_ROUTE_LQ_RECOMMIT)) {
       // the eleven rollouts of the matrix-core search, whole ([b][alpha][t][row]): the commit is then a copy, not a twelfth rollout
       // (11 x the nominal trajectory, ~7 GB at configs[4]: if the device cannot spare them the handle works without -- the ILQR_ROUTE_LQ_RECOMMIT route)
       void *cx = nullptr, *cu = nullptr;
@@ -336,6 +326,7 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
   if (!rc && hipMemsetAsync(h->commit_idx, 0xFF, Bp * sizeof(int), h->stream) != hipSuccess) rc = 1;
   if (rc) return ILQR_ERR_HIP;
   sync_float_view(h);
+  h->plan = plan_route({d->model, d->nx, d->nu, d->flags, d->route, h->ntiles, h->num_cus, kUserTiled, kUserSmall, v.cand_x != nullptr});
 
   h->sp.max_iter = h->params.max_iter;
   h->sp.tol_fun = h->params.tol_fun;
@@ -348,7 +339,7 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
   h->sp.fixes = ((h->flags & ILQR_FLAG_REFERENCE_FIXES) ? 3 : 0) | ((h->flags & ILQR_FLAG_REGULARIZE_VXX) ? 4 : 0);
   // generic handles: ILQR_FLAG_REFERENCE_FIXES -- models with a device twin: their rollouts clamp, their box-QP reports a failed factorisation; the
   // host-evaluated route: the box-QP likewise, the rollouts belong to the caller (the facade clamps).  ILQR_FLAG_REGULARIZE_VXX is the backward pass's alone (k_backward_w3<.., REGV>), on any model
-  if ((h->sp.fixes & 4) && h->aos && h->route.backward_w2)
+  if ((h->sp.fixes & 4) && h->aos && (d->route & ILQR_ROUTE_BACKWARD_W2))
     return fail(ILQR_ERR_UNSUPPORTED, "ILQR_FLAG_REGULARIZE_VXX on the generic path is implemented in k_backward_w3: drop ILQR_ROUTE_BACKWARD_W2");
   // (a host-evaluated model under ILQR_FLAG_REFERENCE_FIXES: part (2), the failed factorisation that ends the box-QP, is the device's -- k_backward_w3 /
   //  k_backward_w2 honour sp.fixes & 2 --; part (1), the clamped rollout, belongs to whoever rolls out: the C++ facade's host_forward does it)
@@ -356,8 +347,7 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
   hipLaunchKernelGGL(k_reset_state<double>, dim3((h->Bp + 255) / 256), dim3(256), 0, h->stream, h->v, h->params.lambda_init,
                      h->params.dlambda_init);
   HIPCHK(hipGetLastError());
-  h->lq_fused = h->model == ILQR_MODEL_LQ && v.analytic && !h->route.full_records && !h->route.backward_w2 && !(h->sp.fixes & 4) && !h->route.two_control_tiles;
-  if (h->lq_fused) {  // both constant records, once (what = 3)
+  if (h->plan.derivatives == Derivatives::fused_lq) {  // both constant records, once (what = 3)
     hipLaunchKernelGGL(k_analytic_lq, dim3(1), dim3(64), 0, h->stream, h->v, h->lq, 1, 3, h->const_rec, kAnalyticChunk);
     HIPCHK(hipGetLastError());
   }
@@ -448,24 +438,21 @@ int ilqr_iterate(ilqr_batch* h, int n_iters) {
     explicit Chain(ilqr_batch* hh) : h(hh) { h->chain_timers = true; h->chain_event = nullptr; }
     ~Chain() { h->chain_timers = false; h->chain_event = nullptr; }
   } chain(h);
-  if (n_iters > 0) h->cands_valid = !(h->active_tiles > 0 && h->active_tiles < h->ntiles);  // (a compacted chunk rolls out the leading tiles only)
-  if (use_persistent(h) && n_iters > 0) {
+  if (n_iters > 0) h->cands = (h->active_tiles > 0 && h->active_tiles < h->ntiles) ? Cands::none : Cands::planes;  // (a compacted chunk rolls out the leading tiles only)
+  if (h->plan.solve != Solve::none && n_iters > 0) {
     if (int rc = launch_solve_tiles(h, n_iters)) return rc;
     return flush_commit(h);
   }
   for (int it = 0; it < n_iters; it++) {
-    if (use_fused_sweep(h)) {
+    if (h->plan.sweep != Sweep::none) {
       if (int rc = launch_sweep_backward(h, 1, h->sp.fixed_work)) return rc;  // STEP 1 + STEP 2
     } else {
       if (int rc = launch_derivatives(h, h->sp.fixed_work)) return rc;  // STEP 1
       if (int rc = launch_backward(h, 1)) return rc;                    // STEP 2
     }
-    if (!h->aos) {  // STEP 3 + STEP 3/4 in one launch: the rollout block of a tile also accepts for it
+    if (h->plan.rollout == Rollout::tiled || h->plan.rollout == Rollout::lq_accept) {
+      // STEP 3 + STEP 3/4 in one launch: the rollout block of a tile, or k_rollout_lq<RG_SEARCH, true>, also accepts
       if (int rc = launch_rollout(h, true, true, line_search_alphas(), NALPHA, h->v.cost_c, 1, true)) return rc;
-      h->commit_pending = true;
-    } else if (lq_search_accepts(h)) {  // STEP 3 + STEP 3/4 in one launch (k_rollout_lq<RG_SEARCH, true>); the commit is a copy (k_commit_lq)
-      if (int rc = launch_rollout(h, true, true, line_search_alphas(), NALPHA, h->v.cost_c, 1, true)) return rc;
-      h->cands_valid = true;
       h->commit_pending = true;
     } else {
       if (int rc = do_rollout_candidates(h, 1)) return rc;              // STEP 3
@@ -541,7 +528,7 @@ static int apply_permutation(ilqr_batch* h, const std::vector<int>& perm) {
   rc |= scalar(v.backpass_done, Bp);
   if (rc) return rc;
   h->recs = ilqr_batch::REC_STALE;
-  h->cands_valid = false;  // the candidates stayed where they were
+  h->cands = Cands::none;  // the candidates stayed where they were
   return 0;
 }
 
@@ -555,7 +542,7 @@ int ilqr_generate_trajectory(ilqr_batch* h) {
   // the per-trajectory arrays, ~0.1 ms per 4096 trajectories), and only those tiles are launched from then on.  The
   // original order is restored before returning.  Trajectories never interact and no kernel's arithmetic depends on a
   // trajectory's slot: statuses, iteration counts and costs are bit-identical (tests/test_gpu_full_solves.py).
-  const bool persistent = use_persistent(h);
+  const bool persistent = h->plan.solve != Solve::none;
   const bool compacting = persistent && h->ntiles > h->num_cus && !(h->sp.fixed_work) && !h->route.no_compaction;
   int done_iters = 0;
   const int chunk = persistent ? (compacting ? std::min(std::max(1, h->params.max_iter), 8) : std::max(1, h->params.max_iter)) : 10;  // (a persistent tile stops by itself)
@@ -626,7 +613,7 @@ int ilqr_warm_start(ilqr_batch* h, const double* x0) {
   // forward_pass(x_0, us) with the stored gains: u = us[t] + K[t](x - xs[t])  (alpha*k term = 0)
   AlphaSet al;
   for (int i = 0; i < NALPHA; i++) al.a[i] = 0.0;
-  if (generic_twin(h)) {  // generic path: the rollout itself overwrites xs/us (slot 0 of `al` for everyone)
+  if (h->plan.commit != Commit::tiled) {  // generic path: the rollout itself overwrites xs/us (slot 0 of `al` for everyone)
     HIPCHK(hipMemsetAsync(h->commit_idx, 0, (size_t)h->Bp * sizeof(int), h->stream));
     if (int rc = launch_rollout(h, true, true, al, 1, h->v.cost, 0)) return rc;
   } else {
@@ -851,12 +838,12 @@ int ilqr_get_candidate(ilqr_batch* h, int a, double* xs, double* us) {
   if (!h) return fail(ILQR_ERR_INVALID, "null handle");
   if (host_model(h)) return no_device_model();
   REQUIRE(a >= 0 && a < NALPHA, "alpha index %d out of range", a);
-  if (!h->cands_valid)
+  if (h->cands == Cands::none)
     return fail(ILQR_ERR_STATE, "no candidates: none rolled out yet, or the solve re-packed running trajectories (compaction) and left the "
                                 "candidate buffers behind -- call ilqr_rollout_candidates / ilqr_iterate first");
   HIPCHK(hipSetDevice(h->device));
   if (h->aos) {  // generic handles keep candidates only on the LQ matrix-core route: [b][alpha][t][row], whole trajectories
-    if (!(h->model == ILQR_MODEL_LQ && h->lq_cands_kept && h->v.cand_x))
+    if (!(h->plan.commit == Commit::lq_copy && h->lq_cands_kept))
       return fail(ILQR_ERR_UNSUPPORTED, "this handle's line search keeps no candidate trajectories (only their costs: ilqr_rollout_candidates)");
     const size_t wx = (size_t)(h->T + 1) * h->nx * sizeof(double), wu = (size_t)h->T * h->nu * sizeof(double);
     if (xs) HIPCHK(hipMemcpy2DAsync(xs, wx, (const char*)h->v.cand_x + (size_t)a * wx, (size_t)NALPHA * wx, wx, h->B, hipMemcpyDeviceToHost, h->stream));
@@ -871,12 +858,11 @@ int ilqr_get_candidate(ilqr_batch* h, int a, double* xs, double* us) {
   const dim3 grid(grid_for((size_t)h->B * (h->T + 1), 256)), block(256);
   if (int rc = with_model(h, [&](auto& v, auto& m, auto&) {
         using MM = std::decay_t<decltype(m)>;
-        if constexpr (MM::NX == 4 && MM::NU == 1) {
-          if (h->cands_grouped) {
+        if constexpr (MM::NX == 4 && MM::NU == 1)
+          if (h->cands == Cands::grouped) {
             hipLaunchKernelGGL((k_unpack_cand<MM, true>), grid, block, 0, h->stream, v, m, a, dxs, dus);
             return 0;
           }
-        }
         hipLaunchKernelGGL((k_unpack_cand<MM>), grid, block, 0, h->stream, v, m, a, dxs, dus);
         return 0;
       }))

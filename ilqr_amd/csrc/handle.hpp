@@ -33,6 +33,8 @@ struct StageTimer {
   int launches = 0;
 };
 
+enum class Cands { none, planes, grouped };  // what the candidate buffers hold (ilqr_batch::cands)
+
 struct ilqr_batch {
   int model, nx, nu, T, B, Bp, ntiles, device, flags;
   int dtype = ILQR_DTYPE_F64;   // arithmetic of the nx = 4 device models (ilqr_desc.dtype)
@@ -67,9 +69,8 @@ struct ilqr_batch {
   // per knot only cx, cu; records_partial says that D holds no matrices for t < T right now
   double* const_rec = nullptr;   // [2][REC]: the constant blocks of every knot t < T, then knot T's record
   bool records_partial = false;
-  // ... on the k_backward_w3 route (lq_fused) no sweep runs at all: the backward pass forms cx = cxx x_t, cu = cuu u_t from the knot, and the
-  // record array D is allocated only if somebody asks for records (getters, ilqr_set_derivatives, the finite-difference mode)
-  bool lq_fused = false;          // the handle can take that route (LQ model, exact derivatives, k_backward_w3, no ILQR_ROUTE_FULL_RECORDS)
+  // ... on the fused LQ route (plan.derivatives == Derivatives::fused_lq) no sweep runs at all: the backward pass forms cx = cxx x_t, cu = cuu u_t
+  // from the knot, and the record array D is allocated only if somebody asks for records (getters, ilqr_set_derivatives)
   bool lq_fused_stale = false;    // fused iterations have run since D was last written: a getter gets the records of the current nominal computed
   bool lq_caller_records = false; // ilqr_set_derivatives replaced the model's blocks: the next backward pass reads D, not the model
   // nx = 4 device models: D (0.75 GB per 4096 acrobot trajectories) is allocated the first time somebody wants
@@ -83,10 +84,10 @@ struct ilqr_batch {
   bool initialised = false;  // init_traj / set_trajectory has run
   bool commit_pending = false;  // an accepted candidate is not yet copied into xs/us
   bool lq_cands_kept = false;   // LQ model: the last search rollout (k_rollout_lq<RG_SEARCH>) stored its candidates in v.cand_x / v.cand_u
-  // cand_u / cand_x / cost_c hold, slot for slot, the last rollouts of the trajectories now in those slots.  Compaction
-  // (ilqr_generate_trajectory) moves trajectories without moving their candidates: after it they belong to nobody.
-  bool cands_valid = false;
-  bool cands_grouped = false;  // ... and lie in k_solve_hex's grouped layout (rollout.hpp: CANDT) instead of one element per trajectory
+  // cand_u / cand_x / cost_c hold, slot for slot, the last rollouts of the trajectories now in those slots (none: they belong to nobody --
+  // compaction, ilqr_generate_trajectory, moves trajectories without moving their candidates), one alpha plane after the other or in
+  // k_solve_hex's grouped layout (rollout.hpp: CANDT).  k_commit and k_derivatives' fused commit read planes only.
+  Cands cands = Cands::none;
   bool aos = false;             // host-model / generic handles: trajectory-contiguous layout, wave-per-trajectory backward
   double* d_umin = nullptr;     // [nu] device copies of the limits (generic kernel)
   double* d_umax = nullptr;
@@ -98,13 +99,12 @@ struct ilqr_batch {
   int* d_perm = nullptr;       // [Bp]
   void* perm_scratch = nullptr;  // as large as the largest per-knot array
   size_t perm_scratch_bytes = 0;
-  // Route choices for A/B runs and the bit-identity tests: ilqr_desc.route, fixed at ilqr_create -- a handle never changes
-  // kernels between calls, and nothing is read from the environment
+  // The kernels of every stage (route.hpp), fixed at ilqr_create -- a handle never changes kernels between calls, and nothing is read
+  // from the environment -- and the ilqr_desc.route knobs the launchers pass on
+  RoutePlan plan;
   struct {
-    bool staged = false, unfused = false, backward_w2 = false, lq_dense_fd = false, lq_thread_rollout = false, full_records = false, no_compaction = false, quad_chain = false;
-    int fused = 0;  // 0 = by batch size
-    int wide_occ = 0;  // wide tiles per CU: 0 = by batch size
-    bool two_control_tiles = false;  // generic backward pass: k_backward_w3 with two 16-column control tiles (stage name "k_backward_w3w") -- what nu > 16 always runs
+    bool full_records = false, no_compaction = false;
+    int wide_occ = 0;  // wide tiles per CU: 0 = by the active tile count
   } route;
   StageTimer timers[ILQR_NUM_STAGES];
   std::vector<hipEvent_t> event_pool;
@@ -155,11 +155,6 @@ static int with_model(ilqr_batch* h, F&& f) {
     }
   }
   return fail(ILQR_ERR_UNSUPPORTED, "model %d has no device kernels of this kind", h->model);
-}
-// f(view) for the handle's arithmetic
-template <class F>
-static int with_view(ilqr_batch* h, F&& f) {
-  return h->dtype == ILQR_DTYPE_F32 ? f(h->vf) : f(h->v);
 }
 // ILQR_MODEL_HOST: the model exists only as host code; nothing but the backward pass runs here
 static bool host_model(const ilqr_batch* h) { return h->model == ILQR_MODEL_HOST; }

@@ -1,5 +1,5 @@
-// launch.hpp -- kernel launchers of the C ABI: dispatch on the handle's device model and arithmetic, and the ROUTE logic (which of
-// several equivalent kernels a handle's batch size / flags / ilqr_desc.route select: DESIGN.md 3.2).  Included once, by capi.hip.
+// launch.hpp -- kernel launchers of the C ABI: dispatch on the handle's device model and arithmetic, and on its route plan (which of
+// several equivalent kernels it runs: route.hpp).  Included once, by capi.hip.
 #pragma once
 #include "handle.hpp"
 
@@ -28,11 +28,6 @@ static int launch_rollout_t(ilqr_batch* h, const V& v, const M& m, bool gains, b
   HIPCHK(hipGetLastError());
   return 0;
 }
-// Does the handle's model have a device twin in the GENERIC kernels (generic.hpp)?  The shipped LQ model, or the build's user
-// model when its dimensions are not a tiled nx = 4 shape.
-static bool generic_twin(const ilqr_batch* h) {
-  return h->model == ILQR_MODEL_LQ || (h->model == ILQR_MODEL_USER && h->aos);
-}
 // f(model) for the handle's generic device twin
 template <class F>
 static int with_generic_model(ilqr_batch* h, F&& f) {
@@ -47,23 +42,21 @@ static int with_generic_model(ilqr_batch* h, F&& f) {
 // matrix cores (k_rollout_lq, one wavefront per trajectory); ILQR_ROUTE_LQ_THREAD_ROLLOUT selects the
 // generic thread-per-rollout kernel (same results bit for bit; kept as the cross-check and as the
 // template for device models without matrix structure).
-// Does the handle's search kernel also accept and commit (k_rollout_lq<RG_SEARCH, true>)?  The LQ model's matrix-core rollout with candidate buffers.
-static bool lq_search_accepts(const ilqr_batch* h) { return h->model == ILQR_MODEL_LQ && !h->route.lq_thread_rollout && h->v.cand_x != nullptr; }
 template <class M>
 static int launch_rollout_g(ilqr_batch* h, const M& m, int what, const AlphaSet& al, double* cost_out, int mode, int write_cost, bool with_accept = false) {
   if constexpr (std::is_same<M, LqModel>::value)
-  if (!h->route.lq_thread_rollout) {
+  if (h->plan.rollout != Rollout::generic) {
     const dim3 grid(h->B), block(64);
-    if (what == RG_SEARCH && with_accept && h->v.cand_x) {
+    const bool keeps = h->plan.rollout == Rollout::lq_accept;  // candidate buffers: the commit of what the next accept chooses is a copy (launch_commit)
+    if (what == RG_SEARCH && with_accept && keeps)
       hipLaunchKernelGGL((k_rollout_lq<RG_SEARCH, true>), grid, block, 0, h->stream, h->v, m, al, cost_out, h->commit_idx, mode, 0, h->sp);
-      h->lq_cands_kept = true;
-    } else if (what == RG_SEARCH) {
+    else if (what == RG_SEARCH)
       hipLaunchKernelGGL((k_rollout_lq<RG_SEARCH>), grid, block, 0, h->stream, h->v, m, al, cost_out, nullptr, mode, 0, h->sp);
-      h->lq_cands_kept = h->v.cand_x != nullptr;  // the commit of what the next accept chooses is a copy (launch_commit)
-    } else if (what == RG_INIT)
+    else if (what == RG_INIT)
       hipLaunchKernelGGL((k_rollout_lq<RG_INIT>), grid, block, 0, h->stream, h->v, m, al, cost_out, nullptr, 0, 1, h->sp);
     else
       hipLaunchKernelGGL((k_rollout_lq<RG_COMMIT>), grid, block, 0, h->stream, h->v, m, al, cost_out, h->commit_idx, 0, write_cost, h->sp);
+    if (what == RG_SEARCH) h->lq_cands_kept = keeps;
     HIPCHK(hipGetLastError());
     return 0;
   }
@@ -84,33 +77,32 @@ static int launch_rollout(ilqr_batch* h, bool gains, bool cand, const AlphaSet& 
                           bool with_accept = false) {
   std::pair<hipEvent_t, hipEvent_t> ev;
   if (int rc = timer_begin(h, ILQR_STAGE_ROLLOUT, &ev)) return rc;
-  int rc;
-  if (generic_twin(h)) {
-    rc = with_generic_model(h, [&](auto& m) {
-      if (!gains) return launch_rollout_g(h, m, RG_INIT, al, cost_out, 0, 1);
-      if (n_alpha == NALPHA) return launch_rollout_g(h, m, RG_SEARCH, al, cost_out, mode, 0, with_accept);
-      return launch_rollout_g(h, m, RG_COMMIT, al, cost_out, 0, 1);  // a single closed-loop rollout written in place (warm start): slot commit_idx of `al`
-    });
-    if (rc) return rc;
-    return timer_end(h, ILQR_STAGE_ROLLOUT, ev);
-  }
-  rc = with_model(h, [&](auto& v, auto& m, auto&) { return launch_rollout_t(h, v, m, gains, cand, al, n_alpha, cost_out, mode, with_accept); });
+  const int rc = (h->plan.rollout != Rollout::tiled)
+      ? with_generic_model(h, [&](auto& m) {
+          if (!gains) return launch_rollout_g(h, m, RG_INIT, al, cost_out, 0, 1);
+          if (n_alpha == NALPHA) return launch_rollout_g(h, m, RG_SEARCH, al, cost_out, mode, 0, with_accept);
+          return launch_rollout_g(h, m, RG_COMMIT, al, cost_out, 0, 1);  // a single closed-loop rollout written in place (warm start): slot commit_idx of `al`
+        })
+      : with_model(h, [&](auto& v, auto& m, auto&) { return launch_rollout_t(h, v, m, gains, cand, al, n_alpha, cost_out, mode, with_accept); });
   if (rc) return rc;
-  if (cand) h->cands_grouped = false;  // (the stage kernels write the alpha planes)
+  if (cand && h->cands == Cands::grouped) h->cands = Cands::planes;  // (the stage kernels write the alpha planes)
   return timer_end(h, ILQR_STAGE_ROLLOUT, ev);
+}
+
+static int refuse_grouped_cands(ilqr_batch* h) {  // k_commit and k_derivatives' fused commit index the candidates as alpha planes
+  return h->cands != Cands::grouped ? 0 : fail(ILQR_ERR_STATE, "the candidate buffers hold k_solve_hex's grouped layout: nothing reads them as alpha planes");
 }
 
 static AlphaSet line_search_alphas();
 static int launch_commit(ilqr_batch* h) {
-  if (generic_twin(h)) {
-    if (h->model == ILQR_MODEL_LQ && h->lq_cands_kept) {  // the matrix-core search kept its eleven rollouts: copy the accepted one
-      hipLaunchKernelGGL(k_commit_lq, dim3(h->B), dim3(256), 0, h->stream, h->v, h->nx, h->nu, h->commit_idx);
-      HIPCHK(hipGetLastError());
-      return 0;
-    }
-    // no stored candidates otherwise on the generic path: re-run the accepted rollout in place
-    return with_generic_model(h, [&](auto& m) { return launch_rollout_g(h, m, RG_COMMIT, line_search_alphas(), h->v.cost, 0, 0); });
+  if (h->plan.commit == Commit::lq_copy && h->lq_cands_kept) {  // the matrix-core search kept its eleven rollouts: copy the accepted one
+    hipLaunchKernelGGL(k_commit_lq, dim3(h->B), dim3(256), 0, h->stream, h->v, h->nx, h->nu, h->commit_idx);
+    HIPCHK(hipGetLastError());
+    return 0;
   }
+  if (h->plan.commit != Commit::tiled)  // no stored candidates otherwise on the generic path: re-run the accepted rollout in place
+    return with_generic_model(h, [&](auto& m) { return launch_rollout_g(h, m, RG_COMMIT, line_search_alphas(), h->v.cost, 0, 0); });
+  if (int rc = refuse_grouped_cands(h)) return rc;
   dim3 grid((h->T + 1 + 15) / 16, h->ntiles), block(256);
   if (int rc = with_model(h, [&](auto& v, auto& m, auto&) {
         hipLaunchKernelGGL((k_commit<std::decay_t<decltype(m)>>), grid, block, 0, h->stream, v, m, h->commit_idx);
@@ -139,45 +131,46 @@ static int forget_pending(ilqr_batch* h) {
   h->records_partial = false;
   h->lq_fused_stale = false;
   h->lq_caller_records = false;
-  h->cands_valid = false;  // (candidates of an earlier solve are nobody's)
+  h->cands = Cands::none;  // (candidates of an earlier solve are nobody's)
   h->commit_pending = false;
   HIPCHK(hipMemsetAsync(h->commit_idx, 0xFF, (size_t)h->Bp * sizeof(int), h->stream));  // all -1
   return 0;
 }
 
 static int launch_derivatives(ilqr_batch* h, int force) {
-  if (generic_twin(h))  // the generic sweep has no fused commit: rebuild the accepted rollout first
+  const Derivatives route = h->plan.derivatives;
+  if (route != Derivatives::tiled)  // the generic sweep has no fused commit: rebuild the accepted rollout first
     if (int rc = flush_commit(h)) return rc;
-  if (h->lq_fused) {  // k_backward_w3<.., LQF> forms cx, cu from the knot itself: no sweep, no record array
+  if (route == Derivatives::fused_lq) {  // k_backward_w3<.., LQF> forms cx, cu from the knot itself: no sweep, no record array
     h->lq_fused_stale = true;
     h->lq_caller_records = false;
     return 0;
   }
+  if (route == Derivatives::tiled && h->commit_pending)
+    if (int rc = refuse_grouped_cands(h)) return rc;
   if (int rc = ensure_records(h)) return rc;
   h->recs = ilqr_batch::REC_VALID;
   std::pair<hipEvent_t, hipEvent_t> ev;
   if (int rc = timer_begin(h, ILQR_STAGE_DERIVATIVES, &ev)) return rc;
   dim3 grid((h->T + 1 + 15) / 16, h->ntiles), block(256);
   const int* ci = h->commit_pending ? h->commit_idx : nullptr;
-  if (generic_twin(h)) {
-    if (h->v.analytic && h->model == ILQR_MODEL_LQ && !h->lq_wide) {
+  if (route != Derivatives::tiled) {
+    if (route == Derivatives::analytic_lq) {
       const int what = h->route.full_records ? 0 : 1;  // (A/B runs and the bit-identity test)
       const int chunk = (what == 1) ? 4 * kAnalyticChunk : kAnalyticChunk;
       const int nchunk = (h->T + 1 + chunk - 1) / chunk;
       hipLaunchKernelGGL(k_analytic_lq, dim3(h->B * nchunk), dim3(64), 0, h->stream, h->v, h->lq, force, what, h->const_rec, chunk);
       h->records_partial = (what == 1);
-    } else {
-      if (h->model == ILQR_MODEL_LQ && !h->route.lq_dense_fd && !h->lq_wide) {
-        // the LQ twin: every perturbed point of the knots t < T evaluated by what moved (k_derivatives_lq), knot T by the generic sweep
-        const int nchunk = (h->T + kLqKnotsPerWave - 1) / kLqKnotsPerWave;
-        hipLaunchKernelGGL(k_derivatives_lq, dim3(h->B * nchunk), dim3(64), 0, h->stream, h->v, h->lq, force);
-        hipLaunchKernelGGL((k_derivatives_g<LqModel>), dim3(h->B), dim3(64), 0, h->stream, h->v, h->lq, force, h->T);
-      } else if (int rc = with_generic_model(h, [&](auto& m) {
-            hipLaunchKernelGGL((k_derivatives_g<std::decay_t<decltype(m)>>), dim3(h->B * (h->T + 1)), dim3(64), 0, h->stream, h->v, m, force, -1);
-            return 0;
-          }))
-        return rc;
-    }
+    } else if (route == Derivatives::lq) {
+      // the LQ twin: every perturbed point of the knots t < T evaluated by what moved (k_derivatives_lq), knot T by the generic sweep
+      const int nchunk = (h->T + kLqKnotsPerWave - 1) / kLqKnotsPerWave;
+      hipLaunchKernelGGL(k_derivatives_lq, dim3(h->B * nchunk), dim3(64), 0, h->stream, h->v, h->lq, force);
+      hipLaunchKernelGGL((k_derivatives_g<LqModel>), dim3(h->B), dim3(64), 0, h->stream, h->v, h->lq, force, h->T);
+    } else if (int rc = with_generic_model(h, [&](auto& m) {
+                 hipLaunchKernelGGL((k_derivatives_g<std::decay_t<decltype(m)>>), dim3(h->B * (h->T + 1)), dim3(64), 0, h->stream, h->v, m, force, -1);
+                 return 0;
+               }))
+      return rc;
     HIPCHK(hipGetLastError());
     return timer_end(h, ILQR_STAGE_DERIVATIVES, ev);
   }
@@ -193,34 +186,29 @@ static int launch_derivatives(ilqr_batch* h, int force) {
   return timer_end(h, ILQR_STAGE_DERIVATIVES, ev);
 }
 
-static bool use_quad_backward(const ilqr_batch* h) {
-  if (h->nx != 4) return false;
-  if (h->flags & ILQR_FLAG_BACKWARD_THREAD_PER_TRAJ) return false;
-  return true;
-}
-
 static int launch_backward(ilqr_batch* h, int mode) {
   if (!h->aos)
     if (int rc = materialise_records(h)) return rc;
   std::pair<hipEvent_t, hipEvent_t> ev;
   if (int rc = timer_begin(h, ILQR_STAGE_BACKWARD, &ev)) return rc;
-  if (h->aos) {
+  const Backward route = h->plan.backward;
+  if (route != Backward::quad && route != Backward::thread) {
     // the register-resident kernels, two (nx > 16) or more (nx <= 16) wavefronts per SIMD: k_backward_w3, or with ILQR_ROUTE_BACKWARD_W2 the
     // literal-order k_backward_w2 (round 1's LDS kernel k_backward_w, whose bits k_backward_w2 reproduces, was retired in ABI 5)
-    const bool fused = h->lq_fused && !h->lq_caller_records;  // cx, cu from the knot, the matrices from const_rec: D untouched
+    const bool fused = h->plan.derivatives == Derivatives::fused_lq && !h->lq_caller_records;  // cx, cu from the knot, the matrices from const_rec: D untouched
     if (!fused)
       if (int rc = ensure_records(h)) return rc;
     const double* crec = (fused || h->records_partial) ? h->const_rec : nullptr;
     const dim3 grid(h->B), block(64);
     const bool full = h->nu == WM && (h->nx == 16 || h->nx == 32);
 #define ILQR_W3(...) hipLaunchKernelGGL((k_backward_w3<__VA_ARGS__>), grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec)
-    if (h->route.two_control_tiles) {  // nu > 16, or ILQR_ROUTE_TWO_CONTROL_TILES (ilqr_create keeps lq_fused, W2 and REGULARIZE_VXX off here)
+    if (route == Backward::w3_two_tiles) {  // nu > 16, or ILQR_ROUTE_TWO_CONTROL_TILES (never the fused LQ route; ilqr_create keeps W2 and REGULARIZE_VXX off here)
       if (h->nx > 16) ILQR_W3(2, false, false, false, 2); else ILQR_W3(1, false, false, false, 2);
-    } else if (h->route.backward_w2 && h->nx > 16)
+    } else if (route == Backward::w2 && h->nx > 16)
       hipLaunchKernelGGL(k_backward_w2<2>, grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec);
-    else if (h->route.backward_w2)
+    else if (route == Backward::w2)
       hipLaunchKernelGGL(k_backward_w2<1>, grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec);
-    else if (h->sp.fixes & 4) {  // ILQR_FLAG_REGULARIZE_VXX: the bounds-checked instantiations on whole records (ilqr_create keeps lq_fused off)
+    else if (route == Backward::w3_regv) {  // ILQR_FLAG_REGULARIZE_VXX: the bounds-checked instantiations on whole records (never the fused LQ route)
       if (h->nx > 16) ILQR_W3(2, false, false, true); else ILQR_W3(1, false, false, true);
     } else if (h->nx > 16) {
       if (fused) { if (full) ILQR_W3(2, true, true); else ILQR_W3(2, false, true); }
@@ -229,7 +217,7 @@ static int launch_backward(ilqr_batch* h, int mode) {
       if (fused) ILQR_W3(1, false, true); else ILQR_W3(1, false, false);
     }
 #undef ILQR_W3
-  } else if (use_quad_backward(h)) {
+  } else if (route == Backward::quad) {
     dim3 grid(h->ntiles), block(64);  // one wavefront = one tile of 16 trajectories x 4 lanes
     if (int rc = with_model(h, [&](auto& v, auto& m, auto&) {
           if constexpr (std::decay_t<decltype(m)>::NX == 4)
@@ -249,47 +237,20 @@ static int launch_backward(ilqr_batch* h, int mode) {
   return timer_end(h, ILQR_STAGE_BACKWARD, ev);
 }
 
-// Which route ilqr_iterate takes.  All of them leave the same bits (tests/test_gpu_fused_sweep.py):
-//   ntiles <= #CU, m = 1, no fixes     one persistent tile per CU, its backward pass as four matrix-core chains   k_solve_hex
-//   ntiles <= #CU otherwise            one persistent 16-trajectory tile per CU            k_solve_tile<.., 1>
-//   m = 1, no opt-in fixes, > 2 tiles per CU    64-trajectory wide tiles, one or two per CU   k_solve_wide
-//   anything larger otherwise          persistent 16-trajectory tiles, two per CU (the dispatcher hands a CU its next
-//                                      tile when one is through)                           k_solve_tile<.., 2>
-//   ILQR_FLAG_STAGED                   one launch per stage: k_sweep_backward (records in the LDS ring, one block per CU
-//                                      or the one-producer variant, two per CU) up to two tiles per CU, beyond that
-//                                      k_derivatives + k_backward_q with the records in HBM
-//   ILQR_FLAG_UNFUSED, AoS (generic) models   always the two-kernel route
-// ilqr_desc.route (ILQR_ROUTE_TILE_PER_CU / TWO_TILES_PER_CU / WIDE_TILES) forces a variant for A/B runs and the bit-identity tests.
-static int fused_variant(const ilqr_batch* h) {  // 0: two kernels, 1: one tile per CU, 2: two tiles per CU, 3: wide tiles (64 trajectories, one per CU), 4: one tile per CU, matrix-core chains
-  if (!use_quad_backward(h) || h->aos || (h->flags & ILQR_FLAG_UNFUSED) || h->route.unfused) return 0;
-  const bool staged = (h->flags & ILQR_FLAG_STAGED) || h->route.staged;
-  const bool wide_ok = !staged && h->nu <= 2 && h->sp.fixes == 0;  // wide tiles (kernels_wide.hpp, kernels_wide2.hpp): persistent route, m <= 2, no opt-in fixes
-  const int one_per_cu = (wide_ok && h->nu == 1 && !h->route.quad_chain) ? 4 : 1;  // k_solve_hex (backward_hex.hpp): the wide tiles' conditions and m = 1
-  if (h->route.fused) return (h->route.fused == 3 && !wide_ok) ? 2 : (h->route.fused == 1 ? one_per_cu : h->route.fused);
-  if (h->ntiles <= h->num_cus) return one_per_cu;
-  // beyond two 16-trajectory tiles per CU: 64-trajectory wide tiles, the thread-per-trajectory chain (one per CU up to 64 #CU
-  // trajectories -- a third tile per CU would be a second round of the two-per-CU kernel: 1.49 against 1.16-1.27 ms at
-  // B = 8448 .. 14336 --, two per CU beyond)
-  if (wide_ok && h->ntiles > 2 * h->num_cus) return 3;
-  if (!staged) return 2;  // persistent tiles, two per CU, for ANY larger batch: the dispatcher hands a CU its next tile when one is through
-  return (h->ntiles <= 2 * h->num_cus) ? 2 : 0;
-}
-static bool use_fused_sweep(const ilqr_batch* h) { return fused_variant(h) != 0; }
 constexpr int kRingKbTwoBlocks = 60;
-template <class V, class M, class MFD>
-static void launch_sweep_backward_t(ilqr_batch* h, const V& v, const M& m, const MFD& fdm, int variant, int mode, int force, const int* ci) {
-  if (variant == 2)
-    hipLaunchKernelGGL((k_sweep_backward<M, 1, kRingKbTwoBlocks, MFD>), dim3(h->ntiles), dim3(64 * 2), 0, h->stream, v, m, fdm, h->sp, mode, force, ci);
-  else
-    hipLaunchKernelGGL((k_sweep_backward<M, kProducers, ILQR_RING_KB, MFD>), dim3(h->ntiles), dim3(64 * (1 + kProducers)), 0, h->stream, v, m, fdm, h->sp, mode, force, ci);
-}
 static int launch_sweep_backward(ilqr_batch* h, int mode, int force) {
   std::pair<hipEvent_t, hipEvent_t> ev;
   if (int rc = timer_begin(h, ILQR_STAGE_BACKWARD, &ev)) return rc;
-  const int variant = fused_variant(h);
   const int* ci = h->commit_pending ? h->commit_idx : nullptr;
   if (int rc = with_model(h, [&](auto& v, auto& m, auto& fdm) {
-        if constexpr (std::decay_t<decltype(m)>::NX == 4) launch_sweep_backward_t(h, v, m, fdm, variant, mode, force, ci);
+        using MM = std::decay_t<decltype(m)>;
+        using MF = std::decay_t<decltype(fdm)>;
+        if constexpr (MM::NX == 4) {
+          if (h->plan.sweep == Sweep::one_producer)
+            hipLaunchKernelGGL((k_sweep_backward<MM, 1, kRingKbTwoBlocks, MF>), dim3(h->ntiles), dim3(64 * 2), 0, h->stream, v, m, fdm, h->sp, mode, force, ci);
+          else
+            hipLaunchKernelGGL((k_sweep_backward<MM, kProducers, ILQR_RING_KB, MF>), dim3(h->ntiles), dim3(64 * (1 + kProducers)), 0, h->stream, v, m, fdm, h->sp, mode, force, ci);
+        }
         return 0;
       }))
     return rc;
@@ -310,13 +271,7 @@ static int launch_accept(ilqr_batch* h) {
   return timer_end(h, ILQR_STAGE_ACCEPT, ev);
 }
 
-// Whole iterations per tile in one persistent kernel (k_solve_tile): the one-block-per-CU regime of the fused
-// kernel.  ILQR_FLAG_STAGED: per-stage launches instead (A/B runs, the bit-identity tests).
-static bool use_persistent(const ilqr_batch* h) {
-  if (h->aos || (h->flags & ILQR_FLAG_STAGED) || h->route.staged) return false;
-  return fused_variant(h) != 0;
-}
-static AlphaSet line_search_alphas();
+// Whole iterations per tile in one persistent kernel (plan.solve: k_solve_hex / _tile / _wide / _wide2).
 static int launch_solve_tiles(ilqr_batch* h, int n_iters) {
   std::pair<hipEvent_t, hipEvent_t> ev;
   HIPCHK(hipMemsetAsync(h->v.n_running, 0, sizeof(int), h->stream));
@@ -324,37 +279,34 @@ static int launch_solve_tiles(ilqr_batch* h, int n_iters) {
   const AlphaSet al = line_search_alphas();
   const int pending = h->commit_pending ? 1 : 0;
   long long* ticks = h->profile ? h->phase_ticks : nullptr;
-  const int occ = fused_variant(h);
+  const Solve solve = h->plan.solve;
   const int grid_tiles = (h->active_tiles > 0 && h->active_tiles < h->ntiles) ? h->active_tiles : h->ntiles;  // (the rest hold finished trajectories only)
   if (int rc = with_model(h, [&](auto& v, auto& m, auto& fdm) {
         using MM = std::decay_t<decltype(m)>;
         using MF = std::decay_t<decltype(fdm)>;
         if constexpr (MM::NX != 4) {
           return fail(ILQR_ERR_STATE, "persistent tiles are nx = 4 kernels");
-        } else
-        if (occ == 3) {
-          if constexpr (MM::NU == 1)
-          {
-            if (h->route.wide_occ == 1 || (h->route.wide_occ == 0 && (grid_tiles + 3) / 4 <= h->num_cus))
-              hipLaunchKernelGGL((k_solve_wide<MM, MF, 1>), dim3((grid_tiles + 3) / 4), dim3(512), 0, h->stream, v, m, fdm, al, h->sp, n_iters, h->sp.fixed_work, h->commit_idx, pending, ticks);
-            else
-              hipLaunchKernelGGL((k_solve_wide<MM, MF, 2>), dim3((grid_tiles + 3) / 4), dim3(256), 0, h->stream, v, m, fdm, al, h->sp, n_iters, h->sp.fixed_work, h->commit_idx, pending, ticks);
+        } else {
+#define ILQR_SOLVE(K, blocks, threads) hipLaunchKernelGGL(K, dim3(blocks), dim3(threads), 0, h->stream, v, m, fdm, al, h->sp, n_iters, h->sp.fixed_work, h->commit_idx, pending, ticks)
+          const int wide_blocks = (grid_tiles + 3) / 4;  // (wide tiles: one per CU while they fit, else two -- or as ILQR_ROUTE_WIDE_ONE/TWO_PER_CU says)
+          const bool wide_one = h->route.wide_occ == 1 || (h->route.wide_occ == 0 && wide_blocks <= h->num_cus);
+          switch (solve) {
+            case Solve::wide: if constexpr (MM::NU == 1) { if (wide_one) ILQR_SOLVE((k_solve_wide<MM, MF, 1>), wide_blocks, 512); else ILQR_SOLVE((k_solve_wide<MM, MF, 2>), wide_blocks, 256); } break;
+            case Solve::wide2: if constexpr (MM::NU == 2) ILQR_SOLVE((k_solve_wide2<MM, MF>), wide_blocks, 256); break;
+            case Solve::hex: if constexpr (MM::NU == 1) ILQR_SOLVE((k_solve_hex<MM, MF>), grid_tiles, 512); break;
+            case Solve::tile1: ILQR_SOLVE((k_solve_tile<MM, MF, 1>), grid_tiles, 256); break;
+            case Solve::tile2: ILQR_SOLVE((k_solve_tile<MM, MF, 2>), grid_tiles, 256); break;
+            case Solve::none: break;
           }
-          else if constexpr (MM::NU == 2)
-            hipLaunchKernelGGL((k_solve_wide2<MM, MF>), dim3((grid_tiles + 3) / 4), dim3(256), 0, h->stream, v, m, fdm, al, h->sp, n_iters, h->sp.fixed_work, h->commit_idx, pending, ticks);
-        } else if (occ == 4) {
-          if constexpr (MM::NU == 1)
-            hipLaunchKernelGGL((k_solve_hex<MM, MF>), dim3(grid_tiles), dim3(512), 0, h->stream, v, m, fdm, al, h->sp, n_iters, h->sp.fixed_work, h->commit_idx, pending, ticks);
-        } else if (occ == 1)
-          hipLaunchKernelGGL((k_solve_tile<MM, MF, 1>), dim3(grid_tiles), dim3(256), 0, h->stream, v, m, fdm, al, h->sp, n_iters, h->sp.fixed_work, h->commit_idx, pending, ticks);
-        else
-          hipLaunchKernelGGL((k_solve_tile<MM, MF, 2>), dim3(grid_tiles), dim3(256), 0, h->stream, v, m, fdm, al, h->sp, n_iters, h->sp.fixed_work, h->commit_idx, pending, ticks);
+#undef ILQR_SOLVE
+        }
         return 0;
       }))
     return rc;
   HIPCHK(hipGetLastError());
-  h->commit_pending = (occ != 4);   // the last iteration's accepts (flushed by the caller); k_solve_hex commits every iteration's itself
-  h->cands_grouped = (occ == 4) && kHexCandT;  // (what ilqr_get_candidate finds in the buffers)
+  h->commit_pending = (solve != Solve::hex);   // the last iteration's accepts (flushed by the caller); k_solve_hex commits every iteration's itself
+  if (h->cands != Cands::none)  // (what ilqr_get_candidate finds in the buffers)
+    h->cands = (solve == Solve::hex && kHexCandT) ? Cands::grouped : Cands::planes;
   h->recs = ilqr_batch::REC_STALE;
   return timer_end(h, ILQR_STAGE_SOLVE, ev);
 }
@@ -367,7 +319,7 @@ static AlphaSet line_search_alphas() {
 
 static int do_rollout_candidates(ilqr_batch* h, int mode) {
   if (int rc = launch_rollout(h, true, true, line_search_alphas(), NALPHA, h->v.cost_c, mode)) return rc;
-  h->cands_valid = true;
+  h->cands = Cands::planes;
   return 0;
 }
 

@@ -403,8 +403,6 @@ constexpr bool kUserTiled = kUserQuad || kUserSmall;   // has tiled kernels (tra
 constexpr bool kUserGeneric = !kUserQuad;              // has generic kernels (trajectory-contiguous layout, wavefront per trajectory)
 }  // namespace ilqr
 #define ILQR_HAVE_USER_MODEL 1
+#else
+namespace ilqr { constexpr bool kUserTiled = false, kUserSmall = false; }  // (no user twin in this build: ilqr_create's route inputs)
 #endif
-
-namespace ilqr {
-
-}  // namespace ilqr

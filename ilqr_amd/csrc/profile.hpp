@@ -65,17 +65,8 @@ int ilqr_profile_shader_clock(ilqr_batch* h, double* mhz_out) {
   return 0;
 }
 const char* ilqr_stage_kernel_name(ilqr_batch* h, int stage) {
-  switch (stage) {
-    case ILQR_STAGE_DERIVATIVES: return (h && h->aos) ? (h->lq_fused ? "" : (h->v.analytic && h->model == ILQR_MODEL_LQ && !h->lq_wide) ? "k_analytic_lq" : (h->model == ILQR_MODEL_LQ && !h->route.lq_dense_fd && !h->lq_wide) ? "k_derivatives_lq" : "k_derivatives_g") : "k_derivatives";
-    case ILQR_STAGE_BACKWARD:  // ("k_backward_w3w": k_backward_w3 with two control tiles, MT = 2)
-      if (h && h->aos) return h->route.two_control_tiles ? "k_backward_w3w" : h->route.backward_w2 ? "k_backward_w2" : "k_backward_w3";
-      if (h && use_fused_sweep(h)) return "k_sweep_backward";  // what ilqr_iterate launches
-      return (h && use_quad_backward(h)) ? "k_backward_q" : "k_backward_t";
-    case ILQR_STAGE_ROLLOUT: return (h && h->aos) ? ((h->route.lq_thread_rollout || h->model != ILQR_MODEL_LQ) ? "k_rollout_g" : "k_rollout_lq") : "k_rollout";
-    case ILQR_STAGE_ACCEPT: return "k_accept";
-    case ILQR_STAGE_SOLVE: return (h && use_persistent(h)) ? (fused_variant(h) == 1 ? "k_solve_tile" : fused_variant(h) == 3 ? (h->nu == 2 ? "k_solve_wide2" : "k_solve_wide") : fused_variant(h) == 4 ? "k_solve_hex" : "k_solve_tile<2>") : "";
-    default: return "";
-  }
+  static const RoutePlan kNoHandle{};
+  return stage_kernel_name(h ? h->plan : kNoHandle, stage);
 }
 
 }  // extern "C"

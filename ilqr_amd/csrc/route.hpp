@@ -1,0 +1,101 @@
+// route.hpp -- which of several equivalent kernels a handle runs, decided once at ilqr_create, and the names
+// ilqr_stage_kernel_name reports for it.  Host code only: tests/test_route_plan.py builds it with a host compiler.
+#pragma once
+#include "../../include/ilqr_amd.h"
+
+namespace ilqr {
+
+// ilqr_iterate's persistent kernel (nx = 4, no ILQR_FLAG_STAGED / _UNFUSED): up to one tile per CU k_solve_hex (m = 1, no opt-in fixes:
+// four matrix-core chains) or k_solve_tile<.., 1>; beyond two per CU, m <= 2, no opt-in fixes, 64-trajectory wide tiles; otherwise two
+// 16-trajectory tiles per CU, k_solve_tile<.., 2>.  ILQR_ROUTE_TILE_PER_CU / TWO_TILES_PER_CU / WIDE_TILES force one (A/B runs, tests).
+enum class Solve { none, hex, tile1, tile2, wide, wide2 };
+// ILQR_FLAG_STAGED: k_sweep_backward (records in LDS, three producers; one on a 60 KB ring at two tiles per CU), beyond that stage kernels
+enum class Sweep { none, three_producers, one_producer };
+// fused_lq: no sweep, k_backward_w3<.., LQF> forms cx, cu from the knot; lq: k_derivatives_lq + k_derivatives_g for knot T
+enum class Derivatives { tiled, analytic_lq, lq, generic, fused_lq };
+// w3_regv: ILQR_FLAG_REGULARIZE_VXX's bounds-checked k_backward_w3; w3_two_tiles: two 16-column control tiles (nu > 16 or by route bit)
+enum class Backward { quad, thread, w3, w3_regv, w3_two_tiles, w2 };
+// tiled: k_rollout accepts per tile; lq_accept: k_rollout_lq accepts and keeps its candidates; lq, generic: k_accept after the search
+enum class Rollout { tiled, lq_accept, lq, generic };
+// k_commit from the alpha planes, k_commit_lq from the LQ search's kept rollouts, or the accepted rollout run again in place
+enum class Commit { tiled, lq_copy, rerun };
+
+struct RoutePlan {  // (the defaults: what ilqr_stage_kernel_name reports for a null handle)
+  Solve solve = Solve::none;
+  Sweep sweep = Sweep::none;
+  Derivatives derivatives = Derivatives::tiled;
+  Backward backward = Backward::thread;
+  Rollout rollout = Rollout::tiled;
+  Commit commit = Commit::tiled;
+};
+
+struct RouteInputs {
+  int model, nx, nu, flags, route, ntiles, num_cus;  // (num_cus after ilqr_desc.assume_cus)
+  bool user_tiled, user_small;  // the build's user twin: kUserTiled, kUserSmall (models.hpp)
+  bool cands_allocated;         // the LQ search's candidate buffers (not under ILQR_ROUTE_LQ_RECOMMIT, nor if the device could not spare them)
+};
+
+// trajectory-contiguous layout, generic kernels: host-evaluated models, the LQ model, user twins without tiled kernels or sent there
+inline bool generic_layout(int model, int route, bool user_tiled, bool user_small) {
+  if (model == ILQR_MODEL_LQ || model == ILQR_MODEL_HOST) return true;
+  return model == ILQR_MODEL_USER && (!user_tiled || (user_small && (route & ILQR_ROUTE_WAVE_PER_TRAJECTORY)));
+}
+// the LQ model's line search on the matrix cores (k_rollout_lq is written for 32 x 16): what candidate buffers are allocated for
+inline bool lq_matrix_core_search(int model, int nu, int route) {
+  return model == ILQR_MODEL_LQ && nu <= 16 && !(route & ILQR_ROUTE_LQ_THREAD_ROLLOUT);
+}
+
+inline RoutePlan plan_route(const RouteInputs& in) {
+  RoutePlan p;
+  const int fl = in.flags, rt = in.route;
+  if (generic_layout(in.model, rt, in.user_tiled, in.user_small)) {
+    const bool lq = in.model == ILQR_MODEL_LQ, lq_wide = lq && in.nu > 16;
+    p.backward = (in.nu > 16 || (rt & ILQR_ROUTE_TWO_CONTROL_TILES)) ? Backward::w3_two_tiles : (rt & ILQR_ROUTE_BACKWARD_W2) ? Backward::w2
+                 : (fl & ILQR_FLAG_REGULARIZE_VXX) ? Backward::w3_regv : Backward::w3;
+    const bool analytic = (fl & ILQR_FLAG_ANALYTIC_DERIVATIVES) != 0;
+    if (lq && analytic && !(rt & ILQR_ROUTE_FULL_RECORDS) && p.backward == Backward::w3) p.derivatives = Derivatives::fused_lq;
+    else if (lq && analytic && !lq_wide) p.derivatives = Derivatives::analytic_lq;
+    else if (lq && !(rt & ILQR_ROUTE_LQ_DENSE_FD) && !lq_wide) p.derivatives = Derivatives::lq;
+    else p.derivatives = Derivatives::generic;
+    p.rollout = !lq_matrix_core_search(in.model, in.nu, rt) ? Rollout::generic : in.cands_allocated ? Rollout::lq_accept : Rollout::lq;
+    p.commit = p.rollout == Rollout::lq_accept ? Commit::lq_copy : Commit::rerun;
+    return p;
+  }
+  const bool quad = in.nx == 4 && !(fl & ILQR_FLAG_BACKWARD_THREAD_PER_TRAJ);
+  p.backward = quad ? Backward::quad : Backward::thread;
+  if (!quad || (fl & ILQR_FLAG_UNFUSED)) return p;
+  const bool staged = (fl & ILQR_FLAG_STAGED) != 0;
+  const bool wide_ok = !staged && in.nu <= 2 && !(fl & (ILQR_FLAG_REFERENCE_FIXES | ILQR_FLAG_REGULARIZE_VXX));
+  const Solve one_per_cu = (wide_ok && in.nu == 1 && !(rt & ILQR_ROUTE_QUAD_CHAIN)) ? Solve::hex : Solve::tile1;
+  const Solve wide = in.nu == 1 ? Solve::wide : Solve::wide2;
+  Solve s;
+  switch (rt & 3) {
+    case ILQR_ROUTE_TILE_PER_CU: s = one_per_cu; break;
+    case ILQR_ROUTE_TWO_TILES_PER_CU: s = Solve::tile2; break;
+    case ILQR_ROUTE_WIDE_TILES: s = wide_ok ? wide : Solve::tile2; break;
+    default:  // by batch size: a third 16-trajectory tile per CU would be a second round of tile2 (1.49 against 1.16-1.27 ms at B = 8448 .. 14336)
+      s = in.ntiles <= in.num_cus ? one_per_cu : (wide_ok && in.ntiles > 2 * in.num_cus) ? wide
+          : (!staged || in.ntiles <= 2 * in.num_cus) ? Solve::tile2 : Solve::none;
+  }
+  if (!staged) p.solve = s;
+  else if (s != Solve::none) p.sweep = s == Solve::tile2 ? Sweep::one_producer : Sweep::three_producers;
+  return p;
+}
+
+// as rocprofv3 reports it; persistent and fused-sweep handles report k_sweep_backward for the backward stage (what ilqr_iterate runs)
+inline const char* stage_kernel_name(const RoutePlan& p, int stage) {
+  static const char* const kSolve[] = {"", "k_solve_hex", "k_solve_tile", "k_solve_tile<2>", "k_solve_wide", "k_solve_wide2"};
+  static const char* const kDerivatives[] = {"k_derivatives", "k_analytic_lq", "k_derivatives_lq", "k_derivatives_g", ""};
+  static const char* const kBackward[] = {"k_backward_q", "k_backward_t", "k_backward_w3", "k_backward_w3", "k_backward_w3w", "k_backward_w2"};
+  static const char* const kRollout[] = {"k_rollout", "k_rollout_lq", "k_rollout_lq", "k_rollout_g"};
+  switch (stage) {
+    case ILQR_STAGE_DERIVATIVES: return kDerivatives[(int)p.derivatives];
+    case ILQR_STAGE_BACKWARD: return (p.solve != Solve::none || p.sweep != Sweep::none) ? "k_sweep_backward" : kBackward[(int)p.backward];
+    case ILQR_STAGE_ROLLOUT: return kRollout[(int)p.rollout];
+    case ILQR_STAGE_ACCEPT: return "k_accept";
+    case ILQR_STAGE_SOLVE: return kSolve[(int)p.solve];
+    default: return "";
+  }
+}
+
+}  // namespace ilqr

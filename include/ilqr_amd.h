@@ -353,7 +353,8 @@ int ilqr_profile_read(ilqr_batch* h, double ms_out[ILQR_NUM_STAGES], int launche
  * over constant-rate ticks, summed over tiles.  MI355X lowers its clock with the number of busy SIMDs, so issue-rate
  * figures derived from a launch duration need the clock of THAT launch (bench.py: roofline_issue). */
 int ilqr_profile_shader_clock(ilqr_batch* h, double* mhz_out);
-/* name of the kernel a stage launches (as rocprofv3 reports it), for bench.py's roofline line */
+/* name of the kernel a stage launches (as rocprofv3 reports it), for bench.py's roofline line: looked up from the route plan the handle
+ * fixed at ilqr_create, the one its launchers switch on */
 const char* ilqr_stage_kernel_name(ilqr_batch* h, int stage);
 
 #ifdef __cplusplus

@@ -139,7 +139,7 @@ def test_nx4_routes_equal_the_two_kernel_route(model, limits, dtype):
     sv = capi.STAGE_NAMES.index("solve")
     for fixes in (False, True):
         base = capi.FLAG_REFERENCE_FIXES if fixes else 0
-        # (with the fixes the persistent route is the 16-trajectory tile, k_solve_tile: launch.hpp fused_variant)
+        # (with the fixes the persistent route is the 16-trajectory tile, k_solve_tile: route.hpp plan_route)
         routes = nx4_routes(model) if not fixes else [("unfused", capi.FLAG_UNFUSED, 0, None), ("default", 0, 0, b"k_solve_tile"),
                                                       ("staged", capi.FLAG_STAGED, 0, b"")]
         out = []
