@@ -384,11 +384,16 @@ static_assert(sizeof(Wave3WLds<2>) <= 40 * 1024, "one wavefront on every SIMD: 4
 #ifndef ILQR_W3_NT2_WAVES
 #define ILQR_W3_NT2_WAVES 2
 #endif
-template <int NT, bool FULL, bool LQF, bool REGV = false, int MT = 1>
-__global__ __launch_bounds__(64, MT == 2 ? 1 : NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES) void k_backward_w3(BatchView v, int n, int m, const double* __restrict__ u_min,
+template <int NT, bool FULL, bool LQF, bool REGV = false, int MT = 1, class S = double>
+__global__ __launch_bounds__(64, MT == 2 ? 1 : NT == 2 ? ILQR_W3_NT2_WAVES : ILQR_W3_NT1_WAVES) void k_backward_w3(BatchViewT<S> v, int n, int m, const double* __restrict__ u_min,
                                                                     const double* __restrict__ u_max, SolverParams sp, int mode,
                                                                     const double* __restrict__ const_rec) {
   static_assert(MT == 1 || (MT == 2 && !FULL && !LQF && !REGV), "two control tiles: whole records, the bounds-checked step");
+  static_assert(MT == 1 || std::is_same<S, double>::value, "two control tiles: fp64 only");
+  // S = float (fp32 handles): knots, gains and records are stored as float -- widened where they are loaded (ldm and the vector loads
+  // below), the gains rounded where they are stored; every operation between is the fp64 instantiation's.  The records the LQF route
+  // takes from const_rec are double on both.  fp32 handles pass const_rec on the LQF route only.
+  using RT = std::conditional_t<LQF, double, S>;  // what the record pointers point at
   using Lds = std::conditional_t<MT == 1, Wave2Lds<NT>, Wave3WLds<NT>>;
   __shared__ Lds L;
   constexpr int N = 16 * NT;
@@ -407,11 +412,12 @@ __global__ __launch_bounds__(64, MT == 2 ? 1 : NT == 2 ? ILQR_W3_NT2_WAVES : ILQ
   const int REC = 2 * n * n + 2 * n * m + n + m + m * m;
   const int oFX = 0, oFU = oFX + n * n, oCX = oFU + n * m, oCXX = oCX + n, oCXU = oCXX + n * n, oCU = oCXU + n * m,
             oCUU = oCU + m;
-  const double* __restrict__ Db = LQF ? const_rec : v.D + (size_t)b * (T + 1) * REC;
-  const double* __restrict__ xsb = v.xs + (size_t)b * (T + 1) * n;
-  const double* __restrict__ usb = v.us + (size_t)b * T * m;
-  double* __restrict__ kb = v.kff + (size_t)b * T * m;
-  double* __restrict__ Kb = v.Kfb + (size_t)b * T * m * n;
+  const RT* __restrict__ Db;
+  if constexpr (LQF) Db = const_rec; else Db = v.D + (size_t)b * (T + 1) * REC;
+  const S* __restrict__ xsb = v.xs + (size_t)b * (T + 1) * n;
+  const S* __restrict__ usb = v.us + (size_t)b * T * m;
+  S* __restrict__ kb = v.kff + (size_t)b * T * m;
+  S* __restrict__ Kb = v.Kfb + (size_t)b * T * m * n;
   double lambda = v.lambda[b], dlambda = v.dlambda[b];
   const int g = lane >> 4, p = lane & 15;
   {
@@ -431,8 +437,8 @@ __global__ __launch_bounds__(64, MT == 2 ? 1 : NT == 2 ? ILQR_W3_NT2_WAVES : ILQ
   unsigned lb_nn = (unsigned)(g + n * p);
   unsigned lb_tn = (unsigned)(p + n * g);
   unsigned lb_mm = (unsigned)(g + m * p);
-  auto ldm = [](const double* r, bool in, unsigned off) __attribute__((always_inline)) {
-    if (FULL) return r[off];
+  auto ldm = [](const RT* r, bool in, unsigned off) __attribute__((always_inline)) {
+    if (FULL) return (double)r[off];
     const double val = r[in ? off : 0u];
     return in ? val : 0.0;
   };
@@ -456,7 +462,7 @@ __global__ __launch_bounds__(64, MT == 2 ? 1 : NT == 2 ? ILQR_W3_NT2_WAVES : ILQ
   while (true) {
     double Vxx[NT][NT][4];
     {  // :353-354
-      const double* r = LQF ? const_rec + REC : Db + (size_t)T * REC;
+      const RT* r = LQF ? Db + REC : Db + (size_t)T * REC;
 #pragma unroll
       for (int ti = 0; ti < NT; ti++)
 #pragma unroll
@@ -491,8 +497,9 @@ __global__ __launch_bounds__(64, MT == 2 ? 1 : NT == 2 ? ILQR_W3_NT2_WAVES : ILQ
     lds_sync();
     for (int i = T - 1; i >= 0; i--) {
       ILQR_W2MARK(7)
-      const double* rk = LQF ? const_rec : Db + (size_t)i * REC;        // this knot's record (cx, cu, and the matrices unless const_rec has them)
-      const double* rm = (LQF || const_rec) ? const_rec : rk;           // ... its matrix blocks
+      const RT* rk = LQF ? Db : Db + (size_t)i * REC;                   // this knot's record (cx, cu, and the matrices unless const_rec has them)
+      const RT* rm;                                                     // ... its matrix blocks
+      if constexpr (std::is_same<RT, double>::value) rm = (LQF || const_rec) ? const_rec : rk; else rm = rk;
       double fx[NT][NT][4], fu[NT][MT][4];
       double kx = 0, ku = 0;  // non-LQF: cx on lanes < n, cu on lanes N .. N + m - 1
       {
@@ -939,7 +946,7 @@ __global__ __launch_bounds__(64, MT == 2 ? 1 : NT == 2 ? ILQR_W3_NT2_WAVES : ILQ
   double acc = 0;
   for (int t = 0; t < T; t++) {
     double val = -1.0;
-    if (lane < m) val = fabs(kb[(size_t)t * m + lane]) / (fabs(usb[(size_t)t * m + lane]) + 1);
+    if (lane < m) val = fabs((double)kb[(size_t)t * m + lane]) / (fabs((double)usb[(size_t)t * m + lane]) + 1);
 #pragma unroll
     for (int off = W / 2; off >= 1; off >>= 1) val = fmax(val, __shfl_xor(val, off, 64));
     acc += __shfl(val, 0, 64);

@@ -122,8 +122,14 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
     return fail(ILQR_ERR_UNSUPPORTED, "ILQR_ROUTE_TWO_CONTROL_TILES and ILQR_ROUTE_BACKWARD_W2 name two different backward kernels");
   if ((d->route & ILQR_ROUTE_TWO_CONTROL_TILES) && (d->flags & ILQR_FLAG_REGULARIZE_VXX))
     return fail(ILQR_ERR_UNSUPPORTED, "ILQR_FLAG_REGULARIZE_VXX is implemented in k_backward_w3 (at most 16 controls): drop ILQR_ROUTE_TWO_CONTROL_TILES");
-  if (d->dtype == ILQR_DTYPE_F32 && d->model != ILQR_MODEL_ACROBOT && d->model != ILQR_MODEL_DOUBLE_INTEGRATOR && d->model != ILQR_MODEL_USER)
-    return fail(ILQR_ERR_UNSUPPORTED, "fp32 is available for the nx = 4 device models (acrobot, double integrator); the generic nx <= 32 path is fp64");
+  if (d->dtype == ILQR_DTYPE_F32 && h->aos) {  // fp32 on the generic path: the device models, k_backward_w3 with one control tile
+    if (d->model == ILQR_MODEL_HOST)
+      return fail(ILQR_ERR_UNSUPPORTED, "fp32 is not available for ILQR_MODEL_HOST: the caller evaluates the model and owns its records (fp64)");
+    if (d->route & ILQR_ROUTE_BACKWARD_W2)
+      return fail(ILQR_ERR_UNSUPPORTED, "fp32 is not available on ILQR_ROUTE_BACKWARD_W2 (the literal-order fp64 cross-check): fp32 handles run k_backward_w3");
+    if (d->route & ILQR_ROUTE_TWO_CONTROL_TILES)
+      return fail(ILQR_ERR_UNSUPPORTED, "fp32 is not available on ILQR_ROUTE_TWO_CONTROL_TILES: fp32 handles run k_backward_w3 with one control tile");
+  }
   h->nx = d->nx;
   h->nu = d->nu;
   h->T = d->T;
@@ -175,7 +181,8 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
     REQUIRE(d->u_min && d->u_max, "ILQR_MODEL_USER needs u_min/u_max (Model::u_min/u_max, include/model.h:17)");
     REQUIRE(!(d->flags & ILQR_FLAG_ANALYTIC_DERIVATIVES) || has_analytic_record<UM>::value, "this user model has no analytic_record()");
     // not a tiled shape -- or a small one asked to take the generic route: the generic kernels (fp64), trajectory-contiguous layout like the LQ model's
-    if (h->aos) REQUIRE(d->dtype == ILQR_DTYPE_F64, "the generic nx <= 32 path is fp64");
+    // (a small twin asked onto the generic kernels -- ILQR_ROUTE_WAVE_PER_TRAJECTORY -- is the fp64 cross-check of its tiled kernels)
+    if (h->aos && kUserSmall) REQUIRE(d->dtype == ILQR_DTYPE_F64, "ILQR_ROUTE_WAVE_PER_TRAJECTORY on a small twin is the fp64 cross-check of its tiled kernels: fp64 only");
     REQUIRE(d->n_user_params >= 0 && (d->n_user_params == 0 || d->user_params), "ILQR_MODEL_USER: n_user_params = %d with user_params = %p", d->n_user_params, (const void*)d->user_params);
     h->user_f.set_params(d->user_params, d->n_user_params);
     if (h->dtype == ILQR_DTYPE_F32) {  // the twin the finite differences are taken in: built from the parameters' FLOAT values, like the shipped models'
@@ -193,6 +200,7 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
       h->user.u_max[j] = (h->dtype == ILQR_DTYPE_F32) ? (double)h->user_f.u_max[j] : d->u_max[j];
     }
     static_cast<UM&>(h->user_g) = h->user;  // the generic kernels' copy: parameters AND limits (a model's cost may read its own u_min / u_max)
+    static_cast<UserModelT<float>&>(h->user_gf) = h->user_f;  // ... and on an fp32 handle the float twin its rollouts integrate
 #endif
   } else if (d->model == ILQR_MODEL_HOST || d->model == ILQR_MODEL_LQ) {
     // Generic dimensions: trajectory-contiguous layout, one wavefront per trajectory in the backward
@@ -218,18 +226,19 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
   if (h->aos) {
     const size_t Bn = h->B;
     v.nch = 0;
-    rc |= dev_alloc(h, &v.x0, Bn * nx);
-    rc |= dev_alloc(h, &v.xs, Bn * T1 * nx);
-    rc |= dev_alloc(h, &v.us, Bn * T * nu);
-    rc |= dev_alloc(h, &v.kff, Bn * T * nu);
-    rc |= dev_alloc(h, &v.Kfb, Bn * T * nu * nx);
+    rc |= dev_alloc_real(h, &v.x0, Bn * nx);  // (fp32 handles: float arrays)
+    rc |= dev_alloc_real(h, &v.xs, Bn * T1 * nx);
+    rc |= dev_alloc_real(h, &v.us, Bn * T * nu);
+    rc |= dev_alloc_real(h, &v.kff, Bn * T * nu);
+    rc |= dev_alloc_real(h, &v.Kfb, Bn * T * nu * nx);
     v.D = nullptr;  // on first use (ensure_records): the fused LQ route never needs it
-    rc |= dev_alloc(h, &h->const_rec, 2 * REC);
+    // (double on every handle; GN zeros behind the two records: the knot k_analytic_lq forms knot T's unused cx from at creation)
+    rc |= dev_alloc(h, &h->const_rec, 2 * REC + GN);
     rc |= dev_alloc(h, &h->d_umin, nu);
     rc |= dev_alloc(h, &h->d_umax, nu);
     v.cand_u = nullptr;
     v.cand_x = nullptr;
-    if (lq_matrix_core_search(d->model, d->nu, d->route) && !(d->route & ILQR_ROUTE_LQ_RECOMMIT)) {
+    if (lq_matrix_core_search(d->model, d->nu, d->route) && !(d->route & ILQR_ROUTE_LQ_RECOMMIT) && d->dtype == ILQR_DTYPE_F64) {
       // the eleven rollouts of the matrix-core search, whole ([b][alpha][t][row]): the commit is then a copy, not a twelfth rollout
       // (11 x the nominal trajectory, ~7 GB at configs[4]: if the device cannot spare them the handle works without -- the ILQR_ROUTE_LQ_RECOMMIT route)
       void *cx = nullptr, *cu = nullptr;
@@ -263,11 +272,32 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
         }
         for (size_t i = 0; i < nu; i++)
           for (size_t j = 0; j < nu; j++) pR[i * GMC + j] = d->lq_R[i * nu + j];
+        // fp32 handle: the float matrices its rollouts integrate, and their values in the double twin (finite differences, exact
+        // derivatives, backward pass), as create_impl does for the other models' parameters
+        std::vector<float> hf;
+        float* padf = nullptr;
+        if (h->dtype == ILQR_DTYPE_F32) {
+          hf.resize(tot);
+          for (size_t e = 0; e < tot; e++) hp[e] = (double)(hf[e] = (float)hp[e]);
+          rc |= dev_alloc(h, &padf, tot);
+        }
         // on the handle's stream, behind dev_alloc's zero fill of the same buffer (a copy on the null
         // stream could be overtaken by it: the stream is non-blocking); hp must outlive the copy
         if (hipMemcpyAsync(pad, hp.data(), tot * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+            (padf && hipMemcpyAsync(padf, hf.data(), tot * sizeof(float), hipMemcpyHostToDevice, h->stream) != hipSuccess) ||
             hipStreamSynchronize(h->stream) != hipSuccess)
           rc = 1;
+        if (padf) {
+          h->lq_f.nx = (int)nx;
+          h->lq_f.nu = (int)nu;
+          h->lq_f.A = padf;
+          h->lq_f.Bm = padf + nA;
+          h->lq_f.Q = padf + nA + nB;
+          h->lq_f.R = padf + 2 * nA + nB;
+          h->lq_f.Qf = padf + 2 * nA + nB + nR;
+          h->lq_f.umin = h->d_umin;
+          h->lq_f.umax = h->d_umax;
+        }
         h->lq.nx = (int)nx;
         h->lq.nu = (int)nu;
         h->lq.A = pad;
@@ -289,8 +319,14 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
       }
     }
     if (!rc) {
-      if (hipMemcpyAsync(h->d_umin, d->u_min, nu * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = 1;
-      if (hipMemcpyAsync(h->d_umax, d->u_max, nu * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = 1;
+      // fp32 handle: the limits' float values (the float rollouts clamp to them, the double backward pass boxes with them)
+      std::vector<double> lim(d->u_min, d->u_min + nu);
+      lim.insert(lim.end(), d->u_max, d->u_max + nu);
+      if (h->dtype == ILQR_DTYPE_F32)
+        for (double& q : lim) q = (double)(float)q;
+      if (hipMemcpyAsync(h->d_umin, lim.data(), nu * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = 1;
+      if (hipMemcpyAsync(h->d_umax, lim.data() + nu, nu * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = 1;
+      if (hipStreamSynchronize(h->stream) != hipSuccess) rc = 1;  // (lim must outlive the copies)
     }
   } else {
   rc |= dev_alloc_real(h, &v.x0, nt * nx * TW);
@@ -326,7 +362,7 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
   if (!rc && hipMemsetAsync(h->commit_idx, 0xFF, Bp * sizeof(int), h->stream) != hipSuccess) rc = 1;
   if (rc) return ILQR_ERR_HIP;
   sync_float_view(h);
-  h->plan = plan_route({d->model, d->nx, d->nu, d->flags, d->route, h->ntiles, h->num_cus, kUserTiled, kUserSmall, v.cand_x != nullptr});
+  h->plan = plan_route({d->model, d->nx, d->nu, d->flags, d->route, h->ntiles, h->num_cus, kUserTiled, kUserSmall, v.cand_x != nullptr, d->dtype});
 
   h->sp.max_iter = h->params.max_iter;
   h->sp.tol_fun = h->params.tol_fun;
@@ -347,8 +383,10 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
   hipLaunchKernelGGL(k_reset_state<double>, dim3((h->Bp + 255) / 256), dim3(256), 0, h->stream, h->v, h->params.lambda_init,
                      h->params.dlambda_init);
   HIPCHK(hipGetLastError());
-  if (h->plan.derivatives == Derivatives::fused_lq) {  // both constant records, once (what = 3)
-    hipLaunchKernelGGL(k_analytic_lq, dim3(1), dim3(64), 0, h->stream, h->v, h->lq, 1, 3, h->const_rec, kAnalyticChunk);
+  if (h->plan.derivatives == Derivatives::fused_lq) {  // both constant records, once (what = 3), in double on every handle
+    BatchView cv = h->v;
+    if (h->dtype == ILQR_DTYPE_F32) cv.xs = h->const_rec + 2 * REC;  // (an fp32 handle's xs holds floats: the zero knot behind the records)
+    hipLaunchKernelGGL(k_analytic_lq<double>, dim3(1), dim3(64), 0, h->stream, cv, h->lq, 1, 3, h->const_rec, kAnalyticChunk);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -882,6 +920,11 @@ int ilqr_copy_cost_to_device(ilqr_batch* h, void* dst) {
 // the handle's (tiled, possibly float) array -> canonical double [B][S][E] in device memory `dst`; enqueued, not waited for
 static int unpack_to_device(ilqr_batch* h, const void* src, double* dst, int S, int E) {
   const size_t n = (size_t)h->B * S * E;
+  if (h->aos && h->dtype == ILQR_DTYPE_F32) {  // generic fp32 handles: the canonical layout, widened
+    hipLaunchKernelGGL((k_convert<float, double>), dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const float*)src, dst, n);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
   if (h->aos) {  // generic handles: the canonical layout IS the device layout
     HIPCHK(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return 0;
@@ -912,10 +955,11 @@ int ilqr_get_results_async(ilqr_batch* h, double* xs, double* us, double* k, dou
   HIPCHK(hipSetDevice(h->device));
   struct Item { const void* src; double* dst; int S, E; };
   const Item items[4] = {{h->v.xs, xs, h->T + 1, h->nx}, {h->v.us, us, h->T, h->nu}, {h->v.kff, k, h->T, h->nu}, {h->v.Kfb, K, h->T, h->nu * h->nx}};
-  if (h->aos) {
+  if (h->aos && h->dtype == ILQR_DTYPE_F64) {
     for (const Item& it : items)
       if (it.dst) HIPCHK(hipMemcpyAsync(it.dst, it.src, (size_t)h->B * it.S * it.E * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   } else {
+    // (tiled handles and generic fp32 handles: widened or unpacked into the staging buffer first)
     // every array gets its own stretch of the staging buffer: the unpack kernels and the copies follow each other on the stream without a
     // host synchronisation in between (the staging buffer is only ever touched by work enqueued on this stream: a later upload is ordered
     // behind these copies)

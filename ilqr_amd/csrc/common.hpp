@@ -137,6 +137,6 @@ struct BatchViewT {
   int* n_running;     // [1] device counter
   int analytic;       // ILQR_FLAG_ANALYTIC_DERIVATIVES: the models' exact derivatives instead of finite differences
 };
-using BatchView = BatchViewT<double>;  // (the generic nx <= 32 path, generic.hpp / backward_wave.hpp, is fp64 only)
+using BatchView = BatchViewT<double>;
 
 }  // namespace ilqr

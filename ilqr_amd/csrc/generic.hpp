@@ -31,21 +31,26 @@ typedef const __attribute__((address_space(4))) double cmem_d;
 // Synthetic LQ model: xdot = A x + B u, cost 0.5 (x'Qx + u'Ru), final cost 0.5 x'Qf x.  The
 // matrices are row-major and zero-padded to the maximum dimensions.  Sums run left to right
 // over the column index (the padding adds exact zeros at the end of every sum).
-struct LqModel {
-  using real = double;  // the generic path is fp64 only
+// Real = double: the fp64 handle's model, and the model an fp32 handle's finite differences, exact derivatives and backward pass are
+// taken in (built from the float-rounded matrices).  Real = float: what an fp32 handle's rollouts integrate (dynamics, cost,
+// final_cost and the limits only; the sweep's helpers below are double's).
+template <class Real>
+struct LqModelT {
+  using real = Real;
+  typedef const __attribute__((address_space(4))) Real cmem;
   static constexpr int NX = GN, NU = GM;
   int nx, nu;
-  const double *A, *Bm, *Q, *R, *Qf;  // device: [GN][GN], [GN][GM], [GN][GN], [GM][GM], [GN][GN]
+  const Real *A, *Bm, *Q, *R, *Qf;  // device: [GN][GN], [GN][GM], [GN][GN], [GM][GM], [GN][GN]
   const double *umin = nullptr, *umax = nullptr;  // device [nu]: Model::u_min / u_max (only the opt-in clamped rollout reads them)
-  __device__ __forceinline__ double limit_lo(int j) const { return umin[j]; }
-  __device__ __forceinline__ double limit_hi(int j) const { return umax[j]; }
+  __device__ __forceinline__ Real limit_lo(int j) const { return (Real)umin[j]; }
+  __device__ __forceinline__ Real limit_hi(int j) const { return (Real)umax[j]; }
 
-  __device__ __forceinline__ void dynamics(const double* x, const double* u, double* dx) const {
-    cmem_d* a = (cmem_d*)A;
-    cmem_d* bm = (cmem_d*)Bm;
+  __device__ __forceinline__ void dynamics(const Real* x, const Real* u, Real* dx) const {
+    cmem* a = (cmem*)A;
+    cmem* bm = (cmem*)Bm;
 #pragma unroll
     for (int i = 0; i < GN; i += 4) {  // four independent row sums in flight (see quad)
-      double acc[4] = {0, 0, 0, 0};
+      Real acc[4] = {0, 0, 0, 0};
 #pragma unroll
       for (int j = 0; j < GN; j++)
 #pragma unroll
@@ -59,14 +64,14 @@ struct LqModel {
     }
   }
   template <int N>
-  static __device__ __forceinline__ double quad(cmem_d* Mx, const double* vv) {
+  static __device__ __forceinline__ Real quad(cmem* Mx, const Real* vv) {
     // four rows at a time: the same sums in the same order, but four independent accumulator
     // chains in flight (one wavefront per SIMD has nothing else to hide the FMA latency)
     static_assert(N % 4 == 0, "row blocking");
-    double s = 0;
+    Real s = 0;
 #pragma unroll
     for (int i = 0; i < N; i += 4) {
-      double r0 = 0, r1 = 0, r2 = 0, r3 = 0;
+      Real r0 = 0, r1 = 0, r2 = 0, r3 = 0;
 #pragma unroll
       for (int j = 0; j < N; j++) {
         r0 += Mx[(i + 0) * N + j] * vv[j];
@@ -113,8 +118,8 @@ struct LqModel {
 #endif
   static constexpr bool kSeparableCost = ILQR_LQ_SEPARABLE != 0;
   static constexpr bool kHasAnalyticRecord = true;
-  __device__ __forceinline__ double cost_x(const double* x) const { return quad<GN>((cmem_d*)Q, x); }
-  __device__ __forceinline__ double cost_u(const double* u) const { return quad<GM>((cmem_d*)R, u); }
+  __device__ __forceinline__ Real cost_x(const Real* x) const { return quad<GN>((cmem*)Q, x); }
+  __device__ __forceinline__ Real cost_u(const Real* u) const { return quad<GM>((cmem*)R, u); }
   // P points at once: every matrix element is fetched once and used P times
   template <int N, int P>
   static __device__ __forceinline__ void quadP(cmem_d* Mx, const double (*vv)[N], double* sums) {
@@ -152,7 +157,7 @@ struct LqModel {
   __device__ __forceinline__ void cost_u2(const double* ua, const double* ub, double& qa, double& qb) const {
     quad2<GM>((cmem_d*)R, ua, ub, qa, qb);
   }
-  static __device__ __forceinline__ double cost_from_parts(double qx, double qu) { return 0.5 * (qx + qu); }
+  static __device__ __forceinline__ Real cost_from_parts(Real qx, Real qu) { return (Real)0.5 * (qx + qu); }
   // cost_x is a quadratic form x'Mx with this (zero-padded, row-major) matrix: the 2n(n+1) points of
   // the cxx sweep can then go through the matrix cores as one [32 x 32] x [32 x points] product
 #ifndef ILQR_LQ_MFMA_CXX
@@ -170,7 +175,7 @@ struct LqModel {
   __device__ __forceinline__ const double* dynamics_u_matrix() const { return Bm; }
   // cost_u is the quadratic form u'Mu with this matrix (the cuu sweep on the matrix cores)
   __device__ __forceinline__ const double* cost_u_matrix() const { return R; }
-  __device__ __forceinline__ double cost(const double* x, const double* u) const {
+  __device__ __forceinline__ Real cost(const Real* x, const Real* u) const {
     return cost_from_parts(cost_x(x), cost_u(u));
   }
   __device__ __forceinline__ void cost2(const double* xa, const double* ua, const double* xb, const double* ub, double& fa,
@@ -181,12 +186,13 @@ struct LqModel {
     fa = cost_from_parts(qa, ra);
     fb = cost_from_parts(qb, rb);
   }
-  __device__ __forceinline__ double final_cost(const double* x) const { return 0.5 * quad<GN>((cmem_d*)Qf, x); }
+  __device__ __forceinline__ Real final_cost(const Real* x) const { return (Real)0.5 * quad<GN>((cmem*)Qf, x); }
   // exact derivatives (opt-in), written cooperatively by the 64 lanes of the knot's wavefront into
   // the record D (runtime offsets for nx, nu; conventions of derivatives.cpp at t = T); x, u point
-  // to the knot in memory (u may be null at t = T)
-  __device__ __forceinline__ void analytic_record(const double* __restrict__ x, const double* __restrict__ u, double dt, bool last,
-                                                  double* __restrict__ D, int lane) const {
+  // to the knot in memory (u may be null at t = T).  fp32 handles: a float knot (widened) and a float record (rounded)
+  template <class SX, class SD>
+  __device__ __forceinline__ void analytic_record(const SX* __restrict__ x, const typename std::remove_cv<SX>::type* __restrict__ u, double dt, bool last,
+                                                  SD* __restrict__ D, int lane) const {
     const int oFX = 0, oFU = oFX + nx * nx, oCX = oFU + nx * nu, oCXX = oCX + nx, oCXU = oCXX + nx * nx, oCU = oCXU + nx * nu,
               oCUU = oCU + nu;
     const double* Wx = last ? Qf : Q;
@@ -217,6 +223,7 @@ struct LqModel {
     }
   }
 };
+using LqModel = LqModelT<double>;
 
 // The LQ twin with 16 < nu <= 32 (GMW = 32 columns of B, a 32 x 32 R): the same model, run by the generic kernels only --
 // thread-per-rollout k_rollout_g (the accepted rollout re-run to commit it), point-by-point finite differences k_derivatives_g, and
@@ -316,8 +323,8 @@ struct LqModelW {
 template <class U>
 struct GenericModelOf : U {
   int nx = U::NX, nu = U::NU;
-  __device__ __forceinline__ double limit_lo(int j) const { return this->u_min[j]; }
-  __device__ __forceinline__ double limit_hi(int j) const { return this->u_max[j]; }
+  __device__ __forceinline__ typename U::real limit_lo(int j) const { return this->u_min[j]; }
+  __device__ __forceinline__ typename U::real limit_hi(int j) const { return this->u_max[j]; }
   static constexpr bool kSeparableCost = false, kQuadraticCostX = false, kLinearDynamics = false, kHasAnalyticRecord = false;
   __device__ __forceinline__ void cost2(const double* xa, const double* ua, const double* xb, const double* ub, double& fa, double& fb) const {
     fa = this->cost(xa, ua);
@@ -328,9 +335,11 @@ struct GenericModelOf : U {
 enum { RG_INIT = 0, RG_SEARCH = 1, RG_COMMIT = 2 };
 constexpr int kSearchTraj = 64 / NALPHA;  // trajectories per wavefront in RG_SEARCH (5)
 
+// fp32 handles (M::real = float: LqModelT<float>, GenericModelOf<UserModelT<float>>): float knots and registers, the cost summed in double.
 template <class M, int MODE>
-__global__ __launch_bounds__(64) void k_rollout_g(BatchView v, M model, AlphaSet alphas, double* __restrict__ cost_out,
+__global__ __launch_bounds__(64) void k_rollout_g(BatchViewT<typename M::real> v, M model, AlphaSet alphas, double* __restrict__ cost_out,
                                                   const int* __restrict__ commit_idx, int mode, int write_cost, int fixes) {
+  using real = typename M::real;
   constexpr int NX = M::NX, NU = M::NU;
   const int nx = model.nx, nu = model.nu, T = v.T;
   const int lane = threadIdx.x;
@@ -349,34 +358,34 @@ __global__ __launch_bounds__(64) void k_rollout_g(BatchView v, M model, AlphaSet
     a = commit_idx[b];
     if (a < 0) return;
   }
-  double alpha = 0;
+  real alpha = 0;
 #pragma unroll
   for (int q = 0; q < NALPHA; q++)
-    if (a == q) alpha = alphas.a[q];
-  const double dt = v.dt;
+    if (a == q) alpha = (real)alphas.a[q];
+  const real dt = (real)v.dt;
 
-  double x[NX];
+  real x[NX];
 #pragma unroll
-  for (int i = 0; i < NX; i++) x[i] = (i < nx) ? v.x0[(size_t)b * nx + i] : 0.0;
+  for (int i = 0; i < NX; i++) x[i] = (i < nx) ? v.x0[(size_t)b * nx + i] : (real)0;
   double total = 0;
-  double* xsb = v.xs + (size_t)b * (T + 1) * nx;
-  double* usb = v.us + (size_t)b * T * nu;
-  const double* kb = v.kff + (size_t)b * T * nu;
-  const double* Kb = v.Kfb + (size_t)b * T * nu * nx;
+  real* xsb = v.xs + (size_t)b * (T + 1) * nx;
+  real* usb = v.us + (size_t)b * T * nu;
+  const real* kb = v.kff + (size_t)b * T * nu;
+  const real* Kb = v.Kfb + (size_t)b * T * nu * nx;
   for (int t = 0; t < T; t++) {
-    double u[NU];
+    real u[NU];
 #pragma unroll
-    for (int j = 0; j < NU; j++) u[j] = (j < nu) ? usb[(size_t)t * nu + j] : 0.0;
+    for (int j = 0; j < NU; j++) u[j] = (j < nu) ? usb[(size_t)t * nu + j] : (real)0;
     if (MODE != RG_INIT) {
-      double d[NX];
+      real d[NX];
 #pragma unroll
-      for (int i = 0; i < NX; i++) d[i] = (i < nx) ? x[i] - xsb[(size_t)t * nx + i] : 0.0;
-      const double* Kt = Kb + (size_t)t * nu * nx;
+      for (int i = 0; i < NX; i++) d[i] = (i < nx) ? x[i] - xsb[(size_t)t * nx + i] : (real)0;
+      const real* Kt = Kb + (size_t)t * nu * nx;
 #pragma unroll
       for (int j = 0; j < NU; j++) {
         if (j < nu) {
           u[j] += kb[(size_t)t * nu + j] * alpha;  // :190
-          double acc = 0;
+          real acc = 0;
 #pragma unroll
           for (int i = 0; i < NX; i++)
             if (i < nx) acc += Kt[j + nu * i] * d[i];
@@ -398,7 +407,7 @@ __global__ __launch_bounds__(64) void k_rollout_g(BatchView v, M model, AlphaSet
         if (j < nu) usb[(size_t)t * nu + j] = u[j];
     }
     total += model.cost(x, u);  // :324
-    double x1[NX];
+    real x1[NX];
     integrate_dynamics(model, x, u, dt, x1);  // :325
 #pragma unroll
     for (int i = 0; i < NX; i++) x[i] = x1[i];
@@ -429,7 +438,10 @@ constexpr int kAnalyticChunk = 8;
 // plus ONE copy of the constant matrices in const_rec, which k_backward_w then reads for every knot
 // t < T -- 77 KB + one record per trajectory instead of 5.4 MB; 2 = the constant matrices of every
 // knot t < T, unconditionally (fills in what 1 skipped, for the derivative getter).
-__global__ __launch_bounds__(64) void k_analytic_lq(BatchView v, LqModel model, int force, int what, double* __restrict__ const_rec,
+// S = float (fp32 handles): the float knot widened, the records rounded; what = 0 only.  const_rec stays double on both -- the
+// blocks of the double twin, written by k_analytic_lq<double> (what = 3) -- so k_backward_w3<.., LQF> does the fp64 handle's arithmetic.
+template <class S>
+__global__ __launch_bounds__(64) void k_analytic_lq(BatchViewT<S> v, LqModel model, int force, int what, double* __restrict__ const_rec,
                                                     int chunk) {
   static_assert(GN == 32 && GM == 16, "store mapping below is written for a 32 x 16 model");
   const int nx = model.nx, nu = model.nu, T = v.T;
@@ -462,6 +474,7 @@ __global__ __launch_bounds__(64) void k_analytic_lq(BatchView v, LqModel model, 
   // even nx: the same values as row PAIRS (rows 2 rp, 2 rp + 1 of column 4 j + cq), stored 16 bytes per
   // lane -- 1 KB per store instruction instead of 512 B (every offset of the record is even then)
   typedef double double2v __attribute__((ext_vector_type(2)));
+  typedef S S2v __attribute__((ext_vector_type(2)));
   const bool pairs = (nx & 1) == 0;
   const int rp = lane & 15;
   double2v fx2[8], cxx2[8], fu2[4];
@@ -490,7 +503,9 @@ __global__ __launch_bounds__(64) void k_analytic_lq(BatchView v, LqModel model, 
   // knot -1 stands for const_rec (matrices only)
   for (int t = fill_const ? -1 : t0; t < t0 + chunk && t <= T; t++) {
     if (t >= 0 && skip_knots) break;
-    double* __restrict__ D = (t < 0) ? const_rec : v.D + ((size_t)b * (T + 1) + t) * REC;
+    S* __restrict__ D;
+    if constexpr (std::is_same<S, double>::value) D = (t < 0) ? const_rec : v.D + ((size_t)b * (T + 1) + t) * REC;
+    else D = v.D + ((size_t)b * (T + 1) + t) * REC;  // (fp32: never t < 0, see above)
     const bool matrices = (t < 0) || what != 1, vectors = (t >= 0) && what != 2;
     if (t == T) {
       if (what != 2) model.analytic_record(v.xs + ((size_t)b * (T + 1) + t) * nx, nullptr, dt, true, D, lane);
@@ -501,8 +516,8 @@ __global__ __launch_bounds__(64) void k_analytic_lq(BatchView v, LqModel model, 
       // the knot arrives with ONE coalesced load per vector (lane j holds x_j / u_j) and is handed round with
       // v_readlane; 48 separate broadcast loads per knot made this the whole cost of the sweep once the
       // matrices were no longer stored per knot.  Padding terms are fma(0, 0, acc): the sums are unchanged.
-      const double* __restrict__ x = v.xs + ((size_t)b * (T + 1) + t) * nx;
-      const double* __restrict__ u = v.us + ((size_t)b * T + t) * nu;
+      const S* __restrict__ x = v.xs + ((size_t)b * (T + 1) + t) * nx;
+      const S* __restrict__ u = v.us + ((size_t)b * T + t) * nu;
       const double xv = (lane < nx) ? x[lane] : 0.0, uv = (lane < nu) ? u[lane] : 0.0;
       auto lane_value = [](double val, int l) {
         return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(val), l), __builtin_amdgcn_readlane(__double2loint(val), l));
@@ -521,16 +536,16 @@ __global__ __launch_bounds__(64) void k_analytic_lq(BatchView v, LqModel model, 
         for (int j = 0; j < 8; j++) {
           const int c = 4 * j + cq;
           if (c < nx) {
-            *reinterpret_cast<double2v*>(D + oFX + 2 * rp + nx * c) = fx2[j];
-            *reinterpret_cast<double2v*>(D + oCXX + 2 * rp + nx * c) = cxx2[j];
+            *reinterpret_cast<S2v*>(D + oFX + 2 * rp + nx * c) = __builtin_convertvector(fx2[j], S2v);
+            *reinterpret_cast<S2v*>(D + oCXX + 2 * rp + nx * c) = __builtin_convertvector(cxx2[j], S2v);
           }
         }
 #pragma unroll
         for (int j = 0; j < 4; j++) {
           const int c = 4 * j + cq;
           if (c < nu) {
-            *reinterpret_cast<double2v*>(D + oFU + 2 * rp + nx * c) = fu2[j];
-            *reinterpret_cast<double2v*>(D + oCXU + 2 * rp + nx * c) = double2v{0.0, 0.0};
+            *reinterpret_cast<S2v*>(D + oFU + 2 * rp + nx * c) = __builtin_convertvector(fu2[j], S2v);
+            *reinterpret_cast<S2v*>(D + oCXU + 2 * rp + nx * c) = S2v{0, 0};
           }
         }
       }
@@ -832,7 +847,7 @@ __global__ __launch_bounds__(256) void k_commit_lq(BatchView v, int nx, int nu, 
 //   cxu      (c(px,pu) - c(mx,pu) - c(px,mu) + c(mx,mu)) / 4eps^2               derivatives.cpp:114-144
 // including the t = T special cases (fx[T] = fu[T] = 0, cx/cxx from final_cost, cu[T] = 0, cuu[T]
 // from cost(x_T, 0), the cxu[T] formula the reference itself marks wrong).
-template <class M>
+template <class M, class S = double>
 // t_only >= 0: one block per trajectory, knot t_only alone (the last knot behind k_derivatives_lq, which sweeps the knots t < T).
 #ifndef ILQR_FD_G_WAVES_SMALL
 // Wavefronts per SIMD of k_derivatives_g: two at NX > 16 (186 registers for the LQ model's 32-vectors); THREE for a model of NX <= 16 (168
@@ -841,7 +856,8 @@ template <class M>
 // bytes of scratch, 18.7 ms).  Same instructions per lane: the same bits.
 #define ILQR_FD_G_WAVES_SMALL 3
 #endif
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((M::NX <= 16 ? ILQR_FD_G_WAVES_SMALL : 2), (M::NX <= 16 ? ILQR_FD_G_WAVES_SMALL : 2)))) void k_derivatives_g(BatchView v, M model, int force, int t_only) {
+// S = float (fp32 handles): the float knot widened, the model evaluated in double (M is the double twin), the record rounded.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((M::NX <= 16 ? ILQR_FD_G_WAVES_SMALL : 2), (M::NX <= 16 ? ILQR_FD_G_WAVES_SMALL : 2)))) void k_derivatives_g(BatchViewT<S> v, M model, int force, int t_only) {
   constexpr int NX = M::NX, NU = M::NU;
   const int nx = model.nx, nu = model.nu, T = v.T;
   const int lane = threadIdx.x;
@@ -850,7 +866,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((M::NX <= 16
   if (!(force || (v.status[b] == 0 && v.flg_change[b]))) return;
   const int oFX = 0, oFU = oFX + nx * nx, oCX = oFU + nx * nu, oCXX = oCX + nx, oCXU = oCXX + nx * nx, oCU = oCXU + nx * nu,
             oCUU = oCU + nu, REC = oCUU + nu * nu;
-  double* D = v.D + ((size_t)b * (T + 1) + t) * REC;
+  S* D = v.D + ((size_t)b * (T + 1) + t) * REC;
   const bool last = (t == T);
 
 #define ILQR_DMARK(k)
@@ -878,7 +894,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((M::NX <= 16
     // a user twin's own analytic_record (the contract of models.hpp: one thread writes the whole record, Rec<> order, column-major
     // blocks, derivatives.cpp's conventions at t = T) -- the record's offsets here are that order at nx = NX, nu = NU
     if (v.analytic) {
-      if (lane == 0) model.analytic_record(x, u, v.dt, last, D);
+      if constexpr (std::is_same<S, double>::value) {
+        if (lane == 0) model.analytic_record(x, u, v.dt, last, D);
+      } else {  // fp32 handle: the double record in LDS, rounded on the way out
+        __shared__ double rec[2 * NX * NX + 2 * NX * NU + NX + NU + NU * NU];
+        if (lane == 0) model.analytic_record(x, u, v.dt, last, rec);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // (one wavefront: orders its LDS accesses)
+        __builtin_amdgcn_wave_barrier();
+        for (int e = lane; e < REC; e += 64) D[e] = rec[e];
+      }
       return;
     }
   }
@@ -954,7 +978,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((M::NX <= 16
         for (int ks = 0; ks < 4; ks++)
 #pragma unroll
           for (int ti = 0; ti < 2; ti++) acc[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(opB[ti][ks], bu[ks], acc[ti], 0, 0, 0);
-        double* col = (var < nx) ? D + oFX + nx * var : D + oFU + nx * (var - nx);
+        S* col = (var < nx) ? D + oFX + nx * var : D + oFU + nx * (var - nx);
 #pragma unroll
         for (int ti = 0; ti < 2; ti++)
 #pragma unroll
@@ -975,7 +999,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((M::NX <= 16
       double px[NX], pu[NU], F[NX];
       perturbed(var < nx, valid ? (var < nx ? var : var - nx) : -1, d, true, -1, 0.0, px, pu);
       integrate_dynamics(model, px, pu, v.dt, F);
-      double* col = (var < nx) ? D + oFX + nx * var : D + oFU + nx * (var - nx);
+      S* col = (var < nx) ? D + oFX + nx * var : D + oFU + nx * (var - nx);
 #pragma unroll
       for (int r = 0; r < NX; r++) {
         const double fp = quad_bcast<0>(F[r]), fm = quad_bcast<1>(F[r]);      // lanes 4q, 4q+1
@@ -1333,7 +1357,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((M::NX <= 16
 // image from it and one column.  Three wavefronts per SIMD (12.5 KB of LDS, <= 168 registers).
 // Knot T (final_cost, the reference's conventions there) is k_derivatives_g's (t_only).  ILQR_ROUTE_LQ_DENSE_FD keeps the dense sweep for every knot (cross-check: tests/test_gpu_lq_end_to_end.py).
 constexpr int kLqKnotsPerWave = 8;
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_derivatives_lq(BatchView v, LqModel model, int force) {
+// S = float (fp32 handles): the float knot widened, the record rounded; everything between is double.
+template <class S>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_derivatives_lq(BatchViewT<S> v, LqModel model, int force) {
   static_assert(GN == 32 && GM == 16, "operand blocks below are written for a 32 x 16 model");
   typedef double double4_t __attribute__((ext_vector_type(4)));
   const int nx = model.nx, nu = model.nu, T = v.T;
@@ -1357,7 +1383,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
   //  the whole wavefront are what a third wavefront per SIMD needs)
 
   for (int t = t0; t < t0 + kLqKnotsPerWave && t < T; t++) {
-    double* __restrict__ D = v.D + ((size_t)b * (T + 1) + t) * REC;
+    S* __restrict__ D = v.D + ((size_t)b * (T + 1) + t) * REC;
     sync();  // (the previous knot's readers of xk .. su are through)
     {
       const double xv = (lane < nx) ? v.xs[((size_t)b * (T + 1) + t) * nx + lane] : 0.0;
@@ -1411,7 +1437,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         double cv[8];
 #pragma unroll
         for (int k = 0; k < 8; k++) cv[k] = colp[(16 * (k >> 2) + 4 * (k & 3) + g) * ld];
-        double* col = isx ? D + oFX + nx * idx : D + oFU + nx * idx;
+        S* col = isx ? D + oFX + nx * idx : D + oFU + nx * idx;
 #pragma unroll
         for (int k = 0; k < 8; k++) {
           const int row = 16 * (k >> 2) + 4 * (k & 3) + g;

@@ -37,7 +37,7 @@ enum class Cands { none, planes, grouped };  // what the candidate buffers hold 
 
 struct ilqr_batch {
   int model, nx, nu, T, B, Bp, ntiles, device, flags;
-  int dtype = ILQR_DTYPE_F64;   // arithmetic of the nx = 4 device models (ilqr_desc.dtype)
+  int dtype = ILQR_DTYPE_F64;   // storage and rollout arithmetic (ilqr_desc.dtype)
   double dt;
   ilqr_params params;
   // fp64 handle: its models.  fp32 handle: the double-precision TWINS the finite differences are taken in
@@ -46,13 +46,15 @@ struct ilqr_batch {
   DoubleIntegratorModel dint;
   AcrobotModelT<float> acrobot_f;          // fp32 handle: what the rollouts integrate
   DoubleIntegratorModelT<float> dint_f;
-  LqModel lq;                   // ILQR_MODEL_LQ: padded matrices on the device
+  LqModel lq;                   // ILQR_MODEL_LQ: padded matrices on the device (fp32 handle: the float-rounded matrices, for the finite differences and the backward pass)
+  LqModelT<float> lq_f;         // ... fp32 handle: the float matrices its rollouts integrate
   LqModelW lq_w;                // ... with 16 < nu <= 32 (lq_wide): B and R padded to 32 columns, the generic kernels only
   bool lq_wide = false;
 #ifdef ILQR_HAVE_USER_MODEL
   UserModelT<double> user;      // ILQR_MODEL_USER: the build's user device twin (fp32 handle: the twin the finite differences are taken in)
   GenericModelOf<UserModelT<double>> user_g;  // ... as the generic kernels take it (any NX <= 32, NU <= 16 that is not a tiled nx = 4 shape)
   UserModelT<float> user_f;
+  GenericModelOf<UserModelT<float>> user_gf;  // fp32 handle on the generic layout: what k_rollout_g integrates
 #endif
   // v is the view every entry point addresses arrays through; for an fp32 handle its trajectory pointers hold
   // the addresses of FLOAT arrays (never dereferenced as double: kernels get vf, the same addresses typed float*)
@@ -127,6 +129,12 @@ static void sync_float_view(ilqr_batch* h) {
   f.cost_c = v.cost_c; f.cost = v.cost; f.lambda = v.lambda; f.dlambda = v.dlambda; f.dV = v.dV; f.gnorm = v.gnorm;
   f.status = v.status; f.iters = v.iters; f.flg_change = v.flg_change; f.alpha_idx = v.alpha_idx; f.diverge = v.diverge;
   f.backpass_done = v.backpass_done; f.n_running = v.n_running; f.analytic = v.analytic;
+}
+// f(view) with the handle's view typed by its storage: h->v (double) or h->vf (float)
+template <class F>
+static int with_view(ilqr_batch* h, F&& f) {
+  if (h->dtype == ILQR_DTYPE_F32) return f(h->vf);
+  return f(h->v);
 }
 // f(view, model, model the finite differences are taken in) for the handle's device model and arithmetic
 template <class F>
@@ -258,6 +266,14 @@ static int ensure_staging(ilqr_batch* h, size_t elems) {
 // canonical host [B][S][E] -> tiled device  (AoS handles: the canonical layout IS the device layout)
 static int upload(ilqr_batch* h, const double* src, void* dst_tiled, int S, int E) {
   const size_t n = (size_t)h->B * S * E;
+  if (h->aos && h->dtype == ILQR_DTYPE_F32) {  // generic fp32 handle: canonical layout, rounded on the device
+    if (int rc = ensure_staging(h, n)) return rc;
+    HIPCHK(hipMemcpyAsync(h->staging, src, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL((k_convert<double, float>), dim3(grid_for(n, 256)), dim3(256), 0, h->stream, h->staging, (float*)dst_tiled, n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));  // staging is reused by the next call
+    return 0;
+  }
   if (h->aos) {
     HIPCHK(hipMemcpyAsync(dst_tiled, src, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -276,6 +292,14 @@ static int upload(ilqr_batch* h, const double* src, void* dst_tiled, int S, int 
 }
 static int download(ilqr_batch* h, const void* src_tiled, double* dst, int S, int E) {
   const size_t n = (size_t)h->B * S * E;
+  if (h->aos && h->dtype == ILQR_DTYPE_F32) {  // generic fp32 handle: widened on the device
+    if (int rc = ensure_staging(h, n)) return rc;
+    hipLaunchKernelGGL((k_convert<float, double>), dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const float*)src_tiled, h->staging, n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(dst, h->staging, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+  }
   if (h->aos) {
     HIPCHK(hipMemcpyAsync(dst, src_tiled, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -292,11 +316,12 @@ static int download(ilqr_batch* h, const void* src_tiled, double* dst, int S, in
   return 0;
 }
 static int launch_derivatives(ilqr_batch* h, int force);
-// the record array of a tiled handle, allocated (zero-filled) on first use
+// the record array, allocated (zero-filled) on first use
 static int ensure_records(ilqr_batch* h) {
   if (h->v.D) return 0;
-  if (h->aos) return dev_alloc(h, &h->v.D, (size_t)h->B * (h->T + 1) * rec_of(h));  // (generic handles: on first use as well -- 44 GB at configs[4])
-  if (int rc = dev_alloc_real(h, &h->v.D, (size_t)h->ntiles * (h->T + 1) * rec_of(h) * TW)) return rc;
+  // (generic handles: on first use as well -- 44 GB at configs[4] in fp64, 22 GB in fp32)
+  const size_t n = h->aos ? (size_t)h->B * (h->T + 1) * rec_of(h) : (size_t)h->ntiles * (h->T + 1) * rec_of(h) * TW;
+  if (int rc = dev_alloc_real(h, &h->v.D, n)) return rc;
   sync_float_view(h);
   return 0;
 }
@@ -313,13 +338,16 @@ static int materialise_records(ilqr_batch* h) {
     h->lq_fused_stale = false;
     h->records_partial = false;
     const int nchunk = (h->T + 1 + kAnalyticChunk - 1) / kAnalyticChunk;
-    hipLaunchKernelGGL(k_analytic_lq, dim3(h->B * nchunk), dim3(64), 0, h->stream, h->v, h->lq, 1, 0, h->const_rec, kAnalyticChunk);
+    with_view(h, [&](auto& v) {
+      hipLaunchKernelGGL((k_analytic_lq<std::remove_pointer_t<decltype(v.D)>>), dim3(h->B * nchunk), dim3(64), 0, h->stream, v, h->lq, 1, 0, h->const_rec, kAnalyticChunk);
+      return 0;
+    });
     HIPCHK(hipGetLastError());
     return 0;
   }
-  if (!h->records_partial) return 0;
+  if (!h->records_partial) return 0;  // (never on an fp32 handle: its sweep writes whole records)
   const int nchunk = (h->T + 1 + kAnalyticChunk - 1) / kAnalyticChunk;
-  hipLaunchKernelGGL(k_analytic_lq, dim3(h->B * nchunk), dim3(64), 0, h->stream, h->v, h->lq, 1, 2, h->const_rec, kAnalyticChunk);
+  hipLaunchKernelGGL(k_analytic_lq<double>, dim3(h->B * nchunk), dim3(64), 0, h->stream, h->v, h->lq, 1, 2, h->const_rec, kAnalyticChunk);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -334,7 +362,10 @@ static int upload_rec(ilqr_batch* h, const double* src, int off, int E) {
   if (int rc = ensure_staging(h, n)) return rc;
   HIPCHK(hipMemcpyAsync(h->staging, src, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
   if (h->aos) {
-    hipLaunchKernelGGL(k_rec_aos, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, h->v.D, h->staging, h->B, S, rec_of(h), off, E, 1);
+    if (h->dtype == ILQR_DTYPE_F32)
+      hipLaunchKernelGGL(k_rec_aos<float>, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, h->vf.D, h->staging, h->B, S, rec_of(h), off, E, 1);
+    else
+      hipLaunchKernelGGL(k_rec_aos<double>, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, h->v.D, h->staging, h->B, S, rec_of(h), off, E, 1);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     return 0;
@@ -353,7 +384,10 @@ static int download_rec(ilqr_batch* h, double* dst, int off, int E) {
   const size_t n = (size_t)h->B * S * E;
   if (int rc = ensure_staging(h, n)) return rc;
   if (h->aos) {
-    hipLaunchKernelGGL(k_rec_aos, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, h->v.D, h->staging, h->B, S, rec_of(h), off, E, 0);
+    if (h->dtype == ILQR_DTYPE_F32)
+      hipLaunchKernelGGL(k_rec_aos<float>, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, h->vf.D, h->staging, h->B, S, rec_of(h), off, E, 0);
+    else
+      hipLaunchKernelGGL(k_rec_aos<double>, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, h->v.D, h->staging, h->B, S, rec_of(h), off, E, 0);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(dst, h->staging, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));

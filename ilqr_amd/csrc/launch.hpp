@@ -28,7 +28,7 @@ static int launch_rollout_t(ilqr_batch* h, const V& v, const M& m, bool gains, b
   HIPCHK(hipGetLastError());
   return 0;
 }
-// f(model) for the handle's generic device twin
+// f(model) for the handle's generic device twin (fp32 handle: the double twin its finite differences are taken in)
 template <class F>
 static int with_generic_model(ilqr_batch* h, F&& f) {
   if (h->model == ILQR_MODEL_LQ) return h->lq_wide ? f(h->lq_w) : f(h->lq);
@@ -37,6 +37,21 @@ static int with_generic_model(ilqr_batch* h, F&& f) {
     if (h->model == ILQR_MODEL_USER) return f(h->user_g);
 #endif
   return fail(ILQR_ERR_UNSUPPORTED, "model %d has no generic device kernels", h->model);
+}
+// f(model) for the model the handle's generic rollouts integrate: the float twin on an fp32 handle
+template <class F>
+static int with_rollout_model(ilqr_batch* h, F&& f) {
+  if (h->dtype != ILQR_DTYPE_F32) return with_generic_model(h, f);
+  if (h->model == ILQR_MODEL_LQ) return f(h->lq_f);
+#ifdef ILQR_HAVE_USER_MODEL
+  if constexpr (kUserGeneric)
+    if (h->model == ILQR_MODEL_USER) return f(h->user_gf);
+#endif
+  return fail(ILQR_ERR_UNSUPPORTED, "model %d has no fp32 generic device kernels", h->model);
+}
+template <class R>
+static const BatchViewT<R>& view_of(const ilqr_batch* h) {
+  if constexpr (std::is_same<R, float>::value) return h->vf; else return h->v;
 }
 // generic path (generic.hpp): what = RG_INIT / RG_SEARCH / RG_COMMIT.  The LQ model rolls out on the
 // matrix cores (k_rollout_lq, one wavefront per trajectory); ILQR_ROUTE_LQ_THREAD_ROLLOUT selects the
@@ -60,13 +75,14 @@ static int launch_rollout_g(ilqr_batch* h, const M& m, int what, const AlphaSet&
     HIPCHK(hipGetLastError());
     return 0;
   }
+  const BatchViewT<typename M::real>& v = view_of<typename M::real>(h);
   if (what == RG_SEARCH)
-    hipLaunchKernelGGL((k_rollout_g<M, RG_SEARCH>), dim3((h->B + kSearchTraj - 1) / kSearchTraj), dim3(64), 0, h->stream, h->v, m, al,
+    hipLaunchKernelGGL((k_rollout_g<M, RG_SEARCH>), dim3((h->B + kSearchTraj - 1) / kSearchTraj), dim3(64), 0, h->stream, v, m, al,
                        cost_out, nullptr, mode, 0, h->sp.fixes);
   else if (what == RG_INIT)
-    hipLaunchKernelGGL((k_rollout_g<M, RG_INIT>), dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->v, m, al, cost_out, nullptr, 0, 1, h->sp.fixes);
+    hipLaunchKernelGGL((k_rollout_g<M, RG_INIT>), dim3((h->B + 63) / 64), dim3(64), 0, h->stream, v, m, al, cost_out, nullptr, 0, 1, h->sp.fixes);
   else
-    hipLaunchKernelGGL((k_rollout_g<M, RG_COMMIT>), dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->v, m, al, cost_out,
+    hipLaunchKernelGGL((k_rollout_g<M, RG_COMMIT>), dim3((h->B + 63) / 64), dim3(64), 0, h->stream, v, m, al, cost_out,
                        h->commit_idx, 0, write_cost, h->sp.fixes);
   HIPCHK(hipGetLastError());
   return 0;
@@ -78,7 +94,7 @@ static int launch_rollout(ilqr_batch* h, bool gains, bool cand, const AlphaSet& 
   std::pair<hipEvent_t, hipEvent_t> ev;
   if (int rc = timer_begin(h, ILQR_STAGE_ROLLOUT, &ev)) return rc;
   const int rc = (h->plan.rollout != Rollout::tiled)
-      ? with_generic_model(h, [&](auto& m) {
+      ? with_rollout_model(h, [&](auto& m) {
           if (!gains) return launch_rollout_g(h, m, RG_INIT, al, cost_out, 0, 1);
           if (n_alpha == NALPHA) return launch_rollout_g(h, m, RG_SEARCH, al, cost_out, mode, 0, with_accept);
           return launch_rollout_g(h, m, RG_COMMIT, al, cost_out, 0, 1);  // a single closed-loop rollout written in place (warm start): slot commit_idx of `al`
@@ -101,7 +117,7 @@ static int launch_commit(ilqr_batch* h) {
     return 0;
   }
   if (h->plan.commit != Commit::tiled)  // no stored candidates otherwise on the generic path: re-run the accepted rollout in place
-    return with_generic_model(h, [&](auto& m) { return launch_rollout_g(h, m, RG_COMMIT, line_search_alphas(), h->v.cost, 0, 0); });
+    return with_rollout_model(h, [&](auto& m) { return launch_rollout_g(h, m, RG_COMMIT, line_search_alphas(), h->v.cost, 0, 0); });
   if (int rc = refuse_grouped_cands(h)) return rc;
   dim3 grid((h->T + 1 + 15) / 16, h->ntiles), block(256);
   if (int rc = with_model(h, [&](auto& v, auto& m, auto&) {
@@ -155,19 +171,35 @@ static int launch_derivatives(ilqr_batch* h, int force) {
   dim3 grid((h->T + 1 + 15) / 16, h->ntiles), block(256);
   const int* ci = h->commit_pending ? h->commit_idx : nullptr;
   if (route != Derivatives::tiled) {
+    // fp32 handles: the same kernels' float-storage instantiations (float knots widened, double arithmetic, float records)
+    const bool f32 = h->dtype == ILQR_DTYPE_F32;
     if (route == Derivatives::analytic_lq) {
-      const int what = h->route.full_records ? 0 : 1;  // (A/B runs and the bit-identity test)
+      const int what = (h->route.full_records || f32) ? 0 : 1;  // (A/B runs and the bit-identity test; fp32: whole records -- const_rec is double)
       const int chunk = (what == 1) ? 4 * kAnalyticChunk : kAnalyticChunk;
       const int nchunk = (h->T + 1 + chunk - 1) / chunk;
-      hipLaunchKernelGGL(k_analytic_lq, dim3(h->B * nchunk), dim3(64), 0, h->stream, h->v, h->lq, force, what, h->const_rec, chunk);
+      if (f32)
+        hipLaunchKernelGGL(k_analytic_lq<float>, dim3(h->B * nchunk), dim3(64), 0, h->stream, h->vf, h->lq, force, what, h->const_rec, chunk);
+      else
+        hipLaunchKernelGGL(k_analytic_lq<double>, dim3(h->B * nchunk), dim3(64), 0, h->stream, h->v, h->lq, force, what, h->const_rec, chunk);
       h->records_partial = (what == 1);
     } else if (route == Derivatives::lq) {
       // the LQ twin: every perturbed point of the knots t < T evaluated by what moved (k_derivatives_lq), knot T by the generic sweep
       const int nchunk = (h->T + kLqKnotsPerWave - 1) / kLqKnotsPerWave;
-      hipLaunchKernelGGL(k_derivatives_lq, dim3(h->B * nchunk), dim3(64), 0, h->stream, h->v, h->lq, force);
-      hipLaunchKernelGGL((k_derivatives_g<LqModel>), dim3(h->B), dim3(64), 0, h->stream, h->v, h->lq, force, h->T);
+      with_view(h, [&](auto& v) {
+        using S = std::remove_pointer_t<decltype(v.D)>;
+        hipLaunchKernelGGL(k_derivatives_lq<S>, dim3(h->B * nchunk), dim3(64), 0, h->stream, v, h->lq, force);
+        hipLaunchKernelGGL((k_derivatives_g<LqModel, S>), dim3(h->B), dim3(64), 0, h->stream, v, h->lq, force, h->T);
+        return 0;
+      });
     } else if (int rc = with_generic_model(h, [&](auto& m) {
-                 hipLaunchKernelGGL((k_derivatives_g<std::decay_t<decltype(m)>>), dim3(h->B * (h->T + 1)), dim3(64), 0, h->stream, h->v, m, force, -1);
+                 using M = std::decay_t<decltype(m)>;
+                 if constexpr (M::NU <= WM) {
+                   if (f32) {
+                     hipLaunchKernelGGL((k_derivatives_g<M, float>), dim3(h->B * (h->T + 1)), dim3(64), 0, h->stream, h->vf, m, force, -1);
+                     return 0;
+                   }
+                 }
+                 hipLaunchKernelGGL((k_derivatives_g<M>), dim3(h->B * (h->T + 1)), dim3(64), 0, h->stream, h->v, m, force, -1);
                  return 0;
                }))
       return rc;
@@ -201,9 +233,18 @@ static int launch_backward(ilqr_batch* h, int mode) {
     const double* crec = (fused || h->records_partial) ? h->const_rec : nullptr;
     const dim3 grid(h->B), block(64);
     const bool full = h->nu == WM && (h->nx == 16 || h->nx == 32);
-#define ILQR_W3(...) hipLaunchKernelGGL((k_backward_w3<__VA_ARGS__>), grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec)
+    const bool f32 = h->dtype == ILQR_DTYPE_F32;  // float storage: the <.., float> instantiations on h->vf (never W2 or two control tiles: ilqr_create)
+#define ILQR_W3_F64(...) hipLaunchKernelGGL((k_backward_w3<__VA_ARGS__>), grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec)
+#define ILQR_W3(NT_, FULL_, LQF_, REGV_)                                                                                                      \
+    do {                                                                                                                                    \
+      if (f32)                                                                                                                              \
+        hipLaunchKernelGGL((k_backward_w3<NT_, FULL_, LQF_, REGV_, 1, float>), grid, block, 0, h->stream, h->vf, h->nx, h->nu, h->d_umin,    \
+                           h->d_umax, h->sp, mode, crec);                                                                                   \
+      else                                                                                                                                  \
+        ILQR_W3_F64(NT_, FULL_, LQF_, REGV_);                                                                                               \
+    } while (0)
     if (route == Backward::w3_two_tiles) {  // nu > 16, or ILQR_ROUTE_TWO_CONTROL_TILES (never the fused LQ route; ilqr_create keeps W2 and REGULARIZE_VXX off here)
-      if (h->nx > 16) ILQR_W3(2, false, false, false, 2); else ILQR_W3(1, false, false, false, 2);
+      if (h->nx > 16) ILQR_W3_F64(2, false, false, false, 2); else ILQR_W3_F64(1, false, false, false, 2);
     } else if (route == Backward::w2 && h->nx > 16)
       hipLaunchKernelGGL(k_backward_w2<2>, grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec);
     else if (route == Backward::w2)
@@ -211,12 +252,13 @@ static int launch_backward(ilqr_batch* h, int mode) {
     else if (route == Backward::w3_regv) {  // ILQR_FLAG_REGULARIZE_VXX: the bounds-checked instantiations on whole records (never the fused LQ route)
       if (h->nx > 16) ILQR_W3(2, false, false, true); else ILQR_W3(1, false, false, true);
     } else if (h->nx > 16) {
-      if (fused) { if (full) ILQR_W3(2, true, true); else ILQR_W3(2, false, true); }
-      else { if (full) ILQR_W3(2, true, false); else ILQR_W3(2, false, false); }
+      if (fused) { if (full) ILQR_W3(2, true, true, false); else ILQR_W3(2, false, true, false); }
+      else { if (full) ILQR_W3(2, true, false, false); else ILQR_W3(2, false, false, false); }
     } else {
-      if (fused) ILQR_W3(1, false, true); else ILQR_W3(1, false, false);
+      if (fused) ILQR_W3(1, false, true, false); else ILQR_W3(1, false, false, false);
     }
 #undef ILQR_W3
+#undef ILQR_W3_F64
   } else if (route == Backward::quad) {
     dim3 grid(h->ntiles), block(64);  // one wavefront = one tile of 16 trajectories x 4 lanes
     if (int rc = with_model(h, [&](auto& v, auto& m, auto&) {

@@ -28,6 +28,11 @@ __global__ void k_pack(const double* __restrict__ src, real* __restrict__ dst, i
     dst[i] = (b < B) ? (real)src[((size_t)b * S + s) * E + e] : real(0);
   }
 }
+// an fp32 generic handle's array (trajectory-contiguous: the canonical layout itself) <-> double, element by element
+template <class From, class To>
+__global__ void k_convert(const From* __restrict__ src, To* __restrict__ dst, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = (To)src[i];
+}
 // tiled src -> canonical dst   (one thread per canonical element; reads are line-strided but
 // this path only serves getters)
 template <class real>

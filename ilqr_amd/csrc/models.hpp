@@ -385,7 +385,7 @@ struct has_analytic_record<M, std::void_t<decltype(std::declval<const M&>().anal
 // persistent routes of the shipped acrobot / double integrator; both arithmetic flavours are instantiated: fp32 handles take
 // their finite differences in UserModelT<double>) -- examples/user_model_acrobot.hpp.  Any other NX <= 32, NU <= 32 runs in
 // the generic kernels (generic.hpp: thread-per-rollout k_rollout_g, wavefront-per-knot finite differences k_derivatives_g,
-// the matrix-core backward pass k_backward_w3; fp64; an analytic_record, if the model has one, is called by one lane per knot under
+// the matrix-core backward pass k_backward_w3; fp64, or fp32 up to NU = 16 with UserModelT<float> as the rollouts' twin; an analytic_record, if the model has one, is called by one lane per knot under
 // ILQR_FLAG_ANALYTIC_DERIVATIVES) -- examples/user_model_linear6.hpp.  A SMALL twin (even NX <= 8, NU <= 4) is compiled into both and
 // runs, unless ILQR_ROUTE_WAVE_PER_TRAJECTORY asks for the generic kernels, in the tiled thread kernels: one thread per knot
 // (k_derivatives), per trajectory (k_backward_t) and per rollout (k_rollout) with the whole 6 x 6 algebra in registers -- a 16 x 16

@@ -33,6 +33,7 @@ struct RouteInputs {
   int model, nx, nu, flags, route, ntiles, num_cus;  // (num_cus after ilqr_desc.assume_cus)
   bool user_tiled, user_small;  // the build's user twin: kUserTiled, kUserSmall (models.hpp)
   bool cands_allocated;         // the LQ search's candidate buffers (not under ILQR_ROUTE_LQ_RECOMMIT, nor if the device could not spare them)
+  int dtype = ILQR_DTYPE_F64;   // ilqr_desc.dtype: an fp32 LQ handle searches with the thread-per-rollout kernel (k_rollout_lq is fp64)
 };
 
 // trajectory-contiguous layout, generic kernels: host-evaluated models, the LQ model, user twins without tiled kernels or sent there
@@ -57,7 +58,7 @@ inline RoutePlan plan_route(const RouteInputs& in) {
     else if (lq && analytic && !lq_wide) p.derivatives = Derivatives::analytic_lq;
     else if (lq && !(rt & ILQR_ROUTE_LQ_DENSE_FD) && !lq_wide) p.derivatives = Derivatives::lq;
     else p.derivatives = Derivatives::generic;
-    p.rollout = !lq_matrix_core_search(in.model, in.nu, rt) ? Rollout::generic : in.cands_allocated ? Rollout::lq_accept : Rollout::lq;
+    p.rollout = (!lq_matrix_core_search(in.model, in.nu, rt) || in.dtype == ILQR_DTYPE_F32) ? Rollout::generic : in.cands_allocated ? Rollout::lq_accept : Rollout::lq;
     p.commit = p.rollout == Rollout::lq_accept ? Commit::lq_copy : Commit::rerun;
     return p;
   }

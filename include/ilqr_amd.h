@@ -59,7 +59,8 @@ enum ilqr_model_id {
   ILQR_MODEL_ACROBOT = 0,           /* include/acrobot.h            nx=4 nu=1 */
   ILQR_MODEL_DOUBLE_INTEGRATOR = 1, /* include/double_integrator.h  nx=4 nu=2 */
   ILQR_MODEL_LQ = 2,                /* synthetic LQ (BASELINE.json configs[4]): xdot = A x + B u, cost .5(x'Qx + u'Ru),
-                                       final .5 x'Qf x, nx<=32 nu<=32 (more than 16: generic thread-per-rollout and point-by-point kernels); device twin, runs end to end (lq_* of the desc) */
+                                       final .5 x'Qf x, nx<=32 nu<=32 (more than 16: generic thread-per-rollout and point-by-point kernels, fp64); device twin, runs end to end (lq_* of the desc);
+                                       fp32 up to nu = 16 (the search then runs the thread-per-rollout kernel: the matrix-core one is fp64) */
   ILQR_MODEL_HOST = 3,              /* a Model that exists only as host code, nx<=32 nu<=32 (at exactly 32 free controls the box-QP factors
                                        with Eigen's UNBLOCKED LLT, as below 32; Eigen 3.3.4 itself switches to its blocked LLT there: rounding,
                                        and the partial factor of an indefinite block, may differ from the reference's): the caller evaluates its
@@ -67,7 +68,7 @@ enum ilqr_model_id {
                                        ilqr_accept_candidates), the backward pass / box-QPs / accept logic run on the
                                        device; rollout and finite-difference entry points return ILQR_ERR_UNSUPPORTED */
   ILQR_MODEL_USER = 4               /* the caller's OWN device twin (nx<=32 nu<=32; nx = 4 with nu in {1,2} runs every kernel of the
-                                       nx = 4 path, both dtypes; other sizes the generic fp64 kernels), compiled into a build of this
+                                       nx = 4 path, both dtypes; other sizes the generic kernels, both dtypes up to nu = 16), compiled into a build of this
                                        library from a header that is not part of it: -DILQR_USER_MODEL_HEADER='"file.hpp"'
                                        (ilqr_amd/csrc/models.hpp states the contract, INTEGRATION.md 5 the recipe).  A build without such a header
                                        answers ILQR_ERR_UNSUPPORTED; ilqr_has_user_model() tells which one is loaded. */
@@ -79,7 +80,10 @@ enum ilqr_model_id {
  * scalars (cost, dV, gradient norm, lambda) stay double, and the finite differences are taken in double
  * from the float knot (eps = 1e-3 second differences of an O(1e3) cost are pure rounding noise in float)
  * and rounded to float when stored.  The ABI's arrays are double in both modes; the conversion happens on
- * the device when they are packed into / unpacked from the handle's layout. */
+ * the device when they are packed into / unpacked from the handle's layout.
+ * ILQR_DTYPE_F32 on the generic path (ILQR_MODEL_LQ and ILQR_MODEL_USER of other sizes, nu <= 16): the same storage, the rollouts
+ * in float; the finite differences, exact derivatives and the whole backward pass in double on the widened float values, the results
+ * rounded when stored.  Not with ILQR_MODEL_HOST, ILQR_ROUTE_BACKWARD_W2 or ILQR_ROUTE_TWO_CONTROL_TILES (ILQR_ERR_UNSUPPORTED). */
 enum ilqr_dtype { ILQR_DTYPE_F64 = 0, ILQR_DTYPE_F32 = 1 };
 
 /* where a trajectory's outer loop stands (src/ilqr_core.cpp:103-288) */
@@ -198,7 +202,8 @@ enum ilqr_route {
   ILQR_ROUTE_LQ_DENSE_FD = 2048,    /* LQ model, finite differences: every perturbed point's quadratic forms evaluated densely on the matrix cores
                                        (k_derivatives_g) instead of by what moved (k_derivatives_lq: Q p = Q x + delta_i Q[:,i] + delta_j Q[:,j]) */
   ILQR_ROUTE_WAVE_PER_TRAJECTORY = 4096, /* a small user twin (even nx <= 8, nu <= 4): the generic wavefront-per-trajectory kernels instead of the tiled
-                                            thread-per-trajectory ones it runs in by default (cross-check; fp64 only) */
+                                            thread-per-trajectory ones it runs in by default (cross-check of the tiled kernels; fp64 only,
+                                            although the generic kernels have an fp32 mode for the twins that have no tiled kernels) */
   ILQR_ROUTE_BACKWARD_W2 = 1024,    /* generic path: round 2's register kernel k_backward_w2 (literal Cholesky in every box-QP, per-knot cx / cu records)
                                        instead of k_backward_w3 (matrix-core refinement of the previous knot's inverse; LQ model with exact
                                        derivatives: no record array at all) */
