@@ -126,6 +126,32 @@ class BatchILQR:
     def synchronize(self):
         self._check(self.lib.ilqr_synchronize(self.h))
 
+    # ---- model-predictive control on the device (ilqr_shift_horizon, ilqr_mpc_step, ilqr_copy_controls_to_device) ----
+    # Nothing below waits for the GPU.  Stream rule: a caller whose x0 is written, or whose controls are read, by torch passes
+    # stream=torch.cuda.current_stream().cuda_stream at construction; torch's kernels and the solver's are then ordered by the stream
+    # itself, without a host synchronisation.  torch's default stream is the null stream (0), and a handle given 0 makes a stream of its
+    # own: run torch on a stream of its own (`with torch.cuda.stream(torch.cuda.Stream()):`) -- INTEGRATION.md, "MPC on the device".
+    _TAILS = {"hold": capi.TAIL_HOLD, "zero": capi.TAIL_ZERO}
+
+    def shift_horizon(self, shift, tail="hold"):
+        """Move the stored nominal (xs, us, k, K) `shift` knots toward t = 0, in place.  tail="hold" repeats us[T-1] and K[T-1], "zero"
+        zeros them; k's tail is zero and xs's is xs[T] under either (include/ilqr_amd.h, enum ilqr_tail)."""
+        self._check(self.lib.ilqr_shift_horizon(self.h, int(shift), self._TAILS[tail]))
+
+    def mpc_step(self, x0=None, x0_ptr=None, shift=1, iters=1, tail="hold"):
+        """One receding-horizon step: shift_horizon(shift, tail), warm start from the new state, `iters` iterations.  x0: numpy [B][nx];
+        x0_ptr: a raw device pointer to [B][nx] float64 on the handle's device (torch.Tensor.data_ptr()).  Exactly one of them."""
+        if (x0 is None) == (x0_ptr is None):
+            raise ValueError("mpc_step: exactly one of x0 and x0_ptr")
+        if x0 is not None:
+            x0 = _c(x0)
+            assert x0.shape == (self.B, self.nx)
+        self._check(self.lib.ilqr_mpc_step(self.h, _p(x0), x0_ptr, int(shift), self._TAILS[tail], int(iters)))
+
+    def copy_controls_to_device(self, t0, n, ptr):
+        """us[:, t0 : t0 + n, :] as float64 [B][n][nu] into caller-owned device memory `ptr` (raw pointer); enqueued on the handle's stream."""
+        self._check(self.lib.ilqr_copy_controls_to_device(self.h, int(t0), int(n), ptr))
+
     # ---- stages ----
     def compute_derivatives(self):
         self._check(self.lib.ilqr_compute_derivatives(self.h))

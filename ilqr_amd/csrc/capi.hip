@@ -357,6 +357,7 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
   rc |= dev_alloc(h, &v.diverge, Bp);
   rc |= dev_alloc(h, &v.backpass_done, Bp);
   rc |= dev_alloc(h, &v.n_running, 1);
+  rc |= dev_alloc(h, &h->x0_stage, (size_t)h->B * nx);
   rc |= dev_alloc(h, &h->commit_idx, Bp);
   rc |= dev_alloc(h, &h->phase_ticks, 5 * (size_t)h->ntiles);
   if (!rc && hipMemsetAsync(h->commit_idx, 0xFF, Bp * sizeof(int), h->stream) != hipSuccess) rc = 1;
@@ -396,7 +397,9 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
 int ilqr_create(const ilqr_desc* d, ilqr_batch** out) {
   if (!d || !out) return fail(ILQR_ERR_INVALID, "null argument");
   *out = nullptr;
-  REQUIRE(d->abi_version == ILQR_AMD_ABI_VERSION, "ABI version %d, library is %d", d->abi_version, ILQR_AMD_ABI_VERSION);
+  // (ABI 6 added entry points only: ilqr_desc is ABI 5's, and a caller built against ABI 5 keeps working)
+  REQUIRE(d->abi_version == ILQR_AMD_ABI_VERSION || d->abi_version == 5, "ABI version %d, library is %d (accepts 5 and %d)", d->abi_version,
+          ILQR_AMD_ABI_VERSION, ILQR_AMD_ABI_VERSION);
   REQUIRE(d->B >= 1 && d->T >= 1 && d->nx >= 1 && d->nu >= 1, "B, T, nx, nu must be positive");
   REQUIRE(d->nx <= MAXN && d->nu <= kMaxControls, "nx <= %d and nu <= %d", MAXN, kMaxControls);
   REQUIRE(d->dt > 0, "dt must be positive");
@@ -669,6 +672,117 @@ int ilqr_warm_start(ilqr_batch* h, const double* x0) {
   if (int rc = scalars_to_dev(h, lam.data(), h->v.lambda)) return rc;
   if (int rc = scalars_to_dev(h, dlam.data(), h->v.dlambda)) return rc;
   return ilqr_generate_trajectory(h);
+}
+
+// ---- receding horizon (ABI 6) ----------------------------------------------------------------
+// Every per-knot array of the nominal (xs, us, k, K) moves `shift` knots toward t = 0 in place (k_shift_horizon, layout.hpp); the tail rule of
+// include/ilqr_amd.h.  Cost, lambda, status and iteration counts stay.  Enqueued on the handle's stream, nothing waited for.
+static int shift_nominal(ilqr_batch* h, int shift, int tail) {
+  if (int rc = flush_commit(h)) return rc;  // an accepted candidate not yet copied into xs / us belongs to the old horizon
+  h->cands = Cands::none;                   // the candidates are rollouts of the old horizon
+  h->lq_cands_kept = false;
+  if (!h->aos && h->recs == ilqr_batch::REC_VALID) h->recs = ilqr_batch::REC_STALE;  // records of the old nominal: recomputed when asked for
+  if (shift == 0) return 0;
+  const int nx = h->nx, nu = h->nu, T = h->T;
+  const int lanes = h->aos ? 1 : TW;  // elements per (knot, element) of a segment
+  ShiftSet set;
+  set.arr[0] = {h->v.xs, T + 1, nx * lanes, SHIFT_TAIL_HOLD};  // xs[T] repeated under either tail
+  set.arr[1] = {h->v.us, T, nu * lanes, tail};
+  set.arr[2] = {h->v.kff, T, nu * lanes, SHIFT_TAIL_ZERO};
+  set.arr[3] = {h->v.Kfb, T, nu * nx * lanes, tail};
+  set.nseg = h->aos ? h->B : h->ntiles;
+  set.shift = shift;
+  const dim3 grid((unsigned)std::min(set.nseg, 65535), 4), block(256);
+  if (h->dtype == ILQR_DTYPE_F32)
+    hipLaunchKernelGGL(k_shift_horizon<float>, grid, block, 0, h->stream, set);
+  else
+    hipLaunchKernelGGL(k_shift_horizon<double>, grid, block, 0, h->stream, set);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+static int check_shift(ilqr_batch* h, int shift, int tail) {
+  REQUIRE(shift >= 0 && shift < h->T, "shift %d: 0 <= shift < T = %d", shift, h->T);
+  REQUIRE(tail == ILQR_TAIL_HOLD || tail == ILQR_TAIL_ZERO, "tail %d: ILQR_TAIL_HOLD or ILQR_TAIL_ZERO", tail);
+  return 0;
+}
+
+int ilqr_shift_horizon(ilqr_batch* h, int shift, int tail) {
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  if (int rc = check_shift(h, shift, tail)) return rc;
+  if (!h->initialised) return fail(ILQR_ERR_STATE, "shift_horizon before ilqr_init_traj/ilqr_set_trajectory: there is no nominal to shift");
+  HIPCHK(hipSetDevice(h->device));
+  return shift_nominal(h, shift, tail == ILQR_TAIL_HOLD ? SHIFT_TAIL_HOLD : SHIFT_TAIL_ZERO);
+}
+
+// shift -> x0 -> ilqr_warm_start's rollout and commit -> the warm reset on the device -> n_iters iterations: the state ilqr_warm_start leaves
+// on a handle with max_iter = n_iters, without one host synchronisation (ilqr_warm_start reads lambda back and waits per chunk)
+int ilqr_mpc_step(ilqr_batch* h, const double* x0, const void* x0_device, int shift, int tail, int n_iters) {
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  if (host_model(h)) return fail(ILQR_ERR_UNSUPPORTED, "ilqr_mpc_step: a host-evaluated model's rollouts run on the host (as for ilqr_warm_start)");
+  REQUIRE((x0 != nullptr) != (x0_device != nullptr), "ilqr_mpc_step: exactly one of x0 (host) and x0_device");
+  if (int rc = check_shift(h, shift, tail)) return rc;
+  REQUIRE(n_iters >= 0, "n_iters %d must be >= 0", n_iters);
+  if (!h->initialised) return fail(ILQR_ERR_STATE, "mpc_step needs a previous solve (assert us.size()>0, ilqr_core.cpp:66)");
+  HIPCHK(hipSetDevice(h->device));
+  if (int rc = shift_nominal(h, shift, tail == ILQR_TAIL_HOLD ? SHIFT_TAIL_HOLD : SHIFT_TAIL_ZERO)) return rc;
+  // x0 into the handle's layout: the host array's one transfer goes to a buffer of its own (the shared staging buffer may be reallocated,
+  // which waits); a device x0 is read where it lies
+  const size_t n0 = (size_t)h->B * h->nx;
+  const double* src = (const double*)x0_device;
+  if (x0) {
+    double* dst = (h->aos && h->dtype == ILQR_DTYPE_F64) ? h->v.x0 : h->x0_stage;
+    HIPCHK(hipMemcpyAsync(dst, x0, n0 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    src = dst;
+  }
+  if (h->aos && h->dtype == ILQR_DTYPE_F32) {
+    hipLaunchKernelGGL((k_convert<double, float>), dim3(grid_for(n0, 256)), dim3(256), 0, h->stream, src, (float*)h->v.x0, n0);
+    HIPCHK(hipGetLastError());
+  } else if (h->aos) {
+    if (src != h->v.x0) HIPCHK(hipMemcpyAsync(h->v.x0, src, n0 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  } else {
+    const size_t nt = (size_t)h->ntiles * h->nx * TW;
+    if (h->dtype == ILQR_DTYPE_F32)
+      hipLaunchKernelGGL(k_pack<float>, dim3(grid_for(nt, 256)), dim3(256), 0, h->stream, src, (float*)h->v.x0, h->B, h->ntiles, 1, h->nx);
+    else
+      hipLaunchKernelGGL(k_pack<double>, dim3(grid_for(nt, 256)), dim3(256), 0, h->stream, src, h->v.x0, h->B, h->ntiles, 1, h->nx);
+    HIPCHK(hipGetLastError());
+  }
+  // ilqr_warm_start's rollout, kernel for kernel: u = us[t] + K[t](x - xs[t]) (every alpha 0), written into xs / us
+  AlphaSet al;
+  for (int i = 0; i < NALPHA; i++) al.a[i] = 0.0;
+  if (h->plan.commit != Commit::tiled) {
+    HIPCHK(hipMemsetAsync(h->commit_idx, 0, (size_t)h->Bp * sizeof(int), h->stream));
+    if (int rc = launch_rollout(h, true, true, al, 1, h->v.cost, 0)) return rc;
+  } else {
+    if (int rc = launch_rollout(h, true, true, al, 1, h->v.cost, 0)) return rc;
+    HIPCHK(hipMemsetAsync(h->commit_idx, 0, (size_t)h->Bp * sizeof(int), h->stream));
+    if (int rc = launch_commit(h)) return rc;
+  }
+  HIPCHK(hipMemsetAsync(h->commit_idx, 0xFF, (size_t)h->Bp * sizeof(int), h->stream));
+  hipLaunchKernelGGL(k_warm_reset<double>, dim3((h->Bp + 255) / 256), dim3(256), 0, h->stream, h->v);
+  HIPCHK(hipGetLastError());
+  if (n_iters == 0) return 0;
+  return ilqr_iterate(h, n_iters);
+}
+
+int ilqr_copy_controls_to_device(ilqr_batch* h, int t0, int n_knots, void* u_device) {
+  if (!h || !u_device) return fail(ILQR_ERR_INVALID, "null argument");
+  REQUIRE(t0 >= 0 && n_knots >= 1 && t0 + n_knots <= h->T, "control window [%d, %d): inside [0, T = %d), at least one knot", t0, t0 + n_knots, h->T);
+  if (!h->initialised) return fail(ILQR_ERR_STATE, "copy_controls_to_device before ilqr_init_traj/ilqr_set_trajectory");
+  HIPCHK(hipSetDevice(h->device));
+  const size_t n = (size_t)h->B * n_knots * h->nu;
+  const dim3 grid(grid_for(n, 256)), block(256);
+  double* dst = (double*)u_device;
+  if (h->aos && h->dtype == ILQR_DTYPE_F32)
+    hipLaunchKernelGGL((k_unpack_window<float, false>), grid, block, 0, h->stream, (const float*)h->v.us, dst, h->B, h->T, h->nu, t0, n_knots);
+  else if (h->aos)
+    hipLaunchKernelGGL((k_unpack_window<double, false>), grid, block, 0, h->stream, (const double*)h->v.us, dst, h->B, h->T, h->nu, t0, n_knots);
+  else if (h->dtype == ILQR_DTYPE_F32)
+    hipLaunchKernelGGL((k_unpack_window<float, true>), grid, block, 0, h->stream, (const float*)h->v.us, dst, h->B, h->T, h->nu, t0, n_knots);
+  else
+    hipLaunchKernelGGL((k_unpack_window<double, true>), grid, block, 0, h->stream, (const double*)h->v.us, dst, h->B, h->T, h->nu, t0, n_knots);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 // ---- stages --------------------------------------------------------------------------------

@@ -67,6 +67,7 @@ struct ilqr_batch {
   long long* phase_ticks = nullptr;  // [ntiles][5] per-tile clocks of k_solve_tile: sweep+backward, rollouts+accept, iterations, shader cycles, wall ticks
   double wall_clock_khz = 100000.0;
   double* staging = nullptr;  // device scratch for canonical <-> tiled conversion
+  double* x0_stage = nullptr;  // [B][nx] canonical: a host x0 of ilqr_mpc_step on its way to the device layout (never reallocated, never waited for)
   // LQ model with exact derivatives: the sweep writes one copy of the constant matrices (const_rec) and
   // per knot only cx, cu; records_partial says that D holds no matrices for t < T right now
   double* const_rec = nullptr;   // [2][REC]: the constant blocks of every knot t < T, then knot T's record

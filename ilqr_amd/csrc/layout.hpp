@@ -1,5 +1,5 @@
 // layout.hpp -- canonical [B][S][E] <-> tiled [tile][S][E][16] conversion, slot permutation (compaction), per-trajectory
-// state reset (init_traj, src/ilqr_core.cpp:11-56).  Lane mapping everywhere: consecutive lanes = consecutive trajectories of
+// state reset (init_traj, src/ilqr_core.cpp:11-56), the receding-horizon shift and the control window of an MPC step.  Lane mapping everywhere: consecutive lanes = consecutive trajectories of
 // a tile, so each vector load / store touches whole 128-byte lines of the tiled layout (common.hpp).
 #pragma once
 #include <type_traits>
@@ -101,11 +101,7 @@ __global__ void k_permute_scalar(const T* __restrict__ src, T* __restrict__ dst,
 // per-trajectory state reset (init_traj, ilqr_core.cpp:11-56; statics of ilqr.h:17-18)
 // ------------------------------------------------------------------------------------------
 template <class real>
-__global__ void k_reset_state(BatchViewT<real> v, double lambda0, double dlambda0) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= v.Bp) return;
-  v.lambda[b] = lambda0;
-  v.dlambda[b] = dlambda0;
+__device__ inline void reset_run_state(const BatchViewT<real>& v, int b) {  // everything k_reset_state resets but lambda / dlambda
   v.dV[b] = 0;
   v.dV[v.Bp + b] = 0;
   v.gnorm[b] = 0;
@@ -115,6 +111,95 @@ __global__ void k_reset_state(BatchViewT<real> v, double lambda0, double dlambda
   v.alpha_idx[b] = -1;
   v.diverge[b] = 0;
   v.backpass_done[b] = 0;
+}
+template <class real>
+__global__ void k_reset_state(BatchViewT<real> v, double lambda0, double dlambda0) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= v.Bp) return;
+  v.lambda[b] = lambda0;
+  v.dlambda[b] = dlambda0;
+  reset_run_state(v, b);
+}
+// a new outer loop on the stored solution (warm start, ilqr_core.cpp:65-76; ilqr_mpc_step): status / iteration count / flgChange restart,
+// lambda and dlambda persist (the reference's file statics) -- on the device, so that an MPC step never waits for the stream
+template <class real>
+__global__ void k_warm_reset(BatchViewT<real> v) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= v.Bp) return;
+  reset_run_state(v, b);
+}
+
+// ------------------------------------------------------------------------------------------
+// receding horizon (ilqr_shift_horizon, ilqr_mpc_step)
+// ------------------------------------------------------------------------------------------
+// Both device layouts keep a trajectory array as segments of S knots of W contiguous elements: a tile of the tiled layout
+// ([tile][S][E][16]: W = 16 E) or a trajectory of the trajectory-contiguous one ([b][S][E]: W = E).  Shifting by s knots is then, per
+// segment, a forward move of s W elements -- a[i] = a[i + s W] for i < (S - s) W -- and a tail of s knots: the last knot repeated (hold)
+// or zeros.  One workgroup per segment and array walks the segment upward in chunks of kShiftR x 256 elements, consecutive threads on
+// consecutive elements: every chunk loads all its sources before any of its stores (a source of the chunk may be a destination of
+// the same chunk), and a chunk never reads what an earlier one wrote (sources lie s W elements above the destinations).  In place, nothing
+// allocated, and nothing behind a segment's S W elements touched (the kRolloutFetchSlack rows of the tiled arrays).
+enum { SHIFT_TAIL_HOLD = 0, SHIFT_TAIL_ZERO = 1 };
+struct ShiftArray {
+  void* a;    // the array (float or double, as the handle stores it)
+  int S, W;   // knots per segment, elements per knot of a segment
+  int tail;   // SHIFT_TAIL_*
+};
+struct ShiftSet {
+  ShiftArray arr[4];  // xs, us, k, K
+  int nseg, shift;
+};
+constexpr int kShiftR = 16;  // elements per thread and chunk: 16 loads in flight per thread
+// p[i] = src(i) for i in [lo, hi), all sources of a chunk read before its first store (the barrier also orders whatever the workgroup
+// did before: chunks of the previous range)
+template <class real, class Src>
+__device__ inline void shift_range(real* p, size_t lo, size_t hi, Src src) {
+  const size_t step = (size_t)kShiftR * blockDim.x;
+  for (size_t base = lo; base < hi; base += step) {
+    real r[kShiftR];
+#pragma unroll
+    for (int j = 0; j < kShiftR; j++) {
+      const size_t i = base + (size_t)j * blockDim.x + threadIdx.x;
+      r[j] = (i < hi) ? src(i) : real(0);
+    }
+    __builtin_amdgcn_s_waitcnt(0);  // this wavefront's loads have returned ...
+    __syncthreads();                // ... and every other wavefront's too: now the chunk's stores may overwrite its sources
+#pragma unroll
+    for (int j = 0; j < kShiftR; j++) {
+      const size_t i = base + (size_t)j * blockDim.x + threadIdx.x;
+      if (i < hi) p[i] = r[j];
+    }
+  }
+}
+// grid (segments, 4 arrays), 256 threads; shift >= 1 (0 is no launch)
+template <class real>
+__global__ void __launch_bounds__(256) k_shift_horizon(ShiftSet set) {
+  const ShiftArray A = set.arr[blockIdx.y];
+  if (!A.a) return;
+  const size_t W = (size_t)A.W, n = (size_t)A.S * W, keep = (size_t)(A.S - set.shift) * W, off = (size_t)set.shift * W;
+  const size_t last = n - W;  // the last knot: only the tail writes it (keep <= last), and a held tail writes it with its own values
+  for (int seg = blockIdx.x; seg < set.nseg; seg += gridDim.x) {
+    real* p = (real*)A.a + (size_t)seg * n;
+    shift_range(p, 0, keep, [&](size_t i) { return p[i + off]; });
+    if (A.tail == SHIFT_TAIL_HOLD)
+      shift_range(p, keep, n, [&](size_t i) { return p[last + (i - keep) % W]; });
+    else
+      shift_range(p, keep, n, [&](size_t) { return real(0); });
+  }
+}
+
+// the control window us[:, t0 : t0 + n, :] of an S-knot array as canonical double [B][n][E] (ilqr_copy_controls_to_device): tiled
+// [tile][S][E][16] or trajectory-contiguous [b][S][E] source, one thread per canonical element
+template <class real, bool TILED>
+__global__ void k_unpack_window(const real* __restrict__ src, double* __restrict__ dst, int B, int S, int E, int t0, int n) {
+  const size_t total = (size_t)B * n * E;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int e = (int)(i % E);
+    size_t r = i / E;
+    const int t = t0 + (int)(r % n);
+    const int b = (int)(r / n);
+    dst[i] = TILED ? (double)src[tidx(b / TW, t, e, b % TW, S, E)] : (double)src[((size_t)b * S + t) * E + e];
+  }
 }
 
 }  // namespace ilqr

@@ -37,9 +37,11 @@
 extern "C" {
 #endif
 
-#define ILQR_AMD_ABI_VERSION 5 /* 2: ilqr_desc.dtype; 3: ILQR_MODEL_USER, ilqr_desc.user_params; 4: ilqr_desc.route, assume_cus (the library reads no environment);
+#define ILQR_AMD_ABI_VERSION 6 /* 2: ilqr_desc.dtype; 3: ILQR_MODEL_USER, ilqr_desc.user_params; 4: ilqr_desc.route, assume_cus (the library reads no environment);
                                   5: results into device memory / in one asynchronous call (ilqr_copy_trajectory_to_device, ilqr_copy_gains_to_device,
-                                     ilqr_get_results_async, ilqr_host_register); route bit 128 (ILQR_ROUTE_BACKWARD_LDS, round 1's LDS kernel) retired */
+                                     ilqr_get_results_async, ilqr_host_register); route bit 128 (ILQR_ROUTE_BACKWARD_LDS, round 1's LDS kernel) retired;
+                                  6: receding-horizon steps on the device (ilqr_shift_horizon, ilqr_mpc_step, ilqr_copy_controls_to_device).  ilqr_desc
+                                     is unchanged: ilqr_create accepts abi_version 5 as well */
 
 typedef struct ilqr_batch ilqr_batch; /* opaque: owns all device memory of one batch */
 
@@ -238,6 +240,40 @@ int ilqr_warm_start(ilqr_batch* h, const double* x0);
 /* n_iters bodies of the outer for-loop (src/ilqr_core.cpp:103-288) for every trajectory that
  * is still running; asynchronous (no host synchronisation inside). */
 int ilqr_iterate(ilqr_batch* h, int n_iters);
+
+/* ---- model-predictive control on the device (ABI 6) ------------------------------------------------------------------------------
+ * A receding-horizon loop whose state never leaves the GPU: advance the stored nominal by `shift` control periods, warm-start it from the
+ * new state and run a fixed budget of iterations, then read the next controls into device memory.  Every call is enqueued on the handle's
+ * stream and returns without waiting for it: a caller whose x0 comes from, or whose controls go to, work on another stream (a simulator in
+ * torch) hands that stream to ilqr_desc.stream / ilqr_set_stream, and stream order does the rest.
+ *
+ * What the shift does to every trajectory's stored nominal (s = shift, T transitions; knots t < T - s of us / k / K and t <= T - s of xs
+ * take the values s knots later):
+ *     array   tail knots, ILQR_TAIL_HOLD    tail knots, ILQR_TAIL_ZERO
+ *     us      us[T-1]                       0
+ *     K       K[T-1]                        0
+ *     k       0                             0          (the next backward pass's box-QP warm start)
+ *     xs      xs[T]                         xs[T]
+ * so that HOLD keeps the final gain around the final state.  Cost, lambda, status and iteration counts are not touched; an accepted candidate
+ * still waiting to be copied into xs / us is copied first, and the candidate buffers belong to nobody afterwards (ilqr_get_candidate:
+ * ILQR_ERR_STATE). */
+enum ilqr_tail { ILQR_TAIL_HOLD = 0, ILQR_TAIL_ZERO = 1 };
+/* Shift every trajectory's stored nominal (xs, us, k, K) by `shift` knots, 0 <= shift < T, in place (shift = 0 changes nothing).  Any handle
+ * that stores a trajectory, host-evaluated models included.  ILQR_ERR_STATE before ilqr_init_traj / ilqr_set_trajectory. */
+int ilqr_shift_horizon(ilqr_batch* h, int shift, int tail);
+/* One receding-horizon step: ilqr_shift_horizon(shift, tail), then x0, then the warm start's rollout (u = us[t] + K[t](x - xs[t])) written
+ * into xs / us, then a new outer loop (status, iteration counts and flgChange restart; lambda and dlambda persist), then n_iters iterations
+ * (ilqr_iterate; n_iters = 0 stops after the warm start's rollout).  It leaves bit for bit the state that shifting on the host,
+ * ilqr_set_trajectory + ilqr_set_gains and ilqr_warm_start(x0) on a handle with params.max_iter = n_iters leave (status and iteration
+ * counts too when this handle's own max_iter is n_iters), with no host synchronisation: no lambda round trip, no wait per chunk, no
+ * compaction of finished trajectories.  Exactly one of x0 (host, [B][nx] double) and x0_device (device memory of this handle's device,
+ * [B][nx] double) is non-NULL.  A host x0 is the call's one host-to-device transfer: from page-locked memory (ilqr_host_register) it is
+ * asynchronous -- the array must then stay unchanged until the stream has passed the step -- from pageable memory the runtime may wait
+ * to stage it.  ILQR_ERR_UNSUPPORTED for ILQR_MODEL_HOST (its rollouts are the caller's, as for ilqr_warm_start). */
+int ilqr_mpc_step(ilqr_batch* h, const double* x0, const void* x0_device, int shift, int tail, int n_iters);
+/* us[:, t0 : t0 + n_knots, :] as canonical double [B][n_knots][nu] into caller-owned device memory, on the handle's stream (the controls to
+ * apply: t0 = 0, n_knots = the shift of the next step).  The window lies inside [0, T) and holds at least one knot. */
+int ilqr_copy_controls_to_device(ilqr_batch* h, int t0, int n_knots, void* u_device);
 
 /* ---- single stages (teacher-forced parity tests, host-model fallback) --------------------- */
 /* STEP 1, src/ilqr_core.cpp:115-120 = src/derivatives.cpp:15-144 over t = 0..T, all trajectories */

@@ -376,6 +376,28 @@ class BatchILQR {
   void copy_trajectory_to_device(void* xs_device, void* us_device) { check(ilqr_copy_trajectory_to_device(h_, xs_device, us_device), "ilqr_copy_trajectory_to_device"); }
   void copy_gains_to_device(void* k_device, void* K_device) { check(ilqr_copy_gains_to_device(h_, k_device, K_device), "ilqr_copy_gains_to_device"); }
   void synchronize() { check(ilqr_synchronize(h_), "ilqr_synchronize"); }
+  // ---- model-predictive control on the device (ABI 6) ----
+  // Shift the stored nominal by `shift` knots (tail: ILQR_TAIL_HOLD / ILQR_TAIL_ZERO, include/ilqr_amd.h), warm-start from x0, run `iters`
+  // iterations -- all enqueued on the handle's stream, none of it waited for.  A host-evaluated model keeps host mirrors of its nominal that
+  // these calls would leave behind: the engine refuses them.
+  void shift_horizon(int shift, int tail = ILQR_TAIL_HOLD) {
+    if (host_) throw std::logic_error("shift_horizon(): a host-evaluated model's nominal lives on the host as well; the device-side shift is for models with a device twin");
+    check(ilqr_shift_horizon(h_, shift, tail), "ilqr_shift_horizon");
+  }
+  void mpc_step(const std::vector<double>& x0, int shift = 1, int iters = 1, int tail = ILQR_TAIL_HOLD) {
+    require(x0.size() == (size_t)B_ * n_, "mpc_step: x0 [B][nx]");
+    if (host_) throw std::logic_error("mpc_step(): a host-evaluated model rolls out on the host; receding-horizon steps need a device twin");
+    check(ilqr_mpc_step(h_, x0.data(), nullptr, shift, tail, iters), "ilqr_mpc_step");
+  }
+  // x0_device: [B][nx] double in device memory of the handle's device
+  void mpc_step(const void* x0_device, int shift = 1, int iters = 1, int tail = ILQR_TAIL_HOLD) {
+    if (host_) throw std::logic_error("mpc_step(): a host-evaluated model rolls out on the host; receding-horizon steps need a device twin");
+    check(ilqr_mpc_step(h_, nullptr, x0_device, shift, tail, iters), "ilqr_mpc_step");
+  }
+  // us[:, t0 : t0 + n_knots, :] as double [B][n_knots][nu] into caller-owned device memory
+  void copy_controls_to_device(int t0, int n_knots, void* u_device) {
+    check(ilqr_copy_controls_to_device(h_, t0, n_knots, u_device), "ilqr_copy_controls_to_device");
+  }
   std::vector<int> status() {
     std::vector<int> s(B_);
     check(ilqr_get_status(h_, s.data(), nullptr, nullptr), "ilqr_get_status");
