@@ -172,6 +172,15 @@ class BatchILQR:
     def line_search(self):
         self._check(self.lib.ilqr_line_search(self.h))
 
+    def accept_candidates(self, cost_c):
+        """Host-evaluated models: STEP 3/4 on the caller's candidate costs cost_c [B][11]; returns the accepted alpha index per
+        trajectory (-1 = none; the caller then stores that rollout with set_trajectory)."""
+        cost_c = _c(cost_c)
+        assert cost_c.shape == (self.B, len(ALPHAS))
+        acc = np.zeros(self.B, dtype=np.int32)
+        self._check(self.lib.ilqr_accept_candidates(self.h, _p(cost_c), acc.ctypes.data_as(_ip)))
+        return acc
+
     def reset_state(self, warm=False):
         """warm=False: the non-rollout part of init_traj; warm=True: a new outer loop on the stored
         solution (status / iteration count / flgChange restart, lambda and gains persist)."""

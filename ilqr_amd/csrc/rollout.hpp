@@ -26,7 +26,13 @@ __device__ __forceinline__ void accept_one(const View& v, const SolverParams& sp
         const double alpha = kAlpha[a];
         new_cost = cost_of(a);
         dcost = cost_s - new_cost;                          // :199
-        const double expected = -alpha * (dV0 + alpha * dV1);  // :200
+        double expected;
+        {
+          // two roundings, as the reference computes it (x86-64 baseline, no FMA): contracted to one v_fma_f64, a z within a rounding
+          // of z_min is decided the other way (tests/test_gpu_accept_schedule.py, contraction rows)
+#pragma clang fp contract(off)
+          expected = -alpha * (dV0 + alpha * dV1);  // :200
+        }
         double z;
         if (expected > 0)
           z = dcost / expected;

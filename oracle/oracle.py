@@ -119,6 +119,8 @@ def build(force=False):
 
 _libs = {}
 _fixes = 0
+PARAM_NAMES = ("tol_fun", "tol_grad", "lambda_factor", "lambda_max", "lambda_min", "z_min")
+_params = None  # set_params' defaults, filled in below it
 
 
 def lib():
@@ -133,6 +135,7 @@ def lib():
             getattr(L, name).restype = _ac()
         L.orc_quad_cost.restype = _rc()
         L.orc_set_fixes(int(_fixes))  # (a flavour loaded after set_fixes -- the fp80 yardstick, lazily -- carries the same switch)
+        L.orc_set_params(*[C.c_double(_params[k]) for k in PARAM_NAMES])  # (and the same tunables, set_params)
         _libs[_cur] = L
     return _libs[_cur]
 
@@ -179,8 +182,29 @@ def set_fixes(bits=0):
 
 
 def set_params(tol_fun=1e-6, tol_grad=1e-6, lambda_factor=1.6, lambda_max=1e11, lambda_min=1e-8, z_min=0.0):
-    """Solver tunables of include/ilqr.h:14-24 (process-wide in the oracle); no arguments = the reference's."""
-    lib().orc_set_params(*[C.c_double(v) for v in (tol_fun, tol_grad, lambda_factor, lambda_max, lambda_min, z_min)])
+    """Solver tunables of include/ilqr.h:14-24 (process-wide in the oracle); no arguments = the reference's.  Like set_fixes they
+    reach every flavour: those loaded already and those loaded later (the float twin, the f80 yardstick)."""
+    global _params
+    _params = dict(tol_fun=float(tol_fun), tol_grad=float(tol_grad), lambda_factor=float(lambda_factor), lambda_max=float(lambda_max),
+                   lambda_min=float(lambda_min), z_min=float(z_min))
+    for name in list(_libs) or ["f64"]:
+        with flavour(name):
+            lib().orc_set_params(*[C.c_double(_params[k]) for k in PARAM_NAMES])
+
+
+def get_params():
+    """The tunables set_params last set (a copy)."""
+    return dict(_params)
+
+
+DEFAULT_PARAMS = {k: v.default for k, v in __import__("inspect").signature(set_params).parameters.items()}  # the reference's
+_params = dict(DEFAULT_PARAMS)
+
+
+def forget(name):
+    """Drop this module's binding of a flavour: the next call in it binds the library again and hands it the current switches and
+    tunables, as for a flavour used for the first time (the library itself stays loaded)."""
+    _libs.pop(name, None)
 
 
 def _pi(a):

@@ -207,11 +207,12 @@ def check_backward(oracle, om, us, derivs, k_prev, lam, k, K, dV, div, ro, max_t
     return dict(good=conv & good, ties=ties, conditioned=conditioned, cond_over10=over10)
 
 
-def oracle_init_state(oracle, om, x0, u0, dt):
+def oracle_init_state(oracle, om, x0, u0, dt, lam0=1.0, dlam0=1.0):
+    """init_traj's state (ilqr_core.cpp:11-56); lambda and dlambda start at ilqr_params.lambda_init / dlambda_init"""
     xs, us, cost = oracle.batch_rollout(om, x0, u0, dt)
     B, T = u0.shape[:2]
     return dict(xs=xs, us=us, k=np.zeros((B, T, om.nu)), K=np.zeros((B, T, om.nu, om.nx)), cost=cost,
-                lam=np.ones(B), dlam=np.ones(B))
+                lam=np.full(B, float(lam0)), dlam=np.full(B, float(dlam0)))
 
 
 def load_state(g, x0, st):
@@ -237,15 +238,15 @@ def walk_iterations(oracle, om, g, x0, u0, dt, n_iters, fixed_work=False, precis
     given the device's state before every iteration -- i.e. every step of a free-running solve is checked.
     Returns dict(checked, ties_backward, ties_search, ties_stop, worst_*) and raises AssertionError on the
     first unexplained deviation."""
-    p = dict(tol_fun=1e-6, lambda_max=1e11, tol_grad=1e-6)
-    p.update(params or {})
+    p = dict(tol_fun=1e-6, lambda_max=1e11, tol_grad=1e-6, z_min=0.0, lambda_init=1.0, dlambda_init=1.0)
+    p.update(params or {})  # (the handle's ilqr_params; the oracle's own tunables are the caller's: oracle.set_params)
     prec = PRECISIONS[precision]
     tol, gtol = prec["tol"], prec["gtol"]
     B, T = u0.shape[:2]
     aux = None
     if drive == "oracle":
         with oracle.flavour(prec["twin"]):
-            st = oracle_init_state(oracle, _tw(om, prec["twin"]), x0, u0, dt)
+            st = oracle_init_state(oracle, _tw(om, prec["twin"]), x0, u0, dt, p["lambda_init"], p["dlambda_init"])
         st = {kk: _f64(v) for kk, v in st.items()}
     else:
         g.init_traj(x0, u0)
@@ -355,7 +356,11 @@ def walk_iterations(oracle, om, g, x0, u0, dt, n_iters, fixed_work=False, precis
                 cc = _candidate_costs(aux, x0, st, b)
                 dcost = st["cost"][b] - cc
                 a_lo = min(x for x in (gs["alpha"][b], nx["alpha"][b]) if x >= 0)
-                # the earlier-accepted alpha (or every alpha when one side found none) has a cost change of rounding size
+                # the earlier-accepted alpha (or every alpha when one side found none) has a cost change within rounding of the
+                # acceptance threshold z_min * expected (:200-206; 0 at the reference's z_min = 0, and in the sgn branch, expected <= 0)
+                from oracle.oracle import ALPHAS
+                ex = -ALPHAS * (nx["dV"][b][0] + ALPHAS * nx["dV"][b][1])
+                dcost = dcost - np.where(ex > 0, p["z_min"] * ex, 0.0)
                 cand = dcost[a_lo:] if min(gs["alpha"][b], nx["alpha"][b]) < 0 else dcost[a_lo:a_lo + 1]
                 if precision == "f32" and not np.any(np.abs(cand) <= prec["tie_rel"] * abs(st["cost"][b])):
                     # Not a tie of rounding size -- but are this trajectory's FLOAT rollouts good for a decision at all?  The same gains
