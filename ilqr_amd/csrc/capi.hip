@@ -85,33 +85,19 @@ void ilqr_destroy(ilqr_batch* h) {
   delete h;
 }
 
-static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(ILQR_ERR_NO_DEVICE, "no HIP device visible: libilqr_amd has no CPU path");
-  if (d->device < 0 || d->device >= ndev) return fail(ILQR_ERR_NO_DEVICE, "device %d out of range (%d visible)", d->device, ndev);
-  HIPCHK(hipSetDevice(d->device));
-  HIPCHK(hipDeviceGetAttribute(&h->num_cus, hipDeviceAttributeMultiprocessorCount, d->device));
-  {
-    int khz = 0;
-    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, d->device) == hipSuccess && khz > 0) h->wall_clock_khz = khz;
-  }
-  // route choices come with the descriptor (ilqr_desc.route, include/ilqr_amd.h): the library reads no environment
-  h->lq_wide = d->model == ILQR_MODEL_LQ && d->nu > WM;  // the LQ twin beyond 16 controls: LqModelW on the generic kernels
-  h->route.full_records = (d->route & ILQR_ROUTE_FULL_RECORDS) != 0;
-  h->route.no_compaction = (d->route & ILQR_ROUTE_NO_COMPACTION) != 0;
-  h->route.wide_occ = (d->route & ILQR_ROUTE_WIDE_ONE_PER_CU) ? 1 : (d->route & ILQR_ROUTE_WIDE_TWO_PER_CU) ? 2 : 0;
-  if (d->assume_cus > 0) h->num_cus = d->assume_cus;
-  h->aos = generic_layout(d->model, d->route, kUserTiled, kUserSmall);
-  h->device = d->device;
-  if (d->stream) {
-    h->stream = (hipStream_t)d->stream;
-  } else {
-    HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    h->own_stream = true;
-  }
-  h->model = d->model;
-  h->dtype = d->dtype;
+// Every refusal of ilqr_create, on the descriptor and this build's user twin alone: no HIP call, so before any device is looked for.
+// When several apply, the first one below wins.
+static int check_desc(const ilqr_desc* d) {
+  // (ABI 6 added entry points only: ilqr_desc is ABI 5's, and a caller built against ABI 5 keeps working)
+  REQUIRE(d->abi_version == ILQR_AMD_ABI_VERSION || d->abi_version == 5, "ABI version %d, library is %d (accepts 5 and %d)", d->abi_version,
+          ILQR_AMD_ABI_VERSION, ILQR_AMD_ABI_VERSION);
+  REQUIRE(d->B >= 1 && d->T >= 1 && d->nx >= 1 && d->nu >= 1, "B, T, nx, nu must be positive");
+  REQUIRE(d->nx <= MAXN && d->nu <= kMaxControls, "nx <= %d and nu <= %d", MAXN, kMaxControls);
+  REQUIRE(d->dt > 0, "dt must be positive");
+  if (d->route & 128)  // (ILQR_ROUTE_BACKWARD_LDS of ABI <= 4)
+    return fail(ILQR_ERR_UNSUPPORTED, "route bit 128 (round 1's LDS kernel k_backward_w) was retired in ABI 5: ILQR_ROUTE_BACKWARD_W2 gives the same bits");
+  if ((d->route & ILQR_ROUTE_WIDE_TWO_PER_CU) && d->nu == 2 && d->nx == 4)
+    return fail(ILQR_ERR_UNSUPPORTED, "ILQR_ROUTE_WIDE_TWO_PER_CU: the m = 2 wide tiles (k_solve_wide2) run one tile per CU (four wavefronts at <= 512 registers); the bit applies to k_solve_wide (m = 1)");
   if (d->dtype != ILQR_DTYPE_F64 && d->dtype != ILQR_DTYPE_F32) return fail(ILQR_ERR_INVALID, "dtype %d: ILQR_DTYPE_F64 or ILQR_DTYPE_F32", d->dtype);
   if (d->nu > WM) {  // 16 < nu <= 32: the generic backward pass with two control tiles (k_backward_w3, MT = 2); what is not widened says so
     const char* what = (d->dtype == ILQR_DTYPE_F32) ? "fp32" : (d->route & ILQR_ROUTE_BACKWARD_W2) ? "ILQR_ROUTE_BACKWARD_W2" : (d->route & ILQR_ROUTE_LQ_DENSE_FD) ? "ILQR_ROUTE_LQ_DENSE_FD"
@@ -122,7 +108,8 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
     return fail(ILQR_ERR_UNSUPPORTED, "ILQR_ROUTE_TWO_CONTROL_TILES and ILQR_ROUTE_BACKWARD_W2 name two different backward kernels");
   if ((d->route & ILQR_ROUTE_TWO_CONTROL_TILES) && (d->flags & ILQR_FLAG_REGULARIZE_VXX))
     return fail(ILQR_ERR_UNSUPPORTED, "ILQR_FLAG_REGULARIZE_VXX is implemented in k_backward_w3 (at most 16 controls): drop ILQR_ROUTE_TWO_CONTROL_TILES");
-  if (d->dtype == ILQR_DTYPE_F32 && h->aos) {  // fp32 on the generic path: the device models, k_backward_w3 with one control tile
+  const bool aos = generic_layout(d->model, d->route, kUserTiled, kUserSmall);
+  if (d->dtype == ILQR_DTYPE_F32 && aos) {  // fp32 on the generic path: the device models, k_backward_w3 with one control tile
     if (d->model == ILQR_MODEL_HOST)
       return fail(ILQR_ERR_UNSUPPORTED, "fp32 is not available for ILQR_MODEL_HOST: the caller evaluates the model and owns its records (fp64)");
     if (d->route & ILQR_ROUTE_BACKWARD_W2)
@@ -130,22 +117,79 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
     if (d->route & ILQR_ROUTE_TWO_CONTROL_TILES)
       return fail(ILQR_ERR_UNSUPPORTED, "fp32 is not available on ILQR_ROUTE_TWO_CONTROL_TILES: fp32 handles run k_backward_w3 with one control tile");
   }
-  h->nx = d->nx;
-  h->nu = d->nu;
-  h->T = d->T;
-  h->B = d->B;
-  h->dt = d->dt;
-  h->flags = d->flags;
+  if (d->model == ILQR_MODEL_ACROBOT) {
+    REQUIRE(d->nx == 4 && d->nu == 1, "acrobot is nx=4 nu=1 (include/acrobot.h:27-28), got %d/%d", d->nx, d->nu);
+  } else if (d->model == ILQR_MODEL_DOUBLE_INTEGRATOR) {
+    REQUIRE(d->nx == 4 && d->nu == 2, "double integrator is nx=4 nu=2 (include/double_integrator.h:16-17), got %d/%d", d->nx, d->nu);
+#ifdef ILQR_HAVE_USER_MODEL
+  } else if (d->model == ILQR_MODEL_USER) {
+    using UM = UserModelT<double>;
+    REQUIRE(d->nx == UM::NX && d->nu == UM::NU, "this build's user model is nx=%d nu=%d, got %d/%d", UM::NX, UM::NU, d->nx, d->nu);
+    REQUIRE(d->u_min && d->u_max, "ILQR_MODEL_USER needs u_min/u_max (Model::u_min/u_max, include/model.h:17)");
+    REQUIRE(!(d->flags & ILQR_FLAG_ANALYTIC_DERIVATIVES) || has_analytic_record<UM>::value, "this user model has no analytic_record()");
+    // not a tiled shape -- or a small one asked to take the generic route: the generic kernels (fp64), trajectory-contiguous layout like the LQ model's
+    // (a small twin asked onto the generic kernels -- ILQR_ROUTE_WAVE_PER_TRAJECTORY -- is the fp64 cross-check of its tiled kernels)
+    if (aos && kUserSmall) REQUIRE(d->dtype == ILQR_DTYPE_F64, "ILQR_ROUTE_WAVE_PER_TRAJECTORY on a small twin is the fp64 cross-check of its tiled kernels: fp64 only");
+    REQUIRE(d->n_user_params >= 0 && (d->n_user_params == 0 || d->user_params), "ILQR_MODEL_USER: n_user_params = %d with user_params = %p", d->n_user_params, (const void*)d->user_params);
+#endif
+  } else if (d->model == ILQR_MODEL_HOST || d->model == ILQR_MODEL_LQ) {
+    // Generic dimensions: trajectory-contiguous layout, one wavefront per trajectory in the backward
+    // pass.  Host-evaluated models receive their derivatives through ilqr_set_derivatives; the LQ
+    // model has a device twin (generic.hpp) and runs end to end.
+    REQUIRE(d->nx <= WN && d->nu <= WMW, "generic kernels: nx <= %d, nu <= %d", WN, WMW);
+    REQUIRE(d->u_min && d->u_max, "generic handles need u_min/u_max (Model::u_min/u_max, include/model.h:17)");
+    if (d->model == ILQR_MODEL_LQ)
+      REQUIRE(d->lq_A && d->lq_B && d->lq_Q && d->lq_R && d->lq_Qf, "ILQR_MODEL_LQ needs lq_A, lq_B, lq_Q, lq_R, lq_Qf");
+  } else {
+    return fail(ILQR_ERR_UNSUPPORTED, "model id %d is not available in this build", d->model);
+  }
+  // generic handles: ILQR_FLAG_REFERENCE_FIXES -- models with a device twin: their rollouts clamp, their box-QP reports a failed factorisation; the
+  // host-evaluated route: the box-QP likewise, the rollouts belong to the caller (the facade clamps).  ILQR_FLAG_REGULARIZE_VXX is the backward pass's alone (k_backward_w3<.., REGV>), on any model
+  if ((d->flags & ILQR_FLAG_REGULARIZE_VXX) && aos && (d->route & ILQR_ROUTE_BACKWARD_W2))
+    return fail(ILQR_ERR_UNSUPPORTED, "ILQR_FLAG_REGULARIZE_VXX on the generic path is implemented in k_backward_w3: drop ILQR_ROUTE_BACKWARD_W2");
+  // (a host-evaluated model under ILQR_FLAG_REFERENCE_FIXES: part (2), the failed factorisation that ends the box-QP, is the device's -- k_backward_w3 /
+  //  k_backward_w2 honour sp.fixes & 2 --; part (1), the clamped rollout, belongs to whoever rolls out: the C++ facade's host_forward does it)
+  return 0;
+}
+
+static void copy_desc(const ilqr_desc* d, ilqr_batch* h) {
+  // route choices come with the descriptor (ilqr_desc.route, include/ilqr_amd.h): the library reads no environment
+  h->lq_wide = d->model == ILQR_MODEL_LQ && d->nu > WM;  // the LQ twin beyond 16 controls: LqModelW on the generic kernels
+  h->route.full_records = (d->route & ILQR_ROUTE_FULL_RECORDS) != 0;
+  h->route.no_compaction = (d->route & ILQR_ROUTE_NO_COMPACTION) != 0;
+  h->route.wide_occ = (d->route & ILQR_ROUTE_WIDE_ONE_PER_CU) ? 1 : (d->route & ILQR_ROUTE_WIDE_TWO_PER_CU) ? 2 : 0;
+  h->aos = generic_layout(d->model, d->route, kUserTiled, kUserSmall);
+  h->model = d->model; h->dtype = d->dtype; h->flags = d->flags;
+  h->nx = d->nx; h->nu = d->nu; h->T = d->T; h->B = d->B; h->dt = d->dt;
   h->Bp = ((d->B + 63) / 64) * 64;
   h->ntiles = h->Bp / TW;
   if (d->params)
     h->params = *d->params;
   else
     ilqr_default_params(&h->params);
+}
 
-  // model parameters (the constructor bodies of acrobot.h:14-40, double_integrator.h:14-27)
+static int open_device(const ilqr_desc* d, ilqr_batch* h) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(ILQR_ERR_NO_DEVICE, "no HIP device visible: libilqr_amd has no CPU path");
+  if (d->device < 0 || d->device >= ndev) return fail(ILQR_ERR_NO_DEVICE, "device %d out of range (%d visible)", d->device, ndev);
+  HIPCHK(hipSetDevice(d->device));
+  h->device = d->device;
+  HIPCHK(hipDeviceGetAttribute(&h->num_cus, hipDeviceAttributeMultiprocessorCount, d->device));
+  if (d->assume_cus > 0) h->num_cus = d->assume_cus;
+  int khz = 0;
+  if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, d->device) == hipSuccess && khz > 0) h->wall_clock_khz = khz;
+  h->stream = (hipStream_t)d->stream;
+  h->own_stream = !d->stream;
+  if (h->own_stream) HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  return 0;
+}
+
+// the models' parameters (the constructor bodies of acrobot.h:14-40, double_integrator.h:14-27); an fp32 handle's float models, and
+// their parameters' float values in the double twins
+static void set_model_params(const ilqr_desc* d, ilqr_batch* h) {
   if (d->model == ILQR_MODEL_ACROBOT) {
-    REQUIRE(d->nx == 4 && d->nu == 1, "acrobot is nx=4 nu=1 (include/acrobot.h:27-28), got %d/%d", d->nx, d->nu);
     AcrobotModel& m = h->acrobot;
     m.goal[0] = 3.1415;
     m.goal[1] = m.goal[2] = m.goal[3] = 0;
@@ -158,7 +202,6 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
       m.u_max[0] = (double)(f.u_max[0] = (float)m.u_max[0]);
     }
   } else if (d->model == ILQR_MODEL_DOUBLE_INTEGRATOR) {
-    REQUIRE(d->nx == 4 && d->nu == 2, "double integrator is nx=4 nu=2 (include/double_integrator.h:16-17), got %d/%d", d->nx, d->nu);
     DoubleIntegratorModel& m = h->dint;
     const double g0[4] = {1.0, 0.5, 0.0, 0.0};
     for (int i = 0; i < 4; i++) m.goal[i] = d->goal ? d->goal[i] : g0[i];
@@ -177,13 +220,6 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
 #ifdef ILQR_HAVE_USER_MODEL
   } else if (d->model == ILQR_MODEL_USER) {
     using UM = UserModelT<double>;
-    REQUIRE(d->nx == UM::NX && d->nu == UM::NU, "this build's user model is nx=%d nu=%d, got %d/%d", UM::NX, UM::NU, d->nx, d->nu);
-    REQUIRE(d->u_min && d->u_max, "ILQR_MODEL_USER needs u_min/u_max (Model::u_min/u_max, include/model.h:17)");
-    REQUIRE(!(d->flags & ILQR_FLAG_ANALYTIC_DERIVATIVES) || has_analytic_record<UM>::value, "this user model has no analytic_record()");
-    // not a tiled shape -- or a small one asked to take the generic route: the generic kernels (fp64), trajectory-contiguous layout like the LQ model's
-    // (a small twin asked onto the generic kernels -- ILQR_ROUTE_WAVE_PER_TRAJECTORY -- is the fp64 cross-check of its tiled kernels)
-    if (h->aos && kUserSmall) REQUIRE(d->dtype == ILQR_DTYPE_F64, "ILQR_ROUTE_WAVE_PER_TRAJECTORY on a small twin is the fp64 cross-check of its tiled kernels: fp64 only");
-    REQUIRE(d->n_user_params >= 0 && (d->n_user_params == 0 || d->user_params), "ILQR_MODEL_USER: n_user_params = %d with user_params = %p", d->n_user_params, (const void*)d->user_params);
     h->user_f.set_params(d->user_params, d->n_user_params);
     if (h->dtype == ILQR_DTYPE_F32) {  // the twin the finite differences are taken in: built from the parameters' FLOAT values, like the shipped models'
       std::vector<double> p32(d->user_params, d->user_params + (d->user_params ? d->n_user_params : 0));
@@ -202,26 +238,16 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
     static_cast<UM&>(h->user_g) = h->user;  // the generic kernels' copy: parameters AND limits (a model's cost may read its own u_min / u_max)
     static_cast<UserModelT<float>&>(h->user_gf) = h->user_f;  // ... and on an fp32 handle the float twin its rollouts integrate
 #endif
-  } else if (d->model == ILQR_MODEL_HOST || d->model == ILQR_MODEL_LQ) {
-    // Generic dimensions: trajectory-contiguous layout, one wavefront per trajectory in the backward
-    // pass.  Host-evaluated models receive their derivatives through ilqr_set_derivatives; the LQ
-    // model has a device twin (generic.hpp) and runs end to end.
-    REQUIRE(d->nx <= WN && d->nu <= WMW, "generic kernels: nx <= %d, nu <= %d", WN, WMW);
-    REQUIRE(d->u_min && d->u_max, "generic handles need u_min/u_max (Model::u_min/u_max, include/model.h:17)");
-    if (d->model == ILQR_MODEL_LQ)
-      REQUIRE(d->lq_A && d->lq_B && d->lq_Q && d->lq_R && d->lq_Qf, "ILQR_MODEL_LQ needs lq_A, lq_B, lq_Q, lq_R, lq_Qf");
-  } else {
-    return fail(ILQR_ERR_UNSUPPORTED, "model id %d is not available in this build", d->model);
   }
+}
 
+// every device array of the handle, zero-filled on its stream
+static int alloc_arrays(const ilqr_desc* d, ilqr_batch* h) {
   const size_t nt = h->ntiles, T = h->T, T1 = h->T + 1, nx = h->nx, nu = h->nu, REC = rec_of(h), Bp = h->Bp;
   BatchView& v = h->v;
-  v.B = h->B;
-  v.Bp = h->Bp;
-  v.ntiles = h->ntiles;
-  v.T = h->T;
-  v.dt = h->dt;
+  v.B = h->B; v.Bp = h->Bp; v.ntiles = h->ntiles; v.T = h->T; v.dt = h->dt;
   v.analytic = (h->flags & ILQR_FLAG_ANALYTIC_DERIVATIVES) ? 1 : 0;
+  v.D = nullptr;  // on first use (ensure_records): the fused LQ route never needs it
   int rc = 0;
   if (h->aos) {
     const size_t Bn = h->B;
@@ -231,7 +257,6 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
     rc |= dev_alloc_real(h, &v.us, Bn * T * nu);
     rc |= dev_alloc_real(h, &v.kff, Bn * T * nu);
     rc |= dev_alloc_real(h, &v.Kfb, Bn * T * nu * nx);
-    v.D = nullptr;  // on first use (ensure_records): the fused LQ route never needs it
     // (double on every handle; GN zeros behind the two records: the knot k_analytic_lq forms knot T's unused cx from at creation)
     rc |= dev_alloc(h, &h->const_rec, 2 * REC + GN);
     rc |= dev_alloc(h, &h->d_umin, nu);
@@ -252,141 +277,100 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
         (void)hipGetLastError();  // (clears the allocation error)
       }
     }
-    rc |= dev_alloc(h, &v.cost_c, (size_t)NALPHA * Bp);  // the 11 candidate costs (device or caller-evaluated)
-    if (d->model == ILQR_MODEL_LQ) {
-      // zero-padded copies of the model matrices at the kernels' maximum dimensions (B, R: GM columns, or GMW for the wide twin)
-      double* pad = nullptr;
-      const size_t GMC = h->lq_wide ? GMW : GM;
-      const size_t nA = GN * GN, nB = GN * GMC, nR = GMC * GMC, tot = 3 * nA + nB + nR;
-      rc |= dev_alloc(h, &pad, tot);
-      if (!rc) {
-        std::vector<double> hp(tot, 0.0);
-        double *pA = hp.data(), *pB = pA + nA, *pQ = pB + nB, *pR = pQ + nA, *pQf = pR + nR;
-        for (size_t i = 0; i < nx; i++) {
-          for (size_t j = 0; j < nx; j++) {
-            pA[i * GN + j] = d->lq_A[i * nx + j];
-            pQ[i * GN + j] = d->lq_Q[i * nx + j];
-            pQf[i * GN + j] = d->lq_Qf[i * nx + j];
-          }
-          for (size_t j = 0; j < nu; j++) pB[i * GMC + j] = d->lq_B[i * nu + j];
-        }
-        for (size_t i = 0; i < nu; i++)
-          for (size_t j = 0; j < nu; j++) pR[i * GMC + j] = d->lq_R[i * nu + j];
-        // fp32 handle: the float matrices its rollouts integrate, and their values in the double twin (finite differences, exact
-        // derivatives, backward pass), as create_impl does for the other models' parameters
-        std::vector<float> hf;
-        float* padf = nullptr;
-        if (h->dtype == ILQR_DTYPE_F32) {
-          hf.resize(tot);
-          for (size_t e = 0; e < tot; e++) hp[e] = (double)(hf[e] = (float)hp[e]);
-          rc |= dev_alloc(h, &padf, tot);
-        }
-        // on the handle's stream, behind dev_alloc's zero fill of the same buffer (a copy on the null
-        // stream could be overtaken by it: the stream is non-blocking); hp must outlive the copy
-        if (hipMemcpyAsync(pad, hp.data(), tot * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-            (padf && hipMemcpyAsync(padf, hf.data(), tot * sizeof(float), hipMemcpyHostToDevice, h->stream) != hipSuccess) ||
-            hipStreamSynchronize(h->stream) != hipSuccess)
-          rc = 1;
-        if (padf) {
-          h->lq_f.nx = (int)nx;
-          h->lq_f.nu = (int)nu;
-          h->lq_f.A = padf;
-          h->lq_f.Bm = padf + nA;
-          h->lq_f.Q = padf + nA + nB;
-          h->lq_f.R = padf + 2 * nA + nB;
-          h->lq_f.Qf = padf + 2 * nA + nB + nR;
-          h->lq_f.umin = h->d_umin;
-          h->lq_f.umax = h->d_umax;
-        }
-        h->lq.nx = (int)nx;
-        h->lq.nu = (int)nu;
-        h->lq.A = pad;
-        h->lq.Bm = pad + nA;
-        h->lq.Q = pad + nA + nB;
-        h->lq.R = pad + 2 * nA + nB;
-        h->lq.Qf = pad + 2 * nA + nB + nR;
-        h->lq.umin = h->d_umin;
-        h->lq.umax = h->d_umax;
-        h->lq_w.nx = (int)nx;
-        h->lq_w.nu = (int)nu;
-        h->lq_w.A = h->lq.A;
-        h->lq_w.Bm = h->lq.Bm;
-        h->lq_w.Q = h->lq.Q;
-        h->lq_w.R = h->lq.R;
-        h->lq_w.Qf = h->lq.Qf;
-        h->lq_w.umin = h->d_umin;
-        h->lq_w.umax = h->d_umax;
-      }
-    }
-    if (!rc) {
-      // fp32 handle: the limits' float values (the float rollouts clamp to them, the double backward pass boxes with them)
-      std::vector<double> lim(d->u_min, d->u_min + nu);
-      lim.insert(lim.end(), d->u_max, d->u_max + nu);
-      if (h->dtype == ILQR_DTYPE_F32)
-        for (double& q : lim) q = (double)(float)q;
-      if (hipMemcpyAsync(h->d_umin, lim.data(), nu * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = 1;
-      if (hipMemcpyAsync(h->d_umax, lim.data() + nu, nu * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = 1;
-      if (hipStreamSynchronize(h->stream) != hipSuccess) rc = 1;  // (lim must outlive the copies)
-    }
   } else {
-  rc |= dev_alloc_real(h, &v.x0, nt * nx * TW);
-  // (+ kRolloutFetchSlack rows: the shared-row rollouts prefetch up to that many steps past T - 1 without clamping the row index -- rollout.hpp --
-  //  which for the last tile is past the array's end; what those loads return is never used)
-  const size_t slack = (size_t)kRolloutFetchSlack * nu * nx * TW;
-  rc |= dev_alloc_real(h, &v.xs, nt * T1 * nx * TW + slack);
-  rc |= dev_alloc_real(h, &v.us, nt * T * nu * TW + slack);
-  rc |= dev_alloc_real(h, &v.kff, nt * T * nu * TW + slack);
-  rc |= dev_alloc_real(h, &v.Kfb, nt * T * nu * nx * TW + slack);
-  v.D = nullptr;  // on first use (ensure_records)
-  v.nch = h->T / CT + 1;
-  // (one plane more than there are alphas: where the rollout lanes without a rollout of their own put their stores, rollout.hpp)
-  // (the matrix-core kernel keeps its candidates in groups of CG controls, a plane row padded to whole chunks past T - 1: rollout.hpp, cand_g_u)
-  rc |= dev_alloc_real(h, &v.cand_u, (size_t)(NALPHA + 1) * nt * (size_t)(cand_groups(T) * CG) * nu * TW);
-  rc |= dev_alloc_real(h, &v.cand_x, (size_t)(NALPHA + 1) * nt * v.nch * nx * TW);
-  rc |= dev_alloc(h, &v.cost_c, (size_t)NALPHA * Bp);
+    rc |= dev_alloc_real(h, &v.x0, nt * nx * TW);
+    // (+ the spare rows the shared-row rollouts prefetch from past T - 1, rollout.hpp)
+    const size_t slack = rollout_fetch_slack_elems(h->nx, h->nu);
+    rc |= dev_alloc_real(h, &v.xs, nt * T1 * nx * TW + slack);
+    rc |= dev_alloc_real(h, &v.us, nt * T * nu * TW + slack);
+    rc |= dev_alloc_real(h, &v.kff, nt * T * nu * TW + slack);
+    rc |= dev_alloc_real(h, &v.Kfb, nt * T * nu * nx * TW + slack);
+    v.nch = h->T / CT + 1;
+    // (one plane more than there are alphas: where the rollout lanes without a rollout of their own put their stores, rollout.hpp)
+    // (the matrix-core kernel keeps its candidates in groups of CG controls, a plane row padded to whole chunks past T - 1: rollout.hpp, cand_g_u)
+    rc |= dev_alloc_real(h, &v.cand_u, (size_t)(NALPHA + 1) * nt * (size_t)(cand_groups(T) * CG) * nu * TW);
+    rc |= dev_alloc_real(h, &v.cand_x, (size_t)(NALPHA + 1) * nt * v.nch * nx * TW);
   }
-  rc |= dev_alloc(h, &v.cost, Bp);
-  rc |= dev_alloc(h, &v.lambda, Bp);
-  rc |= dev_alloc(h, &v.dlambda, Bp);
+  rc |= dev_alloc(h, &v.cost_c, (size_t)NALPHA * Bp);  // the 11 candidate costs (device or caller-evaluated)
+  // the per-trajectory scalars
+  for (double** p : {&v.cost, &v.lambda, &v.dlambda, &v.gnorm}) rc |= dev_alloc(h, p, Bp);
+  for (int** p : {&v.status, &v.iters, &v.flg_change, &v.alpha_idx, &v.diverge, &v.backpass_done, &h->commit_idx}) rc |= dev_alloc(h, p, Bp);
   rc |= dev_alloc(h, &v.dV, 2 * Bp);
-  rc |= dev_alloc(h, &v.gnorm, Bp);
-  rc |= dev_alloc(h, &v.status, Bp);
-  rc |= dev_alloc(h, &v.iters, Bp);
-  rc |= dev_alloc(h, &v.flg_change, Bp);
-  rc |= dev_alloc(h, &v.alpha_idx, Bp);
-  rc |= dev_alloc(h, &v.diverge, Bp);
-  rc |= dev_alloc(h, &v.backpass_done, Bp);
   rc |= dev_alloc(h, &v.n_running, 1);
   rc |= dev_alloc(h, &h->x0_stage, (size_t)h->B * nx);
-  rc |= dev_alloc(h, &h->commit_idx, Bp);
   rc |= dev_alloc(h, &h->phase_ticks, 5 * (size_t)h->ntiles);
-  if (!rc && hipMemsetAsync(h->commit_idx, 0xFF, Bp * sizeof(int), h->stream) != hipSuccess) rc = 1;
   if (rc) return ILQR_ERR_HIP;
+  HIPCHK(hipMemsetAsync(h->commit_idx, 0xFF, Bp * sizeof(int), h->stream));
   sync_float_view(h);
-  h->plan = plan_route({d->model, d->nx, d->nu, d->flags, d->route, h->ntiles, h->num_cus, kUserTiled, kUserSmall, v.cand_x != nullptr, d->dtype});
+  return 0;
+}
 
-  h->sp.max_iter = h->params.max_iter;
-  h->sp.tol_fun = h->params.tol_fun;
-  h->sp.tol_grad = h->params.tol_grad;
-  h->sp.lambda_factor = h->params.lambda_factor;
-  h->sp.lambda_max = h->params.lambda_max;
-  h->sp.lambda_min = h->params.lambda_min;
-  h->sp.z_min = h->params.z_min;
-  h->sp.fixed_work = (h->flags & ILQR_FLAG_FIXED_WORK) ? 1 : 0;
-  h->sp.fixes = ((h->flags & ILQR_FLAG_REFERENCE_FIXES) ? 3 : 0) | ((h->flags & ILQR_FLAG_REGULARIZE_VXX) ? 4 : 0);
-  // generic handles: ILQR_FLAG_REFERENCE_FIXES -- models with a device twin: their rollouts clamp, their box-QP reports a failed factorisation; the
-  // host-evaluated route: the box-QP likewise, the rollouts belong to the caller (the facade clamps).  ILQR_FLAG_REGULARIZE_VXX is the backward pass's alone (k_backward_w3<.., REGV>), on any model
-  if ((h->sp.fixes & 4) && h->aos && (d->route & ILQR_ROUTE_BACKWARD_W2))
-    return fail(ILQR_ERR_UNSUPPORTED, "ILQR_FLAG_REGULARIZE_VXX on the generic path is implemented in k_backward_w3: drop ILQR_ROUTE_BACKWARD_W2");
-  // (a host-evaluated model under ILQR_FLAG_REFERENCE_FIXES: part (2), the failed factorisation that ends the box-QP, is the device's -- k_backward_w3 /
-  //  k_backward_w2 honour sp.fixes & 2 --; part (1), the clamped rollout, belongs to whoever rolls out: the C++ facade's host_forward does it)
+// generic handles: the LQ model's matrices, zero-padded to the kernels' maximum dimensions, and the limits
+static int upload_generic_model(const ilqr_desc* d, ilqr_batch* h) {
+  if (!h->aos) return 0;
+  const size_t nx = h->nx, nu = h->nu;
+  // (hp, hf, lim: alive until the synchronisation below)
+  std::vector<double> hp;
+  std::vector<float> hf;
+  if (d->model == ILQR_MODEL_LQ) {
+    // B and R: GM columns, or GMW for the wide twin
+    const size_t GMC = h->lq_wide ? GMW : GM;
+    const size_t nA = GN * GN, nB = GN * GMC, nR = GMC * GMC, tot = 3 * nA + nB + nR;
+    double* pad = nullptr;
+    if (int rc = dev_alloc(h, &pad, tot)) return rc;
+    hp.assign(tot, 0.0);
+    double *pA = hp.data(), *pB = pA + nA, *pQ = pB + nB, *pR = pQ + nA, *pQf = pR + nR;
+    for (size_t i = 0; i < nx; i++) {
+      for (size_t j = 0; j < nx; j++) {
+        pA[i * GN + j] = d->lq_A[i * nx + j];
+        pQ[i * GN + j] = d->lq_Q[i * nx + j];
+        pQf[i * GN + j] = d->lq_Qf[i * nx + j];
+      }
+      for (size_t j = 0; j < nu; j++) pB[i * GMC + j] = d->lq_B[i * nu + j];
+    }
+    for (size_t i = 0; i < nu; i++)
+      for (size_t j = 0; j < nu; j++) pR[i * GMC + j] = d->lq_R[i * nu + j];
+    // fp32 handle: the float matrices its rollouts integrate, and their values in the double twin (finite differences, exact
+    // derivatives, backward pass), as set_model_params does for the other models' parameters
+    if (h->dtype == ILQR_DTYPE_F32) {
+      float* padf = nullptr;
+      if (int rc = dev_alloc(h, &padf, tot)) return rc;
+      hf.resize(tot);
+      for (size_t e = 0; e < tot; e++) hp[e] = (double)(hf[e] = (float)hp[e]);
+      HIPCHK(hipMemcpyAsync(padf, hf.data(), tot * sizeof(float), hipMemcpyHostToDevice, h->stream));
+      bind_lq(h->lq_f, padf, GMC, h);
+    }
+    // on the handle's stream, behind dev_alloc's zero fill of the same buffer (a copy on the null
+    // stream could be overtaken by it: the stream is non-blocking)
+    HIPCHK(hipMemcpyAsync(pad, hp.data(), tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    bind_lq(h->lq, pad, GMC, h);
+    bind_lq(h->lq_w, pad, GMC, h);
+  }
+  // fp32 handle: the limits' float values (the float rollouts clamp to them, the double backward pass boxes with them)
+  std::vector<double> lim(d->u_min, d->u_min + nu);
+  lim.insert(lim.end(), d->u_max, d->u_max + nu);
+  if (h->dtype == ILQR_DTYPE_F32)
+    for (double& q : lim) q = (double)(float)q;
+  HIPCHK(hipMemcpyAsync(h->d_umin, lim.data(), nu * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->d_umax, lim.data() + nu, nu * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
 
-  hipLaunchKernelGGL(k_reset_state<double>, dim3((h->Bp + 255) / 256), dim3(256), 0, h->stream, h->v, h->params.lambda_init,
-                     h->params.dlambda_init);
+// the kernels of every stage, the solver parameters, and every trajectory's state reset (plus the LQ model's constant records)
+static int plan_and_reset(const ilqr_desc* d, ilqr_batch* h) {
+  h->plan = plan_route({d->model, d->nx, d->nu, d->flags, d->route, h->ntiles, h->num_cus, kUserTiled, kUserSmall, h->v.cand_x != nullptr, d->dtype});
+  SolverParams& sp = h->sp;
+  const ilqr_params& p = h->params;
+  sp.max_iter = p.max_iter; sp.tol_fun = p.tol_fun; sp.tol_grad = p.tol_grad; sp.z_min = p.z_min;
+  sp.lambda_factor = p.lambda_factor; sp.lambda_max = p.lambda_max; sp.lambda_min = p.lambda_min;
+  sp.fixed_work = (h->flags & ILQR_FLAG_FIXED_WORK) ? 1 : 0;
+  sp.fixes = ((h->flags & ILQR_FLAG_REFERENCE_FIXES) ? 3 : 0) | ((h->flags & ILQR_FLAG_REGULARIZE_VXX) ? 4 : 0);
+  hipLaunchKernelGGL(k_reset_state<double>, dim3((h->Bp + 255) / 256), dim3(256), 0, h->stream, h->v, p.lambda_init, p.dlambda_init);
   HIPCHK(hipGetLastError());
   if (h->plan.derivatives == Derivatives::fused_lq) {  // both constant records, once (what = 3), in double on every handle
     BatchView cv = h->v;
-    if (h->dtype == ILQR_DTYPE_F32) cv.xs = h->const_rec + 2 * REC;  // (an fp32 handle's xs holds floats: the zero knot behind the records)
+    if (h->dtype == ILQR_DTYPE_F32) cv.xs = h->const_rec + 2 * rec_of(h);  // (an fp32 handle's xs holds floats: the zero knot behind the records)
     hipLaunchKernelGGL(k_analytic_lq<double>, dim3(1), dim3(64), 0, h->stream, cv, h->lq, 1, 3, h->const_rec, kAnalyticChunk);
     HIPCHK(hipGetLastError());
   }
@@ -394,19 +378,19 @@ static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
   return 0;
 }
 
+static int create_impl(const ilqr_desc* d, ilqr_batch* h) {
+  copy_desc(d, h);
+  if (int rc = open_device(d, h)) return rc;
+  set_model_params(d, h);
+  if (int rc = alloc_arrays(d, h)) return rc;
+  if (int rc = upload_generic_model(d, h)) return rc;
+  return plan_and_reset(d, h);
+}
+
 int ilqr_create(const ilqr_desc* d, ilqr_batch** out) {
   if (!d || !out) return fail(ILQR_ERR_INVALID, "null argument");
   *out = nullptr;
-  // (ABI 6 added entry points only: ilqr_desc is ABI 5's, and a caller built against ABI 5 keeps working)
-  REQUIRE(d->abi_version == ILQR_AMD_ABI_VERSION || d->abi_version == 5, "ABI version %d, library is %d (accepts 5 and %d)", d->abi_version,
-          ILQR_AMD_ABI_VERSION, ILQR_AMD_ABI_VERSION);
-  REQUIRE(d->B >= 1 && d->T >= 1 && d->nx >= 1 && d->nu >= 1, "B, T, nx, nu must be positive");
-  REQUIRE(d->nx <= MAXN && d->nu <= kMaxControls, "nx <= %d and nu <= %d", MAXN, kMaxControls);
-  REQUIRE(d->dt > 0, "dt must be positive");
-  if (d->route & 128)  // (ILQR_ROUTE_BACKWARD_LDS of ABI <= 4)
-    return fail(ILQR_ERR_UNSUPPORTED, "route bit 128 (round 1's LDS kernel k_backward_w) was retired in ABI 5: ILQR_ROUTE_BACKWARD_W2 gives the same bits");
-  if ((d->route & ILQR_ROUTE_WIDE_TWO_PER_CU) && d->nu == 2 && d->nx == 4)
-    return fail(ILQR_ERR_UNSUPPORTED, "ILQR_ROUTE_WIDE_TWO_PER_CU: the m = 2 wide tiles (k_solve_wide2) run one tile per CU (four wavefronts at <= 512 registers); the bit applies to k_solve_wide (m = 1)");
+  if (int rc = check_desc(d)) return rc;
   ilqr_batch* h = new ilqr_batch();
   const int rc = create_impl(d, h);
   if (rc) {

@@ -194,6 +194,14 @@ static int dev_alloc_real(ilqr_batch* h, double** p, size_t n) {
   return 0;
 }
 
+// an LQ model's pointers into a padded buffer [A | B | Q | R | Qf] (A, Q, Qf: GN x GN; B: GN x gm; R: gm x gm) and to the limits
+template <class M, class Real>
+static void bind_lq(M& m, const Real* pad, size_t gm, const ilqr_batch* h) {
+  const size_t nA = (size_t)GN * GN, nB = GN * gm, nR = gm * gm;
+  m.nx = h->nx; m.nu = h->nu; m.umin = h->d_umin; m.umax = h->d_umax;
+  m.A = pad; m.Bm = pad + nA; m.Q = pad + nA + nB; m.R = pad + 2 * nA + nB; m.Qf = pad + 2 * nA + nB + nR;
+}
+
 static int grid_for(size_t n, int block) { return (int)std::min<size_t>((n + block - 1) / block, 65535u * 16u); }
 
 static int no_device_model() {

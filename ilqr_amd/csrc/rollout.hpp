@@ -102,6 +102,8 @@ struct AlphaSet {
 #define ILQR_ROLLOUT_UNCLAMPED_FETCH 1
 #endif
 constexpr int kRolloutFetchSlack = 8;  // >= every prefetch depth PD of the shared-row rollouts
+// spare elements behind xs, us, kff and Kfb (ilqr_create): kRolloutFetchSlack knots of K, the longest knot of the four
+constexpr size_t rollout_fetch_slack_elems(int nx, int nu) { return (size_t)kRolloutFetchSlack * nu * nx * TW; }
 template <class M>
 constexpr int kDeepPrefetch = (M::NU * M::NX + M::NX + 2 * M::NU <= 10) ? 8 : 4;
 
@@ -294,7 +296,7 @@ __device__ __forceinline__ void rollout_tile(const BatchViewT<typename M::real>&
   };
   if constexpr (SHARE && GAINS) {
     static_assert(PD % 2 == 0 || PD == 1, "static ring indices");
-    static_assert(PD <= kRolloutFetchSlack, "the arrays end in kRolloutFetchSlack spare rows");
+    static_assert((size_t)PD * NU * NX * TW <= rollout_fetch_slack_elems(NX, NU), "PD knots past the end");
     constexpr int NROWS = 2 * NU + NU * NX + NX;  // u, k, K, xs
     constexpr int NLD = (NROWS + 3) / 4;          // rows per alpha group
     struct Raw {
@@ -321,9 +323,10 @@ __device__ __forceinline__ void rollout_tile(const BatchViewT<typename M::real>&
       }
     }
     auto fetch = [&](int tt, Raw& d) __attribute__((always_inline)) {
-      // tail (tt >= T): rows that no step consumes.  Not clamped to T - 1: the arrays end in kRolloutFetchSlack spare rows (ilqr_create), and without
+      // tail (tt >= T): rows that no step consumes.  Not clamped to T - 1: the arrays end in rollout_fetch_slack_elems spare elements, and without
       // the clamp the row addresses are plain induction variables -- three pointer increments per step instead of min / multiply / shift / add
-      // (seven instructions of a step's ~145)
+      // (seven instructions of a step's ~145).  Other tiles read the next tile's first knots, which another workgroup may be writing: unsynchronised
+      // on purpose, as nothing uses what these reads return.
 #if !ILQR_ROLLOUT_UNCLAMPED_FETCH
       tt = (tt < T) ? tt : T - 1;
 #endif

@@ -27,6 +27,7 @@
  *     lambda/dlambda, include/ilqr.h:17-18, are per-trajectory state here, reset to (1,1) by
  *     ilqr_init_traj -- i.e. each fresh solve behaves like a fresh reference process).
  *   - There is no CPU fallback: without a HIP device ilqr_create fails with ILQR_ERR_NO_DEVICE.
+ *     A descriptor ilqr_create refuses is refused before any device is looked for, with its own code.
  */
 #ifndef ILQR_AMD_H_
 #define ILQR_AMD_H_
