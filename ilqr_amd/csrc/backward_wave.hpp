@@ -510,19 +510,4 @@ __device__ int w_box_qp(int m, LDS& L, int lane, int& nfR_out ILQR_W2CLOCK_ARG, 
 //  ILQR_ROUTE_BACKWARD_W2; what remains in this file is what the register kernels share: the LDS block of the box-QP, the matrix-core
 //  tile helpers, reductions, and w_box_qp -- boxqp.cpp:26-139 as written.)
 
-// canonical [B][S][len] block  <->  AoS record slot [b][s][off .. off+len)
-template <class real>
-__global__ void k_rec_aos(real* __restrict__ D, double* __restrict__ host_layout, int B, int S, int REC, int off, int len,
-                          int to_record) {
-  const size_t nel = (size_t)B * S * len;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nel; i += (size_t)gridDim.x * blockDim.x) {
-    const int e = (int)(i % len);
-    const size_t bs = i / len;
-    if (to_record)
-      D[bs * REC + off + e] = (real)host_layout[i];
-    else
-      host_layout[i] = (double)D[bs * REC + off + e];
-  }
-}
-
 }  // namespace ilqr

@@ -433,8 +433,8 @@ int ilqr_init_traj(ilqr_batch* h, const double* x0, const double* u0, double* co
   if (!h || !x0 || !u0) return fail(ILQR_ERR_INVALID, "null argument");
   if (host_model(h)) return no_device_model();
   HIPCHK(hipSetDevice(h->device));
-  if (int rc = upload(h, x0, h->v.x0, 1, h->nx)) return rc;
-  if (int rc = upload(h, u0, h->v.us, h->T, h->nu)) return rc;  // us = u_0, ilqr_core.cpp:17
+  if (int rc = upload(h, x0, {h->v.x0, 1, h->nx})) return rc;
+  if (int rc = upload(h, u0, {h->v.us, h->T, h->nu})) return rc;  // us = u_0, ilqr_core.cpp:17
   // ilqr_core.cpp:23-48: zero derivative/gain arrays; statics lambda/dlambda as for a fresh process
   const size_t T = h->T, T1 = h->T + 1;
   if (h->v.D) HIPCHK(hipMemsetAsync(h->v.D, 0, dev_elems(h, T1, rec_of(h)) * elem_size(h), h->stream));
@@ -517,10 +517,11 @@ static int apply_permutation(ilqr_batch* h, const std::vector<int>& perm) {
   HIPCHK(hipMemcpyAsync(h->d_perm, perm.data(), Bp * sizeof(int), hipMemcpyHostToDevice, h->stream));
   auto tiled = [&](void* arr, int S, int E) -> int {
     const size_t n = (size_t)h->ntiles * S * E * TW;
-    if (h->dtype == ILQR_DTYPE_F32)
-      hipLaunchKernelGGL(k_permute_tiled<float>, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const float*)arr, (float*)h->perm_scratch, h->d_perm, h->ntiles, S, E);
-    else
-      hipLaunchKernelGGL(k_permute_tiled<double>, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const double*)arr, (double*)h->perm_scratch, h->d_perm, h->ntiles, S, E);
+    with_real(h, [&](auto r) {
+      using real = decltype(r);
+      hipLaunchKernelGGL(k_permute_tiled<real>, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const real*)arr, (real*)h->perm_scratch, h->d_perm, h->ntiles, S, E);
+      return 0;
+    });
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(arr, h->perm_scratch, n * es, hipMemcpyDeviceToDevice, h->stream));
     return 0;
@@ -634,7 +635,7 @@ int ilqr_warm_start(ilqr_batch* h, const double* x0) {
   if (host_model(h)) return no_device_model();
   if (!h->initialised) return fail(ILQR_ERR_STATE, "warm start needs a previous solve (assert us.size()>0, ilqr_core.cpp:66)");
   HIPCHK(hipSetDevice(h->device));
-  if (int rc = upload(h, x0, h->v.x0, 1, h->nx)) return rc;
+  if (int rc = upload(h, x0, {h->v.x0, 1, h->nx})) return rc;
   // forward_pass(x_0, us) with the stored gains: u = us[t] + K[t](x - xs[t])  (alpha*k term = 0)
   AlphaSet al;
   for (int i = 0; i < NALPHA; i++) al.a[i] = 0.0;
@@ -677,10 +678,10 @@ static int shift_nominal(ilqr_batch* h, int shift, int tail) {
   set.nseg = h->aos ? h->B : h->ntiles;
   set.shift = shift;
   const dim3 grid((unsigned)std::min(set.nseg, 65535), 4), block(256);
-  if (h->dtype == ILQR_DTYPE_F32)
-    hipLaunchKernelGGL(k_shift_horizon<float>, grid, block, 0, h->stream, set);
-  else
-    hipLaunchKernelGGL(k_shift_horizon<double>, grid, block, 0, h->stream, set);
+  with_real(h, [&](auto r) {
+    hipLaunchKernelGGL(k_shift_horizon<decltype(r)>, grid, block, 0, h->stream, set);
+    return 0;
+  });
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -711,26 +712,14 @@ int ilqr_mpc_step(ilqr_batch* h, const double* x0, const void* x0_device, int sh
   if (int rc = shift_nominal(h, shift, tail == ILQR_TAIL_HOLD ? SHIFT_TAIL_HOLD : SHIFT_TAIL_ZERO)) return rc;
   // x0 into the handle's layout: the host array's one transfer goes to a buffer of its own (the shared staging buffer may be reallocated,
   // which waits); a device x0 is read where it lies
-  const size_t n0 = (size_t)h->B * h->nx;
+  const DevArray X0{h->v.x0, 1, h->nx};
   const double* src = (const double*)x0_device;
   if (x0) {
-    double* dst = (h->aos && h->dtype == ILQR_DTYPE_F64) ? h->v.x0 : h->x0_stage;
-    HIPCHK(hipMemcpyAsync(dst, x0, n0 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    double* dst = stored_canonical(h, X0) ? h->v.x0 : h->x0_stage;
+    HIPCHK(hipMemcpyAsync(dst, x0, (size_t)h->B * h->nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
     src = dst;
   }
-  if (h->aos && h->dtype == ILQR_DTYPE_F32) {
-    hipLaunchKernelGGL((k_convert<double, float>), dim3(grid_for(n0, 256)), dim3(256), 0, h->stream, src, (float*)h->v.x0, n0);
-    HIPCHK(hipGetLastError());
-  } else if (h->aos) {
-    if (src != h->v.x0) HIPCHK(hipMemcpyAsync(h->v.x0, src, n0 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  } else {
-    const size_t nt = (size_t)h->ntiles * h->nx * TW;
-    if (h->dtype == ILQR_DTYPE_F32)
-      hipLaunchKernelGGL(k_pack<float>, dim3(grid_for(nt, 256)), dim3(256), 0, h->stream, src, (float*)h->v.x0, h->B, h->ntiles, 1, h->nx);
-    else
-      hipLaunchKernelGGL(k_pack<double>, dim3(grid_for(nt, 256)), dim3(256), 0, h->stream, src, h->v.x0, h->B, h->ntiles, 1, h->nx);
-    HIPCHK(hipGetLastError());
-  }
+  if (int rc = from_canonical(h, src, X0)) return rc;
   // ilqr_warm_start's rollout, kernel for kernel: u = us[t] + K[t](x - xs[t]) (every alpha 0), written into xs / us
   AlphaSet al;
   for (int i = 0; i < NALPHA; i++) al.a[i] = 0.0;
@@ -754,19 +743,7 @@ int ilqr_copy_controls_to_device(ilqr_batch* h, int t0, int n_knots, void* u_dev
   REQUIRE(t0 >= 0 && n_knots >= 1 && t0 + n_knots <= h->T, "control window [%d, %d): inside [0, T = %d), at least one knot", t0, t0 + n_knots, h->T);
   if (!h->initialised) return fail(ILQR_ERR_STATE, "copy_controls_to_device before ilqr_init_traj/ilqr_set_trajectory");
   HIPCHK(hipSetDevice(h->device));
-  const size_t n = (size_t)h->B * n_knots * h->nu;
-  const dim3 grid(grid_for(n, 256)), block(256);
-  double* dst = (double*)u_device;
-  if (h->aos && h->dtype == ILQR_DTYPE_F32)
-    hipLaunchKernelGGL((k_unpack_window<float, false>), grid, block, 0, h->stream, (const float*)h->v.us, dst, h->B, h->T, h->nu, t0, n_knots);
-  else if (h->aos)
-    hipLaunchKernelGGL((k_unpack_window<double, false>), grid, block, 0, h->stream, (const double*)h->v.us, dst, h->B, h->T, h->nu, t0, n_knots);
-  else if (h->dtype == ILQR_DTYPE_F32)
-    hipLaunchKernelGGL((k_unpack_window<float, true>), grid, block, 0, h->stream, (const float*)h->v.us, dst, h->B, h->T, h->nu, t0, n_knots);
-  else
-    hipLaunchKernelGGL((k_unpack_window<double, true>), grid, block, 0, h->stream, (const double*)h->v.us, dst, h->B, h->T, h->nu, t0, n_knots);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return to_canonical(h, {h->v.us, h->T, h->nu, t0, n_knots}, (double*)u_device);
 }
 
 // ---- stages --------------------------------------------------------------------------------
@@ -874,9 +851,9 @@ int ilqr_reset_state(ilqr_batch* h, int warm) {
 int ilqr_set_trajectory(ilqr_batch* h, const double* x0, const double* xs, const double* us, const double* cost) {
   if (!h) return fail(ILQR_ERR_INVALID, "null handle");
   HIPCHK(hipSetDevice(h->device));
-  if (x0) if (int rc = upload(h, x0, h->v.x0, 1, h->nx)) return rc;
-  if (xs) if (int rc = upload(h, xs, h->v.xs, h->T + 1, h->nx)) return rc;
-  if (us) if (int rc = upload(h, us, h->v.us, h->T, h->nu)) return rc;
+  if (x0) if (int rc = upload(h, x0, {h->v.x0, 1, h->nx})) return rc;
+  if (xs) if (int rc = upload(h, xs, {h->v.xs, h->T + 1, h->nx})) return rc;
+  if (us) if (int rc = upload(h, us, {h->v.us, h->T, h->nu})) return rc;
   if (cost) if (int rc = scalars_to_dev(h, cost, h->v.cost)) return rc;
   h->initialised = true;
   return 0;
@@ -884,8 +861,8 @@ int ilqr_set_trajectory(ilqr_batch* h, const double* x0, const double* xs, const
 int ilqr_set_gains(ilqr_batch* h, const double* k, const double* K) {
   if (!h) return fail(ILQR_ERR_INVALID, "null handle");
   HIPCHK(hipSetDevice(h->device));
-  if (k) if (int rc = upload(h, k, h->v.kff, h->T, h->nu)) return rc;
-  if (K) if (int rc = upload(h, K, h->v.Kfb, h->T, h->nu * h->nx)) return rc;
+  if (k) if (int rc = upload(h, k, {h->v.kff, h->T, h->nu})) return rc;
+  if (K) if (int rc = upload(h, K, {h->v.Kfb, h->T, h->nu * h->nx})) return rc;
   return 0;
 }
 int ilqr_set_derivatives(ilqr_batch* h, const double* fx, const double* fu, const double* cx, const double* cu,
@@ -910,15 +887,15 @@ int ilqr_set_lambda(ilqr_batch* h, const double* lambda, const double* dlambda) 
 int ilqr_get_trajectory(ilqr_batch* h, double* xs, double* us) {
   if (!h) return fail(ILQR_ERR_INVALID, "null handle");
   HIPCHK(hipSetDevice(h->device));
-  if (xs) if (int rc = download(h, h->v.xs, xs, h->T + 1, h->nx)) return rc;
-  if (us) if (int rc = download(h, h->v.us, us, h->T, h->nu)) return rc;
+  if (xs) if (int rc = download(h, {h->v.xs, h->T + 1, h->nx}, xs)) return rc;
+  if (us) if (int rc = download(h, {h->v.us, h->T, h->nu}, us)) return rc;
   return 0;
 }
 int ilqr_get_gains(ilqr_batch* h, double* k, double* K) {
   if (!h) return fail(ILQR_ERR_INVALID, "null handle");
   HIPCHK(hipSetDevice(h->device));
-  if (k) if (int rc = download(h, h->v.kff, k, h->T, h->nu)) return rc;
-  if (K) if (int rc = download(h, h->v.Kfb, K, h->T, h->nu * h->nx)) return rc;
+  if (k) if (int rc = download(h, {h->v.kff, h->T, h->nu}, k)) return rc;
+  if (K) if (int rc = download(h, {h->v.Kfb, h->T, h->nu * h->nx}, K)) return rc;
   return 0;
 }
 int ilqr_get_derivatives(ilqr_batch* h, double* fx, double* fu, double* cx, double* cu, double* cxx, double* cxu,
@@ -930,7 +907,7 @@ int ilqr_get_derivatives(ilqr_batch* h, double* fx, double* fu, double* cx, doub
   double* dsts[7] = {fx, fu, cx, cu, cxx, cxu, cuu};
   if (int rc = materialise_records(h)) return rc;
   for (int i = 0; i < 7; i++)
-    if (dsts[i]) if (int rc = download_rec(h, dsts[i], off[i], len[i])) return rc;
+    if (dsts[i]) if (int rc = download(h, rec_block(h, off[i], len[i]), dsts[i])) return rc;
   return 0;
 }
 int ilqr_get_cost(ilqr_batch* h, double* cost) {
@@ -1015,65 +992,44 @@ int ilqr_copy_cost_to_device(ilqr_batch* h, void* dst) {
   HIPCHK(hipMemcpyAsync(dst, h->v.cost, (size_t)h->B * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
   return 0;
 }
-// the handle's (tiled, possibly float) array -> canonical double [B][S][E] in device memory `dst`; enqueued, not waited for
-static int unpack_to_device(ilqr_batch* h, const void* src, double* dst, int S, int E) {
-  const size_t n = (size_t)h->B * S * E;
-  if (h->aos && h->dtype == ILQR_DTYPE_F32) {  // generic fp32 handles: the canonical layout, widened
-    hipLaunchKernelGGL((k_convert<float, double>), dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const float*)src, dst, n);
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  if (h->aos) {  // generic handles: the canonical layout IS the device layout
-    HIPCHK(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    return 0;
-  }
-  if (h->dtype == ILQR_DTYPE_F32)
-    hipLaunchKernelGGL(k_unpack<float>, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const float*)src, dst, h->B, S, E);
-  else
-    hipLaunchKernelGGL(k_unpack<double>, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const double*)src, dst, h->B, S, E);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
 int ilqr_copy_trajectory_to_device(ilqr_batch* h, void* xs_dev, void* us_dev) {
   if (!h) return fail(ILQR_ERR_INVALID, "null handle");
   HIPCHK(hipSetDevice(h->device));
-  if (xs_dev) if (int rc = unpack_to_device(h, h->v.xs, (double*)xs_dev, h->T + 1, h->nx)) return rc;
-  if (us_dev) if (int rc = unpack_to_device(h, h->v.us, (double*)us_dev, h->T, h->nu)) return rc;
+  if (xs_dev) if (int rc = to_canonical(h, {h->v.xs, h->T + 1, h->nx}, (double*)xs_dev)) return rc;
+  if (us_dev) if (int rc = to_canonical(h, {h->v.us, h->T, h->nu}, (double*)us_dev)) return rc;
   return 0;
 }
 int ilqr_copy_gains_to_device(ilqr_batch* h, void* k_dev, void* K_dev) {
   if (!h) return fail(ILQR_ERR_INVALID, "null handle");
   HIPCHK(hipSetDevice(h->device));
-  if (k_dev) if (int rc = unpack_to_device(h, h->v.kff, (double*)k_dev, h->T, h->nu)) return rc;
-  if (K_dev) if (int rc = unpack_to_device(h, h->v.Kfb, (double*)K_dev, h->T, h->nu * h->nx)) return rc;
+  if (k_dev) if (int rc = to_canonical(h, {h->v.kff, h->T, h->nu}, (double*)k_dev)) return rc;
+  if (K_dev) if (int rc = to_canonical(h, {h->v.Kfb, h->T, h->nu * h->nx}, (double*)K_dev)) return rc;
   return 0;
 }
 int ilqr_get_results_async(ilqr_batch* h, double* xs, double* us, double* k, double* K, double* cost) {
   if (!h) return fail(ILQR_ERR_INVALID, "null handle");
   HIPCHK(hipSetDevice(h->device));
-  struct Item { const void* src; double* dst; int S, E; };
-  const Item items[4] = {{h->v.xs, xs, h->T + 1, h->nx}, {h->v.us, us, h->T, h->nu}, {h->v.kff, k, h->T, h->nu}, {h->v.Kfb, K, h->T, h->nu * h->nx}};
-  if (h->aos && h->dtype == ILQR_DTYPE_F64) {
-    for (const Item& it : items)
-      if (it.dst) HIPCHK(hipMemcpyAsync(it.dst, it.src, (size_t)h->B * it.S * it.E * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  } else {
-    // (tiled handles and generic fp32 handles: widened or unpacked into the staging buffer first)
-    // every array gets its own stretch of the staging buffer: the unpack kernels and the copies follow each other on the stream without a
-    // host synchronisation in between (the staging buffer is only ever touched by work enqueued on this stream: a later upload is ordered
-    // behind these copies)
-    size_t total = 0;
-    for (const Item& it : items)
-      if (it.dst) total += (size_t)h->B * it.S * it.E;
-    if (total)
-      if (int rc = ensure_staging(h, total)) return rc;
-    size_t off = 0;
-    for (const Item& it : items) {
-      if (!it.dst) continue;
-      const size_t n = (size_t)h->B * it.S * it.E;
-      if (int rc = unpack_to_device(h, it.src, h->staging + off, it.S, it.E)) return rc;
-      HIPCHK(hipMemcpyAsync(it.dst, h->staging + off, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  struct Item { DevArray src; double* dst; };
+  const Item items[4] = {{{h->v.xs, h->T + 1, h->nx}, xs}, {{h->v.us, h->T, h->nu}, us}, {{h->v.kff, h->T, h->nu}, k}, {{h->v.Kfb, h->T, h->nu * h->nx}, K}};
+  // a handle that stores the canonical arrays themselves: straight to the host.  Otherwise every array is converted into a stretch of the
+  // staging buffer of its own: the kernels and the copies follow each other on the stream without a host synchronisation in between (the
+  // staging buffer is only ever touched by work enqueued on this stream: a later upload is ordered behind these copies)
+  size_t total = 0;
+  for (const Item& it : items)
+    if (it.dst && !stored_canonical(h, it.src)) total += (size_t)h->B * it.src.S * it.src.E;
+  if (total)
+    if (int rc = ensure_staging(h, total)) return rc;
+  size_t off = 0;
+  for (const Item& it : items) {
+    if (!it.dst) continue;
+    const size_t n = (size_t)h->B * it.src.S * it.src.E;
+    const double* dev = (const double*)it.src.p;
+    if (!stored_canonical(h, it.src)) {
+      if (int rc = to_canonical(h, it.src, h->staging + off)) return rc;
+      dev = h->staging + off;
       off += n;
     }
+    HIPCHK(hipMemcpyAsync(it.dst, dev, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   }
   if (cost) HIPCHK(hipMemcpyAsync(cost, h->v.cost, (size_t)h->B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   return 0;

@@ -131,11 +131,21 @@ static void sync_float_view(ilqr_batch* h) {
   f.status = v.status; f.iters = v.iters; f.flg_change = v.flg_change; f.alpha_idx = v.alpha_idx; f.diverge = v.diverge;
   f.backpass_done = v.backpass_done; f.n_running = v.n_running; f.analytic = v.analytic;
 }
+// f(real()) with the handle's storage type, float or double: where a handle's dtype picks between two instantiations of the same code
+template <class F>
+static int with_real(ilqr_batch* h, F&& f) {
+  if (h->dtype == ILQR_DTYPE_F32) return f(float());
+  return f(double());
+}
 // f(view) with the handle's view typed by its storage: h->v (double) or h->vf (float)
 template <class F>
 static int with_view(ilqr_batch* h, F&& f) {
-  if (h->dtype == ILQR_DTYPE_F32) return f(h->vf);
-  return f(h->v);
+  return with_real(h, [&](auto r) {
+    if constexpr (std::is_same_v<decltype(r), float>)
+      return f(h->vf);
+    else
+      return f(h->v);
+  });
 }
 // f(view, model, model the finite differences are taken in) for the handle's device model and arithmetic
 template <class F>
@@ -170,7 +180,7 @@ static bool host_model(const ilqr_batch* h) { return h->model == ILQR_MODEL_HOST
 static int no_device_model();
 // elements of a per-knot array with S time slots of E doubles, in this handle's device layout
 static size_t dev_elems(const ilqr_batch* h, size_t S, size_t E) {
-  return h->aos ? (size_t)h->B * S * E : (size_t)h->ntiles * S * E * TW;
+  return layout_elems(h->aos, h->B, h->ntiles, S, E);
 }
 
 template <class T>
@@ -272,55 +282,85 @@ static int ensure_staging(ilqr_batch* h, size_t elems) {
   h->staging_elems = elems;
   return 0;
 }
-// canonical host [B][S][E] -> tiled device  (AoS handles: the canonical layout IS the device layout)
-static int upload(ilqr_batch* h, const double* src, void* dst_tiled, int S, int E) {
-  const size_t n = (size_t)h->B * S * E;
-  if (h->aos && h->dtype == ILQR_DTYPE_F32) {  // generic fp32 handle: canonical layout, rounded on the device
-    if (int rc = ensure_staging(h, n)) return rc;
-    HIPCHK(hipMemcpyAsync(h->staging, src, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL((k_convert<double, float>), dim3(grid_for(n, 256)), dim3(256), 0, h->stream, h->staging, (float*)dst_tiled, n);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(h->stream));  // staging is reused by the next call
+// One of the handle's arrays as the conversions take it: S knots of E elements per trajectory, of which the knots [t0, t0 + n) are moved
+// (n = 0: all S).  rec: not a plain array but the E elements from offset `off` of every knot's derivative record.
+struct DevArray {
+  void* p;
+  int S, E;
+  int t0 = 0, n = 0;
+  bool rec = false;
+  int off = 0;
+};
+static int knots(const DevArray& a) { return a.n ? a.n : a.S; }
+static DevArray rec_block(const ilqr_batch* h, int off, int E) { return {h->v.D, h->T + 1, E, 0, 0, true, off}; }
+// a generic fp64 handle stores a whole array as the canonical array itself: copied, never converted
+static bool stored_canonical(const ilqr_batch* h, const DevArray& a) {
+  return h->aos && elem_size(h) == sizeof(double) && !a.rec && knots(a) == a.S;
+}
+// f(index map of `a` in this handle's layout) (layout.hpp)
+template <class F>
+static int with_map(const ilqr_batch* h, const DevArray& a, F&& f) {
+  if (h->aos) return f(AosMap{a.S, a.rec ? rec_of(h) : a.E, a.off, a.t0});
+  if (a.rec) return f(TiledRecMap{a.S, rec_of(h), a.off, a.t0});
+  return f(TiledMap{a.S, a.E, a.t0});
+}
+// handle's array -> canonical double [B][n][E] in device memory, and back.  Enqueued on the handle's stream: nothing is waited for,
+// the staging buffer is not touched.
+static int to_canonical(ilqr_batch* h, const DevArray& a, double* dst) {
+  const int n = knots(a);
+  const size_t total = (size_t)h->B * n * a.E;
+  if (stored_canonical(h, a)) {
+    HIPCHK(hipMemcpyAsync(dst, a.p, total * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return 0;
   }
-  if (h->aos) {
-    HIPCHK(hipMemcpyAsync(dst_tiled, src, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+  return with_real(h, [&](auto r) {
+    return with_map(h, a, [&](auto map) {
+      using real = decltype(r);
+      hipLaunchKernelGGL((k_to_canonical<real, decltype(map)>), dim3(grid_for(total, 256)), dim3(256), 0, h->stream, (const real*)a.p, dst, map, h->B, n, a.E);
+      HIPCHK(hipGetLastError());
+      return 0;
+    });
+  });
+}
+static int from_canonical(ilqr_batch* h, const double* src, const DevArray& a) {
+  const int n = knots(a);
+  if (stored_canonical(h, a)) {
+    if (src != a.p) HIPCHK(hipMemcpyAsync(a.p, src, (size_t)h->B * n * a.E * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return 0;
   }
-  if (int rc = ensure_staging(h, n)) return rc;
-  HIPCHK(hipMemcpyAsync(h->staging, src, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  const size_t nt = (size_t)h->ntiles * S * E * TW;
-  if (h->dtype == ILQR_DTYPE_F32)
-    hipLaunchKernelGGL(k_pack<float>, dim3(grid_for(nt, 256)), dim3(256), 0, h->stream, h->staging, (float*)dst_tiled, h->B, h->ntiles, S, E);
-  else
-    hipLaunchKernelGGL(k_pack<double>, dim3(grid_for(nt, 256)), dim3(256), 0, h->stream, h->staging, (double*)dst_tiled, h->B, h->ntiles, S, E);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(h->stream));  // staging is reused by the next call
+  return with_real(h, [&](auto r) {
+    return with_map(h, a, [&](auto map) {
+      using real = decltype(r);
+      const int groups = h->aos ? h->B : h->ntiles;
+      const size_t total = (size_t)groups * n * a.E * map.LANES;
+      hipLaunchKernelGGL((k_from_canonical<real, decltype(map)>), dim3(grid_for(total, 256)), dim3(256), 0, h->stream, src, (real*)a.p, map, h->B, groups, n, a.E);
+      HIPCHK(hipGetLastError());
+      return 0;
+    });
+  });
+}
+// canonical host array -> handle's array and back, waited for (the staging buffer is reused by the next call)
+static int upload(ilqr_batch* h, const double* src, const DevArray& a) {
+  const size_t bytes = (size_t)h->B * knots(a) * a.E * sizeof(double);
+  double* dev = (double*)a.p;
+  if (!stored_canonical(h, a)) {
+    if (int rc = ensure_staging(h, bytes / sizeof(double))) return rc;
+    dev = h->staging;
+  }
+  HIPCHK(hipMemcpyAsync(dev, src, bytes, hipMemcpyHostToDevice, h->stream));
+  if (int rc = from_canonical(h, dev, a)) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }
-static int download(ilqr_batch* h, const void* src_tiled, double* dst, int S, int E) {
-  const size_t n = (size_t)h->B * S * E;
-  if (h->aos && h->dtype == ILQR_DTYPE_F32) {  // generic fp32 handle: widened on the device
-    if (int rc = ensure_staging(h, n)) return rc;
-    hipLaunchKernelGGL((k_convert<float, double>), dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const float*)src_tiled, h->staging, n);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(dst, h->staging, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
+static int download(ilqr_batch* h, const DevArray& a, double* dst) {
+  const size_t bytes = (size_t)h->B * knots(a) * a.E * sizeof(double);
+  const double* dev = (const double*)a.p;
+  if (!stored_canonical(h, a)) {
+    if (int rc = ensure_staging(h, bytes / sizeof(double))) return rc;
+    if (int rc = to_canonical(h, a, h->staging)) return rc;
+    dev = h->staging;
   }
-  if (h->aos) {
-    HIPCHK(hipMemcpyAsync(dst, src_tiled, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-  }
-  if (int rc = ensure_staging(h, n)) return rc;
-  if (h->dtype == ILQR_DTYPE_F32)
-    hipLaunchKernelGGL(k_unpack<float>, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const float*)src_tiled, h->staging, h->B, S, E);
-  else
-    hipLaunchKernelGGL(k_unpack<double>, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const double*)src_tiled, h->staging, h->B, S, E);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(dst, h->staging, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(dst, dev, bytes, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -329,8 +369,7 @@ static int launch_derivatives(ilqr_batch* h, int force);
 static int ensure_records(ilqr_batch* h) {
   if (h->v.D) return 0;
   // (generic handles: on first use as well -- 44 GB at configs[4] in fp64, 22 GB in fp32)
-  const size_t n = h->aos ? (size_t)h->B * (h->T + 1) * rec_of(h) : (size_t)h->ntiles * (h->T + 1) * rec_of(h) * TW;
-  if (int rc = dev_alloc_real(h, &h->v.D, n)) return rc;
+  if (int rc = dev_alloc_real(h, &h->v.D, dev_elems(h, h->T + 1, rec_of(h)))) return rc;
   sync_float_view(h);
   return 0;
 }
@@ -366,50 +405,7 @@ static int upload_rec(ilqr_batch* h, const double* src, int off, int E) {
   h->lq_caller_records = true;
   h->recs = ilqr_batch::REC_VALID;
 
-  const int S = h->T + 1;
-  const size_t n = (size_t)h->B * S * E;
-  if (int rc = ensure_staging(h, n)) return rc;
-  HIPCHK(hipMemcpyAsync(h->staging, src, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (h->aos) {
-    if (h->dtype == ILQR_DTYPE_F32)
-      hipLaunchKernelGGL(k_rec_aos<float>, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, h->vf.D, h->staging, h->B, S, rec_of(h), off, E, 1);
-    else
-      hipLaunchKernelGGL(k_rec_aos<double>, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, h->v.D, h->staging, h->B, S, rec_of(h), off, E, 1);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-  }
-  const size_t nt = (size_t)h->ntiles * S * E * TW;
-  if (h->dtype == ILQR_DTYPE_F32)
-    hipLaunchKernelGGL(k_pack_rec<float>, dim3(grid_for(nt, 256)), dim3(256), 0, h->stream, h->staging, h->vf.D, h->B, h->ntiles, S, rec_of(h), off, E);
-  else
-    hipLaunchKernelGGL(k_pack_rec<double>, dim3(grid_for(nt, 256)), dim3(256), 0, h->stream, h->staging, h->v.D, h->B, h->ntiles, S, rec_of(h), off, E);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return 0;
-}
-static int download_rec(ilqr_batch* h, double* dst, int off, int E) {
-  const int S = h->T + 1;
-  const size_t n = (size_t)h->B * S * E;
-  if (int rc = ensure_staging(h, n)) return rc;
-  if (h->aos) {
-    if (h->dtype == ILQR_DTYPE_F32)
-      hipLaunchKernelGGL(k_rec_aos<float>, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, h->vf.D, h->staging, h->B, S, rec_of(h), off, E, 0);
-    else
-      hipLaunchKernelGGL(k_rec_aos<double>, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, h->v.D, h->staging, h->B, S, rec_of(h), off, E, 0);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(dst, h->staging, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-  }
-  if (h->dtype == ILQR_DTYPE_F32)
-    hipLaunchKernelGGL(k_unpack_rec<float>, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, h->vf.D, h->staging, h->B, S, rec_of(h), off, E);
-  else
-    hipLaunchKernelGGL(k_unpack_rec<double>, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, h->v.D, h->staging, h->B, S, rec_of(h), off, E);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(dst, h->staging, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return 0;
+  return upload(h, src, rec_block(h, off, E));
 }
 // per-trajectory scalar arrays [Bp] on device <-> [B] host
 template <class T>

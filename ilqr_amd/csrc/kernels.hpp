@@ -1,6 +1,6 @@
 // kernels.hpp -- the HIP kernels of the nx = 4 tiled path (gfx950 / MI355X), one header per stage:
 //
-//   layout.hpp           k_pack / k_unpack / k_permute_* / k_reset_state
+//   layout.hpp           index maps, k_to_canonical / k_from_canonical, k_permute_*, k_reset_state, k_shift_horizon
 //   rollout.hpp          rollout_tile, k_rollout, accept_one, k_accept, candidate checkpoints
 //   derivatives.hpp      derivatives_of_knot, k_derivatives
 //   backward_thread.hpp  k_backward_t (one thread per trajectory; cross-check)

@@ -1,5 +1,5 @@
-// layout.hpp -- canonical [B][S][E] <-> tiled [tile][S][E][16] conversion, slot permutation (compaction), per-trajectory
-// state reset (init_traj, src/ilqr_core.cpp:11-56), the receding-horizon shift and the control window of an MPC step.  Lane mapping everywhere: consecutive lanes = consecutive trajectories of
+// layout.hpp -- canonical [B][S][E] <-> a handle's layout (index maps, k_to_canonical / k_from_canonical), slot permutation (compaction),
+// per-trajectory state reset (init_traj, src/ilqr_core.cpp:11-56) and the receding-horizon shift.  Lane mapping everywhere: consecutive lanes = consecutive trajectories of
 // a tile, so each vector load / store touches whole 128-byte lines of the tiled layout (common.hpp).
 #pragma once
 #include <type_traits>
@@ -13,65 +13,57 @@ namespace ilqr {
 // ------------------------------------------------------------------------------------------
 // layout conversion
 // ------------------------------------------------------------------------------------------
-// canonical src[b][s][e]  ->  tiled dst[tile][s][e][l]      (one thread per tiled element)
-template <class real>
-__global__ void k_pack(const double* __restrict__ src, real* __restrict__ dst, int B, int ntiles, int S, int E) {
-  const size_t n = (size_t)ntiles * S * E * TW;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const int l = (int)(i % TW);
-    size_t r = i / TW;
-    const int e = (int)(r % E);
-    r /= E;
-    const int s = (int)(r % S);
-    const int tile = (int)(r / S);
-    const int b = tile * TW + l;
-    dst[i] = (b < B) ? (real)src[((size_t)b * S + s) * E + e] : real(0);
-  }
+// An array crosses the C ABI as canonical double [B][n][E].  A handle stores it tiled or trajectory-contiguous, as double or float
+// (common.hpp); an index map says where element (b, s, e) of the canonical array lives in the handle's array.  The canonical array may
+// be a window of the handle's S knots -- its knot s is the handle's knot t0 + s -- and, of the records, one block of each knot.
+// LANES: trajectories interleaved in the innermost dimension of the device layout, the order k_from_canonical walks it in.
+struct TiledMap {  // [tile][S][E][16]
+  static constexpr int LANES = TW;
+  int S, E, t0;
+  __host__ __device__ size_t operator()(int b, int s, int e) const { return tidx(b / TW, t0 + s, e, b % TW, S, E); }
+};
+struct TiledRecMap {  // elements [off, off + E) of the pair-interleaved records [tile][S][REC/2][16][2]
+  static constexpr int LANES = TW;
+  int S, REC, off, t0;
+  __host__ __device__ size_t operator()(int b, int s, int e) const { return didx(b / TW, t0 + s, off + e, b % TW, S, REC); }
+};
+struct AosMap {  // elements [off, off + E) of [b][S][stride]: a plain array (stride = E, off = 0) or a block of the records (stride = REC)
+  static constexpr int LANES = 1;
+  int S, stride, off, t0;
+  __host__ __device__ size_t operator()(int b, int s, int e) const { return ((size_t)b * S + t0 + s) * stride + off + e; }
+};
+// elements of a handle's array of S knots of E elements per trajectory: what every index map above stays inside
+__host__ __device__ inline size_t layout_elems(bool aos, int B, int ntiles, size_t S, size_t E) {
+  return aos ? (size_t)B * S * E : (size_t)ntiles * S * E * TW;
 }
-// an fp32 generic handle's array (trajectory-contiguous: the canonical layout itself) <-> double, element by element
-template <class From, class To>
-__global__ void k_convert(const From* __restrict__ src, To* __restrict__ dst, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = (To)src[i];
-}
-// tiled src -> canonical dst   (one thread per canonical element; reads are line-strided but
-// this path only serves getters)
-template <class real>
-__global__ void k_unpack(const real* __restrict__ src, double* __restrict__ dst, int B, int S, int E) {
-  const size_t n = (size_t)B * S * E;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+
+// handle's array -> canonical dst[b][s][e], one thread per canonical element (the stores are coalesced; a tiled source is read
+// line-strided, but this direction only serves getters)
+template <class real, class Map>
+__global__ void k_to_canonical(const real* __restrict__ src, double* __restrict__ dst, Map map, int B, int n, int E) {
+  const size_t total = (size_t)B * n * E;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int e = (int)(i % E);
     size_t r = i / E;
-    const int s = (int)(r % S);
-    const int b = (int)(r / S);
-    dst[i] = (double)src[tidx(b / TW, s, e, b % TW, S, E)];
+    const int s = (int)(r % n);
+    const int b = (int)(r / n);
+    dst[i] = (double)src[map(b, s, e)];
   }
 }
-// tiled record sub-range [off, off+E) of a record of size REC  <->  canonical [B][S][E]
-template <class real>
-__global__ void k_pack_rec(const double* __restrict__ src, real* __restrict__ dst, int B, int ntiles, int S,
-                           int REC, int off, int E) {
-  const size_t n = (size_t)ntiles * S * E * TW;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const int l = (int)(i % TW);
-    size_t r = i / TW;
+// canonical src[b][s][e] -> handle's array, one thread per element of the handle's array in its own order [group][s][e][lane] (the
+// stores are coalesced); groups: the handle's tiles, or its trajectories.  The padding lanes b >= B are written as zero.
+template <class real, class Map>
+__global__ void k_from_canonical(const double* __restrict__ src, real* __restrict__ dst, Map map, int B, int groups, int n, int E) {
+  constexpr int L = Map::LANES;
+  const size_t total = (size_t)groups * n * E * L;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int l = (int)(i % L);
+    size_t r = i / L;
     const int e = (int)(r % E);
     r /= E;
-    const int s = (int)(r % S);
-    const int tile = (int)(r / S);
-    const int b = tile * TW + l;
-    dst[didx(tile, s, off + e, l, S, REC)] = (b < B) ? (real)src[((size_t)b * S + s) * E + e] : real(0);
-  }
-}
-template <class real>
-__global__ void k_unpack_rec(const real* __restrict__ src, double* __restrict__ dst, int B, int S, int REC,
-                             int off, int E) {
-  const size_t n = (size_t)B * S * E;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const int e = (int)(i % E);
-    size_t r = i / E;
-    const int s = (int)(r % S);
-    const int b = (int)(r / S);
-    dst[i] = (double)src[didx(b / TW, s, off + e, b % TW, S, REC)];
+    const int s = (int)(r % n);
+    const int b = (int)(r / n) * L + l;
+    dst[map(b, s, e)] = (b < B) ? (real)src[((size_t)b * n + s) * E + e] : real(0);
   }
 }
 
@@ -185,20 +177,6 @@ __global__ void __launch_bounds__(256) k_shift_horizon(ShiftSet set) {
       shift_range(p, keep, n, [&](size_t i) { return p[last + (i - keep) % W]; });
     else
       shift_range(p, keep, n, [&](size_t) { return real(0); });
-  }
-}
-
-// the control window us[:, t0 : t0 + n, :] of an S-knot array as canonical double [B][n][E] (ilqr_copy_controls_to_device): tiled
-// [tile][S][E][16] or trajectory-contiguous [b][S][E] source, one thread per canonical element
-template <class real, bool TILED>
-__global__ void k_unpack_window(const real* __restrict__ src, double* __restrict__ dst, int B, int S, int E, int t0, int n) {
-  const size_t total = (size_t)B * n * E;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int e = (int)(i % E);
-    size_t r = i / E;
-    const int t = t0 + (int)(r % n);
-    const int b = (int)(r / n);
-    dst[i] = TILED ? (double)src[tidx(b / TW, t, e, b % TW, S, E)] : (double)src[((size_t)b * S + t) * E + e];
   }
 }
 
