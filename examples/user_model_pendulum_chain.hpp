@@ -28,6 +28,19 @@ struct UserModelT {
     wf = (real)(n >= 8 ? p[6] : d[6]);
     target = (real)(n >= 8 ? p[7] : d[7]);
   }
+  // per-trajectory parameters (ilqr_set_trajectory_params): all eight, in user_params' order -- a moving target angle per trajectory,
+  // or a perturbed chain per trajectory.  The limits stay the handle's.
+  static constexpr int NTP = 8;
+  __device__ void set_trajectory_params(const double* p) {
+    gl = (real)p[0];
+    damp = (real)p[1];
+    kc = (real)p[2];
+    wq = (real)p[3];
+    ww = (real)p[4];
+    wu = (real)p[5];
+    wf = (real)p[6];
+    target = (real)p[7];
+  }
   __device__ void dynamics(const real* x, const real* u, real* dx) const {
     for (int i = 0; i < NL; i++) dx[i] = x[NL + i];
     for (int i = 0; i < NL; i++) {

@@ -152,6 +152,32 @@ class BatchILQR:
         """us[:, t0 : t0 + n, :] as float64 [B][n][nu] into caller-owned device memory `ptr` (raw pointer); enqueued on the handle's stream."""
         self._check(self.lib.ilqr_copy_controls_to_device(self.h, int(t0), int(n), ptr))
 
+    # ---- per-trajectory model parameters (user twins with NTP / set_trajectory_params on the generic kernels) ----
+    def set_trajectory_params(self, p=None, ptr=None):
+        """Row b = the model parameters of trajectory b for every later rollout, sweep and mpc_step.  p: numpy [B][NTP]; ptr: a raw
+        device pointer to [B][NTP] float64 on the handle's device (torch.Tensor.data_ptr()).  Exactly one of them.  Enqueued on the
+        handle's stream (the stream rule above); the stored cost is not re-evaluated -- warm-start or mpc_step next."""
+        if (p is None) == (ptr is None):
+            raise ValueError("set_trajectory_params: exactly one of p and ptr")
+        n = self.lib.ilqr_trajectory_params_count()
+        if p is not None:
+            p = _c(p)
+            if p.ndim != 2 or p.shape[0] != self.B:
+                raise ValueError("set_trajectory_params: p must be [B][NTP], got %s" % (p.shape,))
+            n = p.shape[1]
+        self._check(self.lib.ilqr_set_trajectory_params(self.h, _p(p), ptr, int(n)))
+
+    def trajectory_params(self):
+        """The rows set_trajectory_params stored, [B][NTP] (synchronises)."""
+        n = self.lib.ilqr_trajectory_params_count()
+        p = np.zeros((self.B, max(n, 1)))
+        self._check(self.lib.ilqr_get_trajectory_params(self.h, _p(p), int(n)))
+        return p
+
+    def clear_trajectory_params(self):
+        """Every trajectory back to the handle-wide parameters of the constructor."""
+        self._check(self.lib.ilqr_clear_trajectory_params(self.h))
+
     # ---- stages ----
     def compute_derivatives(self):
         self._check(self.lib.ilqr_compute_derivatives(self.h))

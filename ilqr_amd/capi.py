@@ -56,6 +56,10 @@ SYMBOLS = {
     "ilqr_shift_horizon": (C.c_int, [_H, C.c_int, C.c_int]),
     "ilqr_mpc_step": (C.c_int, [_H, _dp, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "ilqr_copy_controls_to_device": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
+    "ilqr_trajectory_params_count": (C.c_int, []),
+    "ilqr_set_trajectory_params": (C.c_int, [_H, _dp, C.c_void_p, C.c_int]),
+    "ilqr_get_trajectory_params": (C.c_int, [_H, _dp, C.c_int]),
+    "ilqr_clear_trajectory_params": (C.c_int, [_H]),
     "ilqr_compute_derivatives": (C.c_int, [_H]),
     "ilqr_backward_pass": (C.c_int, [_H, _ip]),
     "ilqr_backward_step": (C.c_int, [_H]),

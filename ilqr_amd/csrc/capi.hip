@@ -746,6 +746,60 @@ int ilqr_copy_controls_to_device(ilqr_batch* h, int t0, int n_knots, void* u_dev
   return to_canonical(h, {h->v.us, h->T, h->nu, t0, n_knots}, (double*)u_device);
 }
 
+// ---- per-trajectory model parameters (additive under ABI 6) ------------------------------------
+int ilqr_trajectory_params_count(void) { return kUserNTP; }
+
+// every refusal the three handle calls share; 0: this handle's kernels take per-trajectory rows
+static int check_trajectory_params(const ilqr_batch* h, const char* who) {
+  if (h->model != ILQR_MODEL_USER)
+    return fail(ILQR_ERR_UNSUPPORTED, "%s: per-trajectory parameters belong to a user device twin (ILQR_MODEL_USER); this handle's model is %d", who, h->model);
+  if (!h->aos) {
+    if (h->nx == 4)
+      return fail(ILQR_ERR_UNSUPPORTED, "%s: an nx = 4 twin runs the persistent tiled kernels, which keep one model for all trajectories; per-trajectory "
+                                        "parameters need the generic wavefront-per-trajectory kernels (a twin of another shape)", who);
+    return fail(ILQR_ERR_UNSUPPORTED, "%s: this handle runs the tiled small-twin kernels, which keep one model for all trajectories; create it with "
+                                      "ILQR_ROUTE_WAVE_PER_TRAJECTORY (the generic wavefront-per-trajectory kernels)", who);
+  }
+  if (kUserNTP == 0)
+    return fail(ILQR_ERR_UNSUPPORTED, "%s: this build's user model declares no per-trajectory parameters (NTP, set_trajectory_params: csrc/models.hpp)", who);
+  if (!takes_trajectory_params(h->plan))
+    return fail(ILQR_ERR_UNSUPPORTED, "%s: this handle's route does not run k_rollout_g / k_derivatives_g", who);
+  return 0;
+}
+
+int ilqr_set_trajectory_params(ilqr_batch* h, const double* p, const void* p_device, int n) {
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  if (int rc = check_trajectory_params(h, "ilqr_set_trajectory_params")) return rc;
+  REQUIRE((p != nullptr) != (p_device != nullptr), "ilqr_set_trajectory_params: exactly one of p (host) and p_device");
+  REQUIRE(n == kUserNTP, "ilqr_set_trajectory_params: n = %d, this build's user model takes NTP = %d parameters per trajectory", n, kUserNTP);
+  HIPCHK(hipSetDevice(h->device));
+  const size_t elems = (size_t)h->B * kUserNTP;
+  if (!h->traj_params)
+    if (int rc = dev_alloc(h, &h->traj_params, elems)) return rc;
+  HIPCHK(hipMemcpyAsync(h->traj_params, p ? (const void*)p : p_device, elems * sizeof(double), p ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
+  h->plan.traj_params = true;
+  return 0;
+}
+
+int ilqr_get_trajectory_params(ilqr_batch* h, double* p, int n) {
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  if (int rc = check_trajectory_params(h, "ilqr_get_trajectory_params")) return rc;
+  REQUIRE(p != nullptr, "ilqr_get_trajectory_params: null array");
+  REQUIRE(n == kUserNTP, "ilqr_get_trajectory_params: n = %d, this build's user model takes NTP = %d parameters per trajectory", n, kUserNTP);
+  if (!h->plan.traj_params) return fail(ILQR_ERR_STATE, "ilqr_get_trajectory_params: no per-trajectory parameters are set (every trajectory uses ilqr_create's)");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipMemcpyAsync(p, h->traj_params, (size_t)h->B * kUserNTP * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int ilqr_clear_trajectory_params(ilqr_batch* h) {
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  if (int rc = check_trajectory_params(h, "ilqr_clear_trajectory_params")) return rc;
+  h->plan.traj_params = false;  // (the rows stay allocated for the next set)
+  return 0;
+}
+
 // ---- stages --------------------------------------------------------------------------------
 int ilqr_compute_derivatives(ilqr_batch* h) {
   if (!h) return fail(ILQR_ERR_INVALID, "null handle");

@@ -332,13 +332,30 @@ struct GenericModelOf : U {
   }
 };
 
+// Per-trajectory model parameters (ilqr_set_trajectory_params; models.hpp: NTP, set_trajectory_params).  The PT instantiations of the two
+// kernels that touch the model take the handle's model with the handle's rows behind it, canonical double [B][NTP]; a kernel overwrites
+// ITS copy of the model (this by-value argument) from the row of its trajectory before the first evaluation.  The instantiations without
+// PT take the model itself, as they always did: not one argument, not one instruction of theirs changes.
+template <class M>
+struct PerTrajectory : M {
+  const double* traj_params = nullptr;
+};
+template <class M, bool PT>
+using model_arg_t = std::conditional_t<PT, PerTrajectory<M>, M>;
+
 enum { RG_INIT = 0, RG_SEARCH = 1, RG_COMMIT = 2 };
 constexpr int kSearchTraj = 64 / NALPHA;  // trajectories per wavefront in RG_SEARCH (5)
+#ifndef ILQR_ROLLOUT_G_PT_WAVES
+#define ILQR_ROLLOUT_G_PT_WAVES 0  // wavefronts per SIMD of k_rollout_g<.., PT> (0: whatever its register count allows, as without PT)
+#endif
 
 // fp32 handles (M::real = float: LqModelT<float>, GenericModelOf<UserModelT<float>>): float knots and registers, the cost summed in double.
-template <class M, int MODE>
-__global__ __launch_bounds__(64) void k_rollout_g(BatchViewT<typename M::real> v, M model, AlphaSet alphas, double* __restrict__ cost_out,
-                                                  const int* __restrict__ commit_idx, int mode, int write_cost, int fixes) {
+// PT: the model's parameters are this lane's trajectory's (RG_SEARCH: the 11 lanes of a trajectory read the same row; RG_INIT / RG_COMMIT:
+// lanes read consecutive rows).  The model's parameter fields then live in vector registers instead of scalar ones.
+template <class M, int MODE, bool PT = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT ? ILQR_ROLLOUT_G_PT_WAVES : 0, PT ? ILQR_ROLLOUT_G_PT_WAVES : 0)))
+void k_rollout_g(BatchViewT<typename M::real> v, model_arg_t<M, PT> model, AlphaSet alphas, double* __restrict__ cost_out,
+                 const int* __restrict__ commit_idx, int mode, int write_cost, int fixes) {
   using real = typename M::real;
   constexpr int NX = M::NX, NU = M::NU;
   const int nx = model.nx, nu = model.nu, T = v.T;
@@ -363,6 +380,12 @@ __global__ __launch_bounds__(64) void k_rollout_g(BatchViewT<typename M::real> v
   for (int q = 0; q < NALPHA; q++)
     if (a == q) alpha = (real)alphas.a[q];
   const real dt = (real)v.dt;
+  if constexpr (PT) {  // row b: the generic path never re-packs trajectories, a trajectory's slot is its index
+    double p[M::NTP];
+#pragma unroll
+    for (int i = 0; i < M::NTP; i++) p[i] = model.traj_params[(size_t)b * M::NTP + i];
+    model.set_trajectory_params(p);  // (a float twin casts: the float-rounded values on an fp32 handle)
+  }
 
   real x[NX];
 #pragma unroll
@@ -847,7 +870,7 @@ __global__ __launch_bounds__(256) void k_commit_lq(BatchView v, int nx, int nu, 
 //   cxu      (c(px,pu) - c(mx,pu) - c(px,mu) + c(mx,mu)) / 4eps^2               derivatives.cpp:114-144
 // including the t = T special cases (fx[T] = fu[T] = 0, cx/cxx from final_cost, cu[T] = 0, cuu[T]
 // from cost(x_T, 0), the cxu[T] formula the reference itself marks wrong).
-template <class M, class S = double>
+template <class M, class S = double, bool PT = false>
 // t_only >= 0: one block per trajectory, knot t_only alone (the last knot behind k_derivatives_lq, which sweeps the knots t < T).
 #ifndef ILQR_FD_G_WAVES_SMALL
 // Wavefronts per SIMD of k_derivatives_g: two at NX > 16 (186 registers for the LQ model's 32-vectors); THREE for a model of NX <= 16 (168
@@ -857,7 +880,11 @@ template <class M, class S = double>
 #define ILQR_FD_G_WAVES_SMALL 3
 #endif
 // S = float (fp32 handles): the float knot widened, the model evaluated in double (M is the double twin), the record rounded.
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((M::NX <= 16 ? ILQR_FD_G_WAVES_SMALL : 2), (M::NX <= 16 ? ILQR_FD_G_WAVES_SMALL : 2)))) void k_derivatives_g(BatchViewT<S> v, M model, int force, int t_only) {
+// PT: the model's parameters are trajectory b's.  b comes from blockIdx.x, so the row is wave-uniform: it is read through the constant
+// address space (scalar loads, as the LQ model's matrices are) and the parameters stay in scalar registers, where the 880 cost evaluations
+// per knot find them today.  fp32 handles: the float-rounded values (the float rollouts' twin casts the same row), rounded by the vector
+// unit and handed back to scalar registers with v_readfirstlane.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((M::NX <= 16 ? ILQR_FD_G_WAVES_SMALL : 2), (M::NX <= 16 ? ILQR_FD_G_WAVES_SMALL : 2)))) void k_derivatives_g(BatchViewT<S> v, model_arg_t<M, PT> model, int force, int t_only) {
   constexpr int NX = M::NX, NU = M::NU;
   const int nx = model.nx, nu = model.nu, T = v.T;
   const int lane = threadIdx.x;
@@ -868,6 +895,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((M::NX <= 16
             oCUU = oCU + nu, REC = oCUU + nu * nu;
   S* D = v.D + ((size_t)b * (T + 1) + t) * REC;
   const bool last = (t == T);
+  if constexpr (PT) {  // row b (see k_rollout_g)
+    cmem_d* row = (cmem_d*)model.traj_params + (size_t)b * M::NTP;
+    double p[M::NTP];
+#pragma unroll
+    for (int i = 0; i < M::NTP; i++) {
+      p[i] = row[i];
+      if constexpr (!std::is_same<S, double>::value) {
+        const double r = (double)(float)p[i];
+        p[i] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(r)), __builtin_amdgcn_readfirstlane(__double2loint(r)));
+      }
+    }
+    model.set_trajectory_params(p);
+  }
 
 #define ILQR_DMARK(k)
   double x[NX], u[NU];  // the knot (same in every lane): one coalesced load per vector, handed round with

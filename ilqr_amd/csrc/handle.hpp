@@ -56,6 +56,10 @@ struct ilqr_batch {
   UserModelT<float> user_f;
   GenericModelOf<UserModelT<float>> user_gf;  // fp32 handle on the generic layout: what k_rollout_g integrates
 #endif
+  // per-trajectory model parameters (ilqr_set_trajectory_params): canonical double [B][NTP], allocated on first use; plan.traj_params says
+  // whether the kernels read them.  Row b is the trajectory in slot b: the generic path never re-packs trajectories (ilqr_generate_trajectory
+  // compacts on the persistent routes only) -- whoever brings compaction to this path must move these rows with the trajectories.
+  double* traj_params = nullptr;
   // v is the view every entry point addresses arrays through; for an fp32 handle its trajectory pointers hold
   // the addresses of FLOAT arrays (never dereferenced as double: kernels get vf, the same addresses typed float*)
   BatchView v;

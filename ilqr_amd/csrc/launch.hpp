@@ -57,6 +57,14 @@ static const BatchViewT<R>& view_of(const ilqr_batch* h) {
 // matrix cores (k_rollout_lq, one wavefront per trajectory); ILQR_ROUTE_LQ_THREAD_ROLLOUT selects the
 // generic thread-per-rollout kernel (same results bit for bit; kept as the cross-check and as the
 // template for device models without matrix structure).
+// the model with the handle's per-trajectory rows behind it: what the PT instantiations of k_rollout_g / k_derivatives_g take
+template <class M>
+static PerTrajectory<M> per_trajectory(const ilqr_batch* h, const M& m) {
+  PerTrajectory<M> pm;
+  static_cast<M&>(pm) = m;
+  pm.traj_params = h->traj_params;
+  return pm;
+}
 template <class M>
 static int launch_rollout_g(ilqr_batch* h, const M& m, int what, const AlphaSet& al, double* cost_out, int mode, int write_cost, bool with_accept = false) {
   if constexpr (std::is_same<M, LqModel>::value)
@@ -76,6 +84,20 @@ static int launch_rollout_g(ilqr_batch* h, const M& m, int what, const AlphaSet&
     return 0;
   }
   const BatchViewT<typename M::real>& v = view_of<typename M::real>(h);
+  if constexpr (has_trajectory_params<M>::value)
+    if (h->plan.traj_params) {  // the same three launches with every lane's model copy set from its trajectory's row
+      const PerTrajectory<M> pm = per_trajectory(h, m);
+      if (what == RG_SEARCH)
+        hipLaunchKernelGGL((k_rollout_g<M, RG_SEARCH, true>), dim3((h->B + kSearchTraj - 1) / kSearchTraj), dim3(64), 0, h->stream, v, pm, al,
+                           cost_out, nullptr, mode, 0, h->sp.fixes);
+      else if (what == RG_INIT)
+        hipLaunchKernelGGL((k_rollout_g<M, RG_INIT, true>), dim3((h->B + 63) / 64), dim3(64), 0, h->stream, v, pm, al, cost_out, nullptr, 0, 1, h->sp.fixes);
+      else
+        hipLaunchKernelGGL((k_rollout_g<M, RG_COMMIT, true>), dim3((h->B + 63) / 64), dim3(64), 0, h->stream, v, pm, al, cost_out,
+                           h->commit_idx, 0, write_cost, h->sp.fixes);
+      HIPCHK(hipGetLastError());
+      return 0;
+    }
   if (what == RG_SEARCH)
     hipLaunchKernelGGL((k_rollout_g<M, RG_SEARCH>), dim3((h->B + kSearchTraj - 1) / kSearchTraj), dim3(64), 0, h->stream, v, m, al,
                        cost_out, nullptr, mode, 0, h->sp.fixes);
@@ -193,6 +215,17 @@ static int launch_derivatives(ilqr_batch* h, int force) {
       });
     } else if (int rc = with_generic_model(h, [&](auto& m) {
                  using M = std::decay_t<decltype(m)>;
+                 if constexpr (has_trajectory_params<M>::value)
+                   if (h->plan.traj_params) {
+                     const dim3 grid(h->B * (h->T + 1)), block(64);
+                     if constexpr (M::NU <= WM)
+                       if (f32) {
+                         hipLaunchKernelGGL((k_derivatives_g<M, float, true>), grid, block, 0, h->stream, h->vf, per_trajectory(h, m), force, -1);
+                         return 0;
+                       }
+                     hipLaunchKernelGGL((k_derivatives_g<M, double, true>), grid, block, 0, h->stream, h->v, per_trajectory(h, m), force, -1);
+                     return 0;
+                   }
                  if constexpr (M::NU <= WM) {
                    if (f32) {
                      hipLaunchKernelGGL((k_derivatives_g<M, float>), dim3(h->B * (h->T + 1)), dim3(64), 0, h->stream, h->vf, m, force, -1);

@@ -361,6 +361,17 @@ template <class M>
 struct has_analytic_record<M, std::void_t<decltype(std::declval<const M&>().analytic_record((const typename M::real*)nullptr, (const typename M::real*)nullptr,
                                                                                             typename M::real(0), false, (typename M::real*)nullptr))>> : std::true_type {};
 
+// does a device model take per-trajectory parameters (NTP, set_trajectory_params)?  Optional: without them every trajectory of a handle
+// sees the handle-wide parameters of ilqr_create and ilqr_set_trajectory_params answers ILQR_ERR_UNSUPPORTED.
+template <class M, class = void>
+struct has_trajectory_params : std::false_type {};
+template <class M>
+struct has_trajectory_params<M, std::void_t<decltype(M::NTP), decltype(std::declval<M&>().set_trajectory_params((const double*)nullptr))>> : std::true_type {};
+template <class M, bool = has_trajectory_params<M>::value>
+struct trajectory_params_count : std::integral_constant<int, 0> {};
+template <class M>
+struct trajectory_params_count<M, true> : std::integral_constant<int, M::NTP> {};
+
 }  // namespace ilqr
 
 // ------------------------------------------------------------------------------------------
@@ -379,7 +390,16 @@ struct has_analytic_record<M, std::void_t<decltype(std::declval<const M&>().anal
 //       __device__ real cost(const real* x, const real* u) const;                 // Model::cost
 //       __device__ real final_cost(const real* x) const;                          // Model::final_cost
 //       // optional: __device__ void analytic_record(const real* x, const real* u, real dt, bool last, real* rec) const;
+//       // optional, both or neither (per-trajectory parameters, ilqr_set_trajectory_params; generic kernels only):
+//       //   static constexpr int NTP = 8;                              // parameters per trajectory, 1 <= NTP <= 64
+//       //   __device__ void set_trajectory_params(const double* p);   // overwrite this copy's own parameter fields from p[NTP]
 //     };
+//
+// set_trajectory_params: a kernel calls it on ITS OWN copy of the model (the by-value kernel argument) with its trajectory's row of
+// ilqr_set_trajectory_params before the first evaluation; fields it does not write keep the handle-wide values of ilqr_create (user_params,
+// u_min / u_max).  p is always double -- UserModelT<float> casts; on an fp32 handle both twins are handed the float-rounded values, as
+// ilqr_create does for user_params.  It must NOT write u_min / u_max: the limits also feed the box-QP of the backward kernels, which
+// never see the model.
 //
 // It may use what this file offers (sincos_shared, Rec<>).  NX = 4 with NU = 1 or 2 runs in the tiled lane-quad kernels (the
 // persistent routes of the shipped acrobot / double integrator; both arithmetic flavours are instantiated: fp32 handles take
@@ -401,8 +421,11 @@ constexpr bool kUserQuad = UserModelT<double>::NX == 4 && (UserModelT<double>::N
 constexpr bool kUserSmall = !kUserQuad && UserModelT<double>::NX % 2 == 0 && UserModelT<double>::NX <= 8 && UserModelT<double>::NU <= 4;  // tiled thread kernels
 constexpr bool kUserTiled = kUserQuad || kUserSmall;   // has tiled kernels (trajectory-interleaved layout)
 constexpr bool kUserGeneric = !kUserQuad;              // has generic kernels (trajectory-contiguous layout, wavefront per trajectory)
+constexpr int kUserNTP = trajectory_params_count<UserModelT<double>>::value;  // per-trajectory parameters of the build's twin (0: none)
+static_assert(kUserNTP == trajectory_params_count<UserModelT<float>>::value, "UserModelT<float> and UserModelT<double> take the same per-trajectory parameters");
+static_assert(!has_trajectory_params<UserModelT<double>>::value || (kUserNTP >= 1 && kUserNTP <= 64), "user device models: 1 <= NTP <= 64");
 }  // namespace ilqr
 #define ILQR_HAVE_USER_MODEL 1
 #else
-namespace ilqr { constexpr bool kUserTiled = false, kUserSmall = false; }  // (no user twin in this build: ilqr_create's route inputs)
+namespace ilqr { constexpr bool kUserTiled = false, kUserSmall = false; constexpr int kUserNTP = 0; }  // (no user twin in this build: ilqr_create's route inputs)
 #endif

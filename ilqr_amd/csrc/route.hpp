@@ -27,6 +27,9 @@ struct RoutePlan {  // (the defaults: what ilqr_stage_kernel_name reports for a 
   Backward backward = Backward::thread;
   Rollout rollout = Rollout::tiled;
   Commit commit = Commit::tiled;
+  // per-trajectory model parameters are set (ilqr_set_trajectory_params ... ilqr_clear_trajectory_params): every launcher that hands the
+  // user twin to k_rollout_g / k_derivatives_g takes their PT instantiations.  The one part of the plan that changes after ilqr_create.
+  bool traj_params = false;
 };
 
 struct RouteInputs {
@@ -44,6 +47,11 @@ inline bool generic_layout(int model, int route, bool user_tiled, bool user_smal
 // the LQ model's line search on the matrix cores (k_rollout_lq is written for 32 x 16): what candidate buffers are allocated for
 inline bool lq_matrix_core_search(int model, int nu, int route) {
   return model == ILQR_MODEL_LQ && nu <= 16 && !(route & ILQR_ROUTE_LQ_THREAD_ROLLOUT);
+}
+
+// can this plan take per-trajectory model parameters?  Only where the model is touched by k_rollout_g and k_derivatives_g alone
+inline bool takes_trajectory_params(const RoutePlan& p) {
+  return p.rollout == Rollout::generic && p.derivatives == Derivatives::generic && p.commit == Commit::rerun;
 }
 
 inline RoutePlan plan_route(const RouteInputs& in) {

@@ -276,6 +276,25 @@ int ilqr_mpc_step(ilqr_batch* h, const double* x0, const void* x0_device, int sh
  * apply: t0 = 0, n_knots = the shift of the next step).  The window lies inside [0, T) and holds at least one knot. */
 int ilqr_copy_controls_to_device(ilqr_batch* h, int t0, int n_knots, void* u_device);
 
+/* ---- per-trajectory model parameters (additive under ABI 6) ----------------------------------------------------------------------
+ * A user device twin may declare NTP parameters that differ from trajectory to trajectory (csrc/models.hpp: NTP, set_trajectory_params) --
+ * a target that moves between receding-horizon steps, a perturbed model per trajectory.  Once set, every later rollout, derivative sweep
+ * and ilqr_mpc_step of the handle evaluates trajectory b's model with row b; what a model's set_trajectory_params does not write keeps the
+ * handle-wide values of ilqr_create (user_params, u_min / u_max).  An fp32 handle uses the rows' float-rounded values in both of its twins,
+ * as it does for user_params.  Setting parameters does NOT re-evaluate the stored cost or trajectory: a caller who changes them in the
+ * middle of a solve calls ilqr_warm_start or ilqr_mpc_step next (both roll out and cost again).  ilqr_get_derivatives returns what the last
+ * sweep left.  Only ILQR_MODEL_USER handles on the generic wavefront-per-trajectory kernels take them: ILQR_ERR_UNSUPPORTED for every other
+ * model, for a twin without the two members, for an nx = 4 twin (persistent tiled kernels) and for a small twin created without
+ * ILQR_ROUTE_WAVE_PER_TRAJECTORY; ilqr_last_error() names which. */
+int ilqr_trajectory_params_count(void); /* NTP of this build's user model, 0 = none; needs no device */
+/* p [B][n] double, n == NTP.  Exactly one of p (host) and p_device (this handle's device) is non-NULL.  Enqueued on the handle's stream,
+ * no synchronisation; a host array from page-locked memory must stay unchanged until the stream has passed the call (as x0 of
+ * ilqr_mpc_step).  The first call on a handle allocates the rows. */
+int ilqr_set_trajectory_params(ilqr_batch* h, const double* p, const void* p_device, int n);
+int ilqr_get_trajectory_params(ilqr_batch* h, double* p, int n); /* the rows as they were set; synchronises; ILQR_ERR_STATE while none are set */
+/* back to the handle-wide parameters of ilqr_create for every trajectory */
+int ilqr_clear_trajectory_params(ilqr_batch* h);
+
 /* ---- single stages (teacher-forced parity tests, host-model fallback) --------------------- */
 /* STEP 1, src/ilqr_core.cpp:115-120 = src/derivatives.cpp:15-144 over t = 0..T, all trajectories */
 int ilqr_compute_derivatives(ilqr_batch* h);

@@ -398,6 +398,24 @@ class BatchILQR {
   void copy_controls_to_device(int t0, int n_knots, void* u_device) {
     check(ilqr_copy_controls_to_device(h_, t0, n_knots, u_device), "ilqr_copy_controls_to_device");
   }
+  // Per-trajectory model parameters of a user device twin (NTP, set_trajectory_params: csrc/models.hpp) on the generic kernels: row b is
+  // trajectory b's model for every later rollout, sweep and mpc_step.  The stored cost is not re-evaluated: warm-start or mpc_step next.
+  void set_trajectory_params(const std::vector<double>& p) {
+    const int n = ilqr_trajectory_params_count();
+    require(n > 0 && p.size() == (size_t)B_ * n, "set_trajectory_params: p [B][NTP]");
+    check(ilqr_set_trajectory_params(h_, p.data(), nullptr, n), "ilqr_set_trajectory_params");
+  }
+  // p_device: [B][NTP] double in device memory of the handle's device; enqueued on the handle's stream, nothing waited for
+  void set_trajectory_params(const void* p_device) {
+    check(ilqr_set_trajectory_params(h_, nullptr, p_device, ilqr_trajectory_params_count()), "ilqr_set_trajectory_params");
+  }
+  std::vector<double> trajectory_params() {
+    const int n = ilqr_trajectory_params_count();
+    std::vector<double> p((size_t)B_ * (n > 0 ? n : 1));
+    check(ilqr_get_trajectory_params(h_, p.data(), n), "ilqr_get_trajectory_params");
+    return p;
+  }
+  void clear_trajectory_params() { check(ilqr_clear_trajectory_params(h_), "ilqr_clear_trajectory_params"); }
   std::vector<int> status() {
     std::vector<int> s(B_);
     check(ilqr_get_status(h_, s.data(), nullptr, nullptr), "ilqr_get_status");
