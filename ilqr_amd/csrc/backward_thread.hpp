@@ -2,6 +2,7 @@
 // trajectory with the generic box_qp<M>: the cross-check of the quad kernel (ILQR_FLAG_BACKWARD_THREAD_PER_TRAJ).
 #pragma once
 #include "derivatives.hpp"
+#include "pass_driver.hpp"
 
 namespace ilqr {
 
@@ -286,8 +287,8 @@ __global__ __launch_bounds__(64) void k_backward_t(BatchViewT<typename M::real> 
       break;
     }
     if (diverge != 0) {  // :142-148
-      dlambda = fmax(dlambda * sp.lambda_factor, sp.lambda_factor);
-      lambda = fmax(lambda * dlambda, sp.lambda_min);
+      dlambda = raised_dlambda(dlambda, sp);
+      lambda = raised_lambda(lambda, dlambda, sp);
       if (lambda > sp.lambda_max) break;
       continue;
     }
@@ -316,7 +317,7 @@ __global__ __launch_bounds__(64) void k_backward_t(BatchViewT<typename M::real> 
   }
   const double gnorm = acc / T;
   v.gnorm[b] = gnorm;
-  if (mode == 1 && !sp.fixed_work && gnorm < sp.tol_grad && lambda < 1e-5) {  // :154-159
+  if (mode == 1 && !sp.fixed_work && gnorm < sp.tol_grad && lambda < kLambdaConverged) {  // :154-159
     v.status[b] = 1;
     v.iters[b] += 1;  // this iteration was started
   }

@@ -24,6 +24,7 @@
 // 32 x 32 scratch matrix for the transpose in Vxx <- (Vn + Vn')/2, K for the rare stale-factor path.
 #pragma once
 #include "backward_wave.hpp"
+#include "pass_driver.hpp"
 
 namespace ilqr {
 
@@ -441,8 +442,8 @@ __global__ __launch_bounds__(64, NT == 2 ? 2 : 3) void k_backward_w2(BatchView v
       break;
     }
     if (diverge != 0) {  // :142-148
-      dlambda = fmax(dlambda * sp.lambda_factor, sp.lambda_factor);
-      lambda = fmax(lambda * dlambda, sp.lambda_min);
+      dlambda = raised_dlambda(dlambda, sp);
+      lambda = raised_lambda(lambda, dlambda, sp);
       if (lambda > sp.lambda_max) break;
       continue;
     }
@@ -473,7 +474,7 @@ __global__ __launch_bounds__(64, NT == 2 ? 2 : 3) void k_backward_w2(BatchView v
     if (mode == 1) {
       v.lambda[b] = lambda;
       v.dlambda[b] = dlambda;
-      if (!sp.fixed_work && gnorm < sp.tol_grad && lambda < 1e-5) {
+      if (!sp.fixed_work && gnorm < sp.tol_grad && lambda < kLambdaConverged) {
         v.status[b] = 1;
         v.iters[b] += 1;
       }

@@ -929,8 +929,8 @@ __global__ __launch_bounds__(64, MT == 2 ? 1 : NT == 2 ? ILQR_W3_NT2_WAVES : ILQ
       break;
     }
     if (diverge != 0) {  // :142-148
-      dlambda = fmax(dlambda * sp.lambda_factor, sp.lambda_factor);
-      lambda = fmax(lambda * dlambda, sp.lambda_min);
+      dlambda = raised_dlambda(dlambda, sp);
+      lambda = raised_lambda(lambda, dlambda, sp);
       if (lambda > sp.lambda_max) break;
       continue;
     }
@@ -961,7 +961,7 @@ __global__ __launch_bounds__(64, MT == 2 ? 1 : NT == 2 ? ILQR_W3_NT2_WAVES : ILQ
     if (mode == 1) {
       v.lambda[b] = lambda;
       v.dlambda[b] = dlambda;
-      if (!sp.fixed_work && gnorm < sp.tol_grad && lambda < 1e-5) {
+      if (!sp.fixed_work && gnorm < sp.tol_grad && lambda < kLambdaConverged) {
         v.status[b] = 1;
         v.iters[b] += 1;
       }

@@ -244,8 +244,8 @@ __device__ __forceinline__ void backward_wide2(const BatchViewT<typename M::real
       break;
     }
     if (diverge != 0) {  // :142-148
-      dlambda = fmax(dlambda * sp.lambda_factor, sp.lambda_factor);
-      lambda = fmax(lambda * dlambda, sp.lambda_min);
+      dlambda = raised_dlambda(dlambda, sp);
+      lambda = raised_lambda(lambda, dlambda, sp);
       if (lambda > sp.lambda_max) break;
       continue;
     }
@@ -277,7 +277,7 @@ __device__ __forceinline__ void backward_wide2(const BatchViewT<typename M::real
   if (mode == 1) {
     v.lambda[b] = lambda;
     v.dlambda[b] = dlambda;
-    if (!sp.fixed_work && gnorm < sp.tol_grad && lambda < 1e-5) {  // :154-159
+    if (!sp.fixed_work && gnorm < sp.tol_grad && lambda < kLambdaConverged) {  // :154-159
       v.status[b] = 1;
       v.iters[b] += 1;
     }
