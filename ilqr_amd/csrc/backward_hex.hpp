@@ -44,29 +44,63 @@ constexpr bool kHexCandT = ILQR_HEX_CAND_T != 0;
 
 // One pair's ring: a slot holds one knot of the sub-tile's 4 trajectories, pair-interleaved like the HBM records:
 // [pair][trajectory lp][2].
-template <int NX, int NU, class real, int SLOTS_>
+// COMPACT (a model with a state_free_running_cost, models.hpp): the slot is a CompactRec (derivatives.hpp) -- 12 pair rows instead
+// of 24 and the knot's one number Z = c - c, which stands for its cx, cxx and cxu, in the first half of the pad row; knot T,
+// whose cx and cxx are final_cost's, has an area of its own beside the ring (HexPair::term).
+template <int NX, int NU, class real, int SLOTS_, bool COMPACT_ = false>
 struct HexRing {
+  static constexpr bool COMPACT = COMPACT_;
   static constexpr int US = Rec<NX, NU>::SIZE;
-  static constexpr int PAIRS = (Rec<NX, NU>::SIZE + NU + 1) / 2;
+  static constexpr int PAIRS = COMPACT ? CompactRec<NX, NU>::PAIRS : (Rec<NX, NU>::SIZE + NU + 1) / 2;
   static constexpr int ROW = 2 * HT;             // `real`s from one element pair to the next
   static constexpr int PAD = ROW - 2 * TW;       // what derivatives_of_knot adds to its 16-trajectory row (negative: a narrower row)
   // SLOT_PAD: a producer round writes 16 knots = 16 consecutive slots with one store instruction per pair row; unpadded the slot
   // stride (1536 bytes in double) is a whole number of bank rows and the knots of a lane group land on the same banks (a 2-way
   // conflict on every one of a round's 24 stores); 8 `real`s further on each, the two (fp32: four) knots of a group sit side by side.
+  // COMPACT, 12 rows: unpadded the stride is 768 bytes in double, three whole bank rows of 256 bytes -- the same conflict.  With the
+  // 8 `real`s the stride is 832 = 3 x 256 + 64 bytes: the four knots that share a bank row (16 lanes x 16 bytes) start 0, 64, 128, 192
+  // bytes into it, each 64 bytes long.  In float 416 bytes: the eight knots of a 32-lane group start 0, 160, 64, 224, 128, 32, 192, 96
+  // bytes into the bank row, each 32 bytes long.  Every byte offset once in both: the same pad serves 12 rows, and it is where Z lives.
   static constexpr int ELEMS = PAIRS * ROW + ILQR_HEX_SLOT_PAD;
+  static constexpr int Z = PAIRS * ROW;          // COMPACT: Z of trajectory lp at Z + 2 lp
+  static_assert(!COMPACT || ILQR_HEX_SLOT_PAD >= ROW, "the compact slot keeps Z in its pad row");
+  static_assert(!COMPACT || (NX == 4 && NU == 1), "compact slots: nx = 4, nu = 1");
   static constexpr int SLOTS = SLOTS_;
   static constexpr bool PERM = (ILQR_HEX_PAIR_PERM != 0) && NX == 4 && NU == 1;
-  static constexpr int pos(int pair) { return PERM ? hex_pair_pos(pair) : pair; }
+  // fx keeps its rows in both layouts (pairs 0..7, hex_pair_pos); nothing else of the compact slot is permuted
+  static constexpr int pos(int pair) { return PERM && (!COMPACT || pair < 8) ? hex_pair_pos(pair) : pair; }
 };
 
 constexpr int kHexKnotsPerRound = 64 / HT;       // a producer round: 16 knots x 4 trajectories
-constexpr int kHexSlots = 24;
-constexpr int kHexLead = 7;                      // a round may be written once its first knot is at most this far ahead of the consumer
-static_assert(kHexSlots > kHexLead + kHexKnotsPerRound - 1, "a round must not reach a slot the chain has not left");
+// The LDS a pair's records may take is what 24 full slots take (4 pairs x 24 x 1 600 B = 154 KB in double: one block per CU);
+// a compact slot is about half a full one, so the same bytes -- less the knot-T area -- hold 45 of them.
+constexpr int kHexFullSlots = 24;
+template <int NX, int NU, class real, bool COMPACT>
+struct HexRingSize {
+  using Full = HexRing<NX, NU, real, kHexFullSlots, false>;
+  static constexpr int TERM = COMPACT ? ((NX + NX * NX) / 2) * Full::ROW : 0;  // `real`s of the knot-T area: 10 pair rows x 4 trajectories
+  static constexpr int SLOTS = COMPACT ? (kHexFullSlots * Full::ELEMS - TERM) / HexRing<NX, NU, real, 1, COMPACT>::ELEMS : kHexFullSlots;
+  // a round may be written once its first knot is at most LEAD knots ahead of the consumer: the whole ring but a round and a knot
+  // to spare (24 full slots: 7; 45 compact ones: 28)
+  static constexpr int LEAD = SLOTS - kHexKnotsPerRound - 1;
+  static_assert(SLOTS > LEAD + kHexKnotsPerRound - 1 && LEAD >= 1, "a round must not reach a slot the chain has not left");
+  static_assert(SLOTS * HexRing<NX, NU, real, 1, COMPACT>::ELEMS + TERM <= kHexFullSlots * Full::ELEMS, "the pair's records fit the bytes of 24 full slots");
+};
 
-template <class real, int NX, int NU>
-struct HexPair {  // LDS of one (chain, producer) pair
-  using RS = HexRing<NX, NU, real, kHexSlots>;
+template <class real, int N>
+struct HexTerm {
+  alignas(16) real term[N];           // cx, cxx of knot T for the pair's 4 trajectories: [pair][trajectory lp][2], written by the producer in round 0 of every pass
+};
+template <class real>
+struct HexTerm<real, 0> {
+  static constexpr real* term = nullptr;
+};
+
+template <class real, int NX, int NU, bool COMPACT = false>
+struct HexPair : HexTerm<real, HexRingSize<NX, NU, real, COMPACT>::TERM> {  // LDS of one (chain, producer) pair
+  using Size = HexRingSize<NX, NU, real, COMPACT>;
+  using RS = HexRing<NX, NU, real, Size::SLOTS, COMPACT>;
+  static constexpr int LEAD = Size::LEAD;
   alignas(16) real ring[RS::SLOTS * RS::ELEMS];  // (16-byte aligned: the rollouts read it in row pairs, rollout.hpp)
   int rounds_done;                    // rounds (counted across passes) whose records are in the ring
   int consumer_at;                    // running index of the knot the chain waits for (everything below is consumed)
@@ -181,7 +215,7 @@ __device__ __forceinline__ void qp1_search_hex(QP1StateT<double>& q, int j, int 
 
 // RS::pos for a pair index that depends on the lane (computed once per wavefront: the addresses are loop invariants)
 template <class RS>
-__device__ __forceinline__ int hex_pos_rt(int pair) { return RS::PERM ? hex_pair_pos(pair) : pair; }
+__device__ __forceinline__ int hex_pos_rt(int pair) { return RS::pos(pair); }
 
 template <class real>
 struct HexStep {  // what lane (r, t, c) needs of one derivative record, as loaded (widened to the chain's arithmetic when used)
@@ -193,7 +227,8 @@ struct HexStep {  // what lane (r, t, c) needs of one derivative record, as load
 // One sub-tile's backward pass: run by ONE wavefront, lane = 16 r + 4 t + c.  Records from the pair's ring.
 template <class M, class Gate, class RS>
 __device__ __forceinline__ void backward_hex(const BatchViewT<typename M::real>& v, const M& model, const SolverParams& sp, int mode, int tile, int sub,
-                                             int lane, const double* __restrict__ lds_steps, Gate& gate, const typename M::real* __restrict__ ring) {
+                                             int lane, const double* __restrict__ lds_steps, Gate& gate, const typename M::real* __restrict__ ring,
+                                             const typename M::real* __restrict__ term /* knot T's cx, cxx (compact ring) */) {
   using real = typename M::real;   // what is stored per knot
   using creal = double;            // what the recursion computes in (backward_quad.hpp)
   static_assert(M::NX == 4 && M::NU == 1, "hex chain: nx = 4, nu = 1");
@@ -220,6 +255,17 @@ __device__ __forceinline__ void backward_hex(const BatchViewT<typename M::real>&
     lds_cd* r = (lds_cd*)(ring + gate.slot(t) * RS::ELEMS + t_ * 2);
     auto pair = [&](int e) { return *(lds_cd2*)(r + RS::pos(e >> 1) * RS::ROW); };   // (constant e)
     auto one = [&](int e) { return r[hex_pos_rt<RS>(e >> 1) * RS::ROW + (e & 1)]; };  // (e depends on the lane)
+    if constexpr (RS::COMPACT) {
+      // five loads instead of nine: the knot's cx, cxx, cxu entries are all the one value Z (+0.0, or NaN with an overflowing
+      // cost).  The step below still ADDS them (-0.0 + 0.0 is +0.0: a dropped addition would change signs of zero).
+      using C = CompactRec<4, 1>;
+      d.F = one(C::FX + r_ + 4 * c_);
+      d.fu_r = one(C::FU + r_);
+      d.cxx_rc = d.cxx_cr = d.cx_r = d.cxu_r = d.cxu_c = r[RS::Z];
+      d.tail = pair(C::CU);
+      d.uw = pair(C::US);
+      return;
+    }
     d.F = one(R::FX + r_ + 4 * c_);
     d.cxx_rc = one(R::CXX + r_ + 4 * c_);
     d.cxx_cr = one(R::CXX + c_ + 4 * r_);
@@ -239,10 +285,17 @@ __device__ __forceinline__ void backward_hex(const BatchViewT<typename M::real>&
     creal V, RVx, kprev;   // Vxx'[r][c] (D layout), Vx'[r] (replicated over c)
     const creal lam_r = (creal)lambda;
     {
-      gate.wait(T);
+      gate.wait(T);  // (compact ring: knot T keeps its place in the count -- its slot stays empty -- and its round carries the term area)
+      if constexpr (RS::COMPACT) {
+        using C = CompactRec<4, 1>;
+        lds_cd* r = (lds_cd*)(term + t_ * 2);
+        RVx = (creal)r[((C::TERM_CX + r_) >> 1) * RS::ROW + ((C::TERM_CX + r_) & 1)];                          // :353
+        V = (creal)r[((C::TERM_CXX + r_ + 4 * c_) >> 1) * RS::ROW + ((C::TERM_CXX + r_ + 4 * c_) & 1)];        // :354
+      } else {
       lds_cd* r = (lds_cd*)(ring + gate.slot(T) * RS::ELEMS + t_ * 2);
       RVx = (creal)r[hex_pos_rt<RS>((R::CX + r_) >> 1) * RS::ROW + ((R::CX + r_) & 1)];                        // :353
       V = (creal)r[hex_pos_rt<RS>((R::CXX + r_ + 4 * c_) >> 1) * RS::ROW + ((R::CXX + r_ + 4 * c_) & 1)];    // :354
+      }
     }
     kprev = (creal)kt[(unsigned)((T - 1) * TW)];
     // (gfx950 counts stores in vmcnt too: with this load still "in flight" at the loop header the compiler made every step wait for
@@ -441,7 +494,7 @@ __device__ __forceinline__ void sweep_backward_hex(const BatchViewT<typename M::
   if (role < 4) {
     __builtin_amdgcn_s_setprio(3);
     HexGate<P> gate(sh, T);
-    backward_hex<M, decltype(gate), RS>(v, model, sp, mode, tile, role, lane, lds_steps, gate, sh.ring);
+    backward_hex<M, decltype(gate), RS>(v, model, sp, mode, tile, role, lane, lds_steps, gate, sh.ring, sh.term);
     gate.finish();
     __builtin_amdgcn_s_setprio(0);
   } else {
@@ -461,12 +514,17 @@ __device__ __forceinline__ void sweep_backward_hex(const BatchViewT<typename M::
       const bool mine = (lanes >> (4 * lp)) & 1ull;  // does trajectory lp take part in this pass?  (its chain lanes are 16 r + 4 lp + c)
       for (int r = 0; r < nrounds; r++) {
         const int j0 = r * kHexKnotsPerRound, G0 = pass * N + j0;
-        while (G0 > __hip_atomic_load(&sh.consumer_at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) + kHexLead) __builtin_amdgcn_s_sleep(4);
+        while (G0 > __hip_atomic_load(&sh.consumer_at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) + P::LEAD) __builtin_amdgcn_s_sleep(4);
         const int started = __hip_atomic_load(&sh.passes_started, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         if ((started < 0) | (started > pass + 1)) break;  // the chain has left this pass behind
         const int t = T - (j0 + ks);
-        if (t >= 0 && (pass == 0 || mine))
-          derivatives_of_knot<M, true, MFD, RS::PAD, RS::PERM>(v, model, fdm, force, nullptr, tile, t, l, sh.ring + ((G0 + ks) % RS::SLOTS) * RS::ELEMS + lp * 2, true);
+        if (t >= 0 && (pass == 0 || mine)) {
+          typename M::real* rs = sh.ring + ((G0 + ks) % RS::SLOTS) * RS::ELEMS + lp * 2;
+          if constexpr (RS::COMPACT) {
+            if (t == T) rs = sh.term + lp * 2;  // (lanes 0..3 of round 0: the chain reads it once per pass, behind this round's release)
+          }
+          derivatives_of_knot<M, true, MFD, RS::PAD, RS::PERM, RS::COMPACT>(v, model, fdm, force, nullptr, tile, t, l, rs, true);
+        }
         __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the round's LDS writes are done
         if (lane == 0) __hip_atomic_store(&sh.rounds_done, pass * nrounds + r + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
@@ -581,7 +639,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                                                                                                  int* __restrict__ commit_idx, int commit_pending,
                                                                                                  long long* __restrict__ phase_ticks) {
   using real = typename M::real;
-  using P = HexPair<real, M::NX, M::NU>;
+  using P = HexPair<real, M::NX, M::NU, state_free_running_cost<M>::value>;
   __shared__ P pairs[4];
   __shared__ double steps[104];  // (the chain runs in double for every handle)
   __shared__ double lds_cost[NALPHA * TW];

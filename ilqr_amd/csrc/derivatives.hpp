@@ -10,7 +10,7 @@ namespace ilqr {
 // ------------------------------------------------------------------------------------------
 // include/finite_diff.h:67-86 applied to a scalar functor of an N-vector.
 template <int N, class real, class F>
-__device__ __forceinline__ void fd_hessian(const real* x, F f, real* out /* N x N col-major */) {
+__host__ __device__ __forceinline__ void fd_hessian(const real* x, F f, real* out /* N x N col-major */) {
 #pragma unroll
   for (int i = 0; i < N; i++)
 #pragma unroll
@@ -33,7 +33,7 @@ __device__ __forceinline__ void fd_hessian(const real* x, F f, real* out /* N x 
 }
 // include/finite_diff.h:22-33
 template <int N, class real, class F>
-__device__ __forceinline__ void fd_gradient(const real* x, F f, real* out) {
+__host__ __device__ __forceinline__ void fd_gradient(const real* x, F f, real* out) {
 #pragma unroll
   for (int i = 0; i < N; i++) {
     real p[N], m[N];
@@ -88,7 +88,20 @@ __host__ __device__ constexpr int hex_pair_pos(int p) {
   const int a = (q >> 2) & 1, b = (q >> 1) & 1, c = q & 1;
   return (p - q) + 4 * a + 2 * b + (a ^ c);
 }
-template <class M, bool RING = false, class MFD = M, int RING_PAD = 0, bool PERM = false>
+// The compact ring slot of a model with a state_free_running_cost (models.hpp), nx = 4, nu = 1: what the chain needs of a knot
+// t < T is fx, fu, (cu, cuu), (u, 1 / (|u| + 1)) -- 24 elements, 12 pair rows, fx in the rows hex_pair_pos gives it -- and Z, the
+// value c - c that every cx, cxx, cxu entry of the knot is (times a constant): in the first pad row behind the 12.  Knot T has
+// no slot: its cx (4) and cxx (16), the only entries the chain reads of it, go to an area of their own, 10 pair rows, unpermuted.
+template <int NX, int NU>
+struct CompactRec {
+  static constexpr int FX = 0, FU = FX + NX * NX, CU = FU + NX * NU, CUU = CU + NU, US = CUU + NU * NU, SIZE = US + NU + 1;
+  static constexpr int PAIRS = SIZE / 2;                 // 12
+  static constexpr int Z = 2 * PAIRS;                    // (element index: pair row PAIRS, first half)
+  static constexpr int TERM_CX = 0, TERM_CXX = NX, TERM_PAIRS = (NX + NX * NX) / 2;
+  static constexpr int pos(int pair, bool perm) { return (perm && pair < 8) ? hex_pair_pos(pair) : pair; }
+};
+// COMPACT (with RING): `rs` is a compact slot (t < T) or the pair's knot-T area (t == T), see CompactRec.
+template <class M, bool RING = false, class MFD = M, int RING_PAD = 0, bool PERM = false, bool COMPACT = false>
 __device__ __forceinline__ void derivatives_of_knot(const BatchViewT<typename M::real>& v, const M& model, const MFD& fdm, int force,
                                                     const int* __restrict__ commit_idx, int tile, int t, int l,
                                                     typename M::real* rs = nullptr, bool records = true) {
@@ -97,6 +110,9 @@ __device__ __forceinline__ void derivatives_of_knot(const BatchViewT<typename M:
   using RSl = RingSlot<M::NX, M::NU, real>;
   constexpr int NX = M::NX, NU = M::NU;
   using R = Rec<NX, NU>;
+  // (both models: the rollouts' M names the layout, the finite differences' MFD is the cost whose c - c is stored)
+  static_assert(!COMPACT || (RING && state_free_running_cost<M>::value && state_free_running_cost<MFD>::value),
+                "compact records: the ring of a model whose running cost ignores the state");
   typedef real real2_t __attribute__((ext_vector_type(2)));
   const int b = tile * TW + l;
   const int T = v.T;
@@ -132,6 +148,88 @@ __device__ __forceinline__ void derivatives_of_knot(const BatchViewT<typename M:
   }
   if (!want) return;  // (finished trajectory whose last candidate was committed above)
 
+  if constexpr (COMPACT) {
+    using C = CompactRec<NX, NU>;
+    constexpr int ROW = 2 * TW + RING_PAD;
+    auto cput2 = [&](int row, fdr v0, fdr v1) {
+      real2_t w;
+      w.x = (real)v0;
+      w.y = (real)v1;
+      *reinterpret_cast<real2_t*>(rs + row * ROW) = w;
+    };
+    const bool exact = has_analytic_record<M>::value && v.analytic;  // (wave-uniform)
+    real rec[R::SIZE];
+    if constexpr (has_analytic_record<M>::value) {
+      if (exact) model.analytic_record(xk, uk, dt, t == T, rec);  // zero-fills cx, cxx, cxu of a knot t < T: Z = 0
+    }
+    fdr x[NX], u[NU];
+#pragma unroll
+    for (int i = 0; i < NX; i++) x[i] = (fdr)xk[i];
+#pragma unroll
+    for (int j = 0; j < NU; j++) u[j] = (fdr)uk[j];
+    const fdr dtf = (fdr)dt;
+    const fdr inv2eps = fdr(1.0 / (2 * kEps));
+    if (t == T) {  // cx, cxx of final_cost (derivatives.cpp:49, :92), the expressions of the full record below
+      fdr g[NX], H[NX * NX];
+      if (exact) {
+#pragma unroll
+        for (int i = 0; i < NX; i++) g[i] = (fdr)rec[R::CX + i];
+#pragma unroll
+        for (int e = 0; e < NX * NX; e++) H[e] = (fdr)rec[R::CXX + e];
+      } else {
+        fd_gradient<NX>(x, [&](const fdr* xx) { return fdm.final_cost(xx); }, g);
+        fd_hessian<NX>(x, [&](const fdr* xx) { return fdm.final_cost(xx); }, H);
+      }
+#pragma unroll
+      for (int i = 0; i < NX; i += 2) cput2((C::TERM_CX + i) >> 1, g[i], g[i + 1]);
+#pragma unroll
+      for (int e = 0; e < NX * NX; e += 2) cput2((C::TERM_CXX + e) >> 1, H[e], H[e + 1]);
+      return;
+    }
+    rs[(C::US >> 1) * ROW] = uk[0];
+    rs[(C::US >> 1) * ROW + 1] = recip(abs_of(uk[0]) + real(1));  // the weight of this knot's gradient-norm term, as below
+    if (exact) {
+#pragma unroll
+      for (int e = 0; e < NX * NX + NX * NU; e += 2) cput2(C::pos((C::FX + e) >> 1, PERM), (fdr)rec[R::FX + e], (fdr)rec[R::FX + e + 1]);
+      cput2(C::CU >> 1, (fdr)rec[R::CU], (fdr)rec[R::CUU]);
+      rs[(C::Z >> 1) * ROW] = real(0);
+      return;
+    }
+    // fx, fu, cu, cuu: the expressions of the full record below, operand for operand
+#pragma unroll
+    for (int i = 0; i < NX; i++) {
+      fdr p[NX], m[NX], fp[NX], fm[NX];
+#pragma unroll
+      for (int q = 0; q < NX; q++) p[q] = m[q] = x[q];
+      p[i] += fdr(kEps);
+      m[i] -= fdr(kEps);
+      integrate_dynamics(fdm, p, u, dtf, fp);
+      integrate_dynamics(fdm, m, u, dtf, fm);
+#pragma unroll
+      for (int r = 0; r < NX; r += 2)
+        cput2(C::pos((C::FX + r + NX * i) >> 1, PERM), (fp[r] - fm[r]) * inv2eps, (fp[r + 1] - fm[r + 1]) * inv2eps);
+    }
+    {
+      fdr p[NU], m[NU], fp[NX], fm[NX];
+      p[0] = m[0] = u[0];
+      p[0] += fdr(kEps);
+      m[0] -= fdr(kEps);
+      integrate_dynamics(fdm, x, p, dtf, fp);
+      integrate_dynamics(fdm, x, m, dtf, fm);
+#pragma unroll
+      for (int r = 0; r < NX; r += 2)
+        cput2((C::FU + r) >> 1, (fp[r] - fm[r]) * inv2eps, (fp[r + 1] - fm[r + 1]) * inv2eps);
+    }
+    fdr g[NU], H[NU * NU];
+    fd_gradient<NU>(u, [&](const fdr* uu) { return fdm.cost(x, uu); }, g);
+    fd_hessian<NU>(u, [&](const fdr* uu) { return fdm.cost(x, uu); }, H);
+    cput2(C::CU >> 1, g[0], H[0]);
+    // every entry of cx, cxx, cxu is ((c - c) ...) x constant: +0.0 for a finite c, NaN otherwise.  Not folded to a literal:
+    // an overflowing control must poison the chain exactly as the full record's entries do.
+    const fdr c = fdm.cost(x, u);
+    rs[(C::Z >> 1) * ROW] = (real)(c - c);
+    return;
+  }
   real* D = RING ? nullptr : v.D + didx(tile, t, 0, l, T + 1, R::SIZE);
   auto put = [&](int e, fdr val_) {
     const real val = (real)val_;

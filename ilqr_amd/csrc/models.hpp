@@ -234,8 +234,9 @@ struct AcrobotModelT {
     rec[R::CU] = 2 * real(0.1) * real(0.1) * u[0];
   }
 
-  // acrobot.h:83-92: Ks = Kd = 0, Kr = 0.1 -> the state terms are exact zeros for finite x
-  __device__ __forceinline__ real cost(const real* x, const real* u) const {
+  // acrobot.h:83-92: Ks = Kd = 0, Kr = 0.1 -> the state terms are exact zeros for finite x (state_free_running_cost below;
+  // __host__ too: tests/test_state_free_cost_on_host.py evaluates the finite differences of this function on the CPU)
+  __host__ __device__ __forceinline__ real cost(const real* x, const real* u) const {
     // contraction by the source, not by the optimiser: every inlined copy of this function (rollout kernels, the
     // persistent kernel, the commit / getter re-integration, the finite differences) must round identically
 #pragma clang fp contract(on)
@@ -360,6 +361,15 @@ struct has_analytic_record : std::false_type {};
 template <class M>
 struct has_analytic_record<M, std::void_t<decltype(std::declval<const M&>().analytic_record((const typename M::real*)nullptr, (const typename M::real*)nullptr,
                                                                                             typename M::real(0), false, (typename M::real*)nullptr))>> : std::true_type {};
+
+// does M::cost(x, u) never read x?  Then the cx, cxx and cxu of every knot t < T are finite differences of one value c = cost(x, u)
+// with itself: c - c scaled (+0.0 for a finite c, NaN for an overflowing one), and the matrix-core chain's ring carries that one
+// number per knot instead of the 24 entries (derivatives.hpp: COMPACT, backward_hex.hpp).  Knot T is not concerned: its cx, cxx
+// come from final_cost.  Declared per model, never deduced; a user twin keeps the full record.
+template <class M>
+struct state_free_running_cost : std::false_type {};
+template <class real>
+struct state_free_running_cost<AcrobotModelT<real>> : std::true_type {};
 
 // does a device model take per-trajectory parameters (NTP, set_trajectory_params)?  Optional: without them every trajectory of a handle
 // sees the handle-wide parameters of ilqr_create and ilqr_set_trajectory_params answers ILQR_ERR_UNSUPPORTED.
