@@ -288,6 +288,20 @@ class BatchILQR:
     def copy_gains_to_device(self, k_ptr=None, K_ptr=None):
         self._check(self.lib.ilqr_copy_gains_to_device(self.h, k_ptr, K_ptr))
 
+    def value(self, t0=0, n=None):
+        """The value model of the stored policy over the knots [t0, t0 + n) (n=None: up to knot T): Vx [B][n][nx], Vxx [B][n][nx][nx]
+        (include/ilqr_amd.h, ilqr_get_value: recomputed on the device from the current records and the stored gains; synchronises)."""
+        n = self.T + 1 - int(t0) if n is None else int(n)
+        Vx = np.zeros((self.B, max(n, 0), self.nx))
+        Vxx = np.zeros((self.B, max(n, 0), self.nx, self.nx))  # memory: column-major nx x nx
+        self._check(self.lib.ilqr_get_value(self.h, int(t0), n, _p(Vx), _p(Vxx)))
+        return Vx, np.swapaxes(Vxx, -1, -2)
+
+    def copy_value_to_device(self, t0, n, Vx_ptr=None, Vxx_ptr=None):
+        """The same window as float64 [B][n][nx] / [B][n][nx*nx] (column-major per knot) into caller-owned device memory (raw pointers,
+        e.g. torch.Tensor.data_ptr(); either may be None); enqueued on the handle's stream, nothing waited for."""
+        self._check(self.lib.ilqr_copy_value_to_device(self.h, int(t0), int(n), Vx_ptr, Vxx_ptr))
+
     def derivatives(self):
         n, m, B, T1 = self.nx, self.nu, self.B, self.T + 1
         mem = dict(fx=np.zeros((B, T1, n, n)), fu=np.zeros((B, T1, m, n)), cx=np.zeros((B, T1, n)),

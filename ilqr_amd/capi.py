@@ -56,6 +56,8 @@ SYMBOLS = {
     "ilqr_shift_horizon": (C.c_int, [_H, C.c_int, C.c_int]),
     "ilqr_mpc_step": (C.c_int, [_H, _dp, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "ilqr_copy_controls_to_device": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
+    "ilqr_get_value": (C.c_int, [_H, C.c_int, C.c_int, _dp, _dp]),
+    "ilqr_copy_value_to_device": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ilqr_trajectory_params_count": (C.c_int, []),
     "ilqr_set_trajectory_params": (C.c_int, [_H, _dp, C.c_void_p, C.c_int]),
     "ilqr_get_trajectory_params": (C.c_int, [_H, _dp, C.c_int]),

@@ -20,6 +20,8 @@
 #include "kernels_wide.hpp"
 #include "kernels_wide2.hpp"
 #include "kernels.hpp"
+#include "value_thread.hpp"
+#include "value_wave.hpp"
 
 using namespace ilqr;
 
@@ -744,6 +746,46 @@ int ilqr_copy_controls_to_device(ilqr_batch* h, int t0, int n_knots, void* u_dev
   if (!h->initialised) return fail(ILQR_ERR_STATE, "copy_controls_to_device before ilqr_init_traj/ilqr_set_trajectory");
   HIPCHK(hipSetDevice(h->device));
   return to_canonical(h, {h->v.us, h->T, h->nu, t0, n_knots}, (double*)u_device);
+}
+
+// ---- the value model of the stored policy (additive under ABI 6) ---------------------------------
+// every refusal the two calls share, then the records as ilqr_get_derivatives would return them now
+static int prepare_value(ilqr_batch* h, int t0, int n_knots, const void* Vx, const void* Vxx, const char* who) {
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  REQUIRE(t0 >= 0 && n_knots >= 1 && t0 <= h->T && n_knots <= h->T + 1 - t0, "%s: window [%d, %d): inside [0, T = %d], at least one knot", who, t0, t0 + n_knots, h->T);
+  REQUIRE(Vx || Vxx, "%s: Vx and Vxx are both null", who);
+  if (!h->initialised) return fail(ILQR_ERR_STATE, "%s before ilqr_init_traj/ilqr_set_trajectory: no policy is stored", who);
+  HIPCHK(hipSetDevice(h->device));
+  return materialise_records(h);
+}
+static int run_value(ilqr_batch* h, int t0, int n_knots, double* Vx, double* Vxx, const char* who) {
+  const char* kernel = "";
+  const int rc = launch_value(h, t0, n_knots, Vx, Vxx, &kernel);
+  if (rc == ILQR_ERR_HIP) {  // (the launch itself was refused: say which kernel)
+    char keep[sizeof(g_err)];
+    memcpy(keep, g_err, sizeof(keep));
+    return fail(rc, "%s: %s: %.400s", who, kernel, keep);
+  }
+  return rc;
+}
+
+int ilqr_copy_value_to_device(ilqr_batch* h, int t0, int n_knots, void* Vx_device, void* Vxx_device) {
+  if (int rc = prepare_value(h, t0, n_knots, Vx_device, Vxx_device, "ilqr_copy_value_to_device")) return rc;
+  return run_value(h, t0, n_knots, (double*)Vx_device, (double*)Vxx_device, "ilqr_copy_value_to_device");
+}
+
+int ilqr_get_value(ilqr_batch* h, int t0, int n_knots, double* Vx, double* Vxx) {
+  if (int rc = prepare_value(h, t0, n_knots, Vx, Vxx, "ilqr_get_value")) return rc;
+  // a window-sized device buffer (the staging buffer: Vx, then Vxx), copied out and waited for
+  const size_t n_vx = Vx ? (size_t)h->B * n_knots * h->nx : 0, n_vxx = Vxx ? (size_t)h->B * n_knots * h->nx * h->nx : 0;
+  if (int rc = ensure_staging(h, n_vx + n_vxx)) return rc;
+  double* const d_vx = Vx ? h->staging : nullptr;
+  double* const d_vxx = Vxx ? h->staging + n_vx : nullptr;
+  if (int rc = run_value(h, t0, n_knots, d_vx, d_vxx, "ilqr_get_value")) return rc;
+  if (Vx) HIPCHK(hipMemcpyAsync(Vx, d_vx, n_vx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (Vxx) HIPCHK(hipMemcpyAsync(Vxx, d_vxx, n_vxx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
 }
 
 // ---- per-trajectory model parameters (additive under ABI 6) ------------------------------------

@@ -386,6 +386,42 @@ static int launch_solve_tiles(ilqr_batch* h, int n_iters) {
   return timer_end(h, ILQR_STAGE_SOLVE, ev);
 }
 
+// The value model of the stored policy (ilqr_get_value / ilqr_copy_value_to_device; value_wave.hpp, value_thread.hpp): picked by the
+// handle's layout and sizes alone -- no route bit, no stage timer.  The caller has materialised the records.  Vx [B][nk][nx], Vxx
+// [B][nk][nx * nx]: canonical double in device memory, either may be null.
+static const char* value_kernel_name(const ilqr_batch* h) {
+  if (!h->aos) return "k_value_t";
+  return h->nu > WM ? (h->nx > 16 ? "k_value_w<2, 2>" : "k_value_w<1, 2>") : (h->nx > 16 ? "k_value_w<2, 1>" : "k_value_w<1, 1>");
+}
+static int launch_value(ilqr_batch* h, int t0, int nk, double* Vx, double* Vxx, const char** name) {
+  *name = value_kernel_name(h);
+  if (!h->aos) {
+    const dim3 grid(h->Bp / 64), block(64);
+    if (int rc = with_model(h, [&](auto& v, auto& m, auto&) {
+          hipLaunchKernelGGL((k_value_t<std::decay_t<decltype(m)>>), grid, block, 0, h->stream, v, t0, nk, Vx, Vxx);
+          return 0;
+        }))
+      return rc;
+  } else {
+    const dim3 grid(h->B), block(64);
+    const bool f32 = h->dtype == ILQR_DTYPE_F32;  // float storage (never with two control tiles: ilqr_create)
+#define ILQR_VALUE_W(NT_, MT_)                                                                                                          \
+    do {                                                                                                                                \
+      if (f32 && MT_ == 1)                                                                                                              \
+        hipLaunchKernelGGL((k_value_w<NT_, 1, float>), grid, block, 0, h->stream, h->vf, h->nx, h->nu, t0, nk, Vx, Vxx);                  \
+      else if (f32)                                                                                                                     \
+        return fail(ILQR_ERR_UNSUPPORTED, "%s: no fp32 handle has more than %d controls", *name, WM);                                   \
+      else                                                                                                                              \
+        hipLaunchKernelGGL((k_value_w<NT_, MT_, double>), grid, block, 0, h->stream, h->v, h->nx, h->nu, t0, nk, Vx, Vxx);               \
+    } while (0)
+    if (h->nu > WM) { if (h->nx > 16) ILQR_VALUE_W(2, 2); else ILQR_VALUE_W(1, 2); }
+    else { if (h->nx > 16) ILQR_VALUE_W(2, 1); else ILQR_VALUE_W(1, 1); }
+#undef ILQR_VALUE_W
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 static AlphaSet line_search_alphas() {
   AlphaSet a;
   for (int i = 0; i < NALPHA; i++) a.a[i] = kAlphaHost[i];

@@ -276,6 +276,31 @@ int ilqr_mpc_step(ilqr_batch* h, const double* x0, const void* x0_device, int sh
  * apply: t0 = 0, n_knots = the shift of the next step).  The window lies inside [0, T) and holds at least one knot. */
 int ilqr_copy_controls_to_device(ilqr_batch* h, int t0, int n_knots, void* u_device);
 
+/* ---- the value model of the stored policy (additive under ABI 6) -------------------------------------------------------------------
+ * The reference's backward pass leaves a quadratic cost-to-go model Vx[t], Vxx[t] at every knot beside the gains (members Vx, Vxx;
+ * src/ilqr_core.cpp:353-354, 391-393).  The kernels here carry it in registers and drop it; these calls recompute it on the device for a
+ * window of knots.  DEFINITION -- from the derivative records ilqr_get_derivatives would return at this moment (see there for which
+ * trajectory they describe) and the stored gains k, K:
+ *     Vx[T] = cx[T],  Vxx[T] = cxx[T]                                       (as stored: knot T is not symmetrised)
+ *     t = T-1 .. 0:   Qx = cx + fx'Vx[t+1],  Qu = cu + fu'Vx[t+1],  Qxx = cxx + fx'Vxx[t+1] fx,  Qux = cxu' + fu'Vxx[t+1] fx,
+ *                     Quu = cuu + fu'Vxx[t+1] fu                            (src/ilqr_core.cpp:359-363; Quu without lambda)
+ *                     Vx[t]  = Qx  + K'Quu k + K'Qu  + Qux'k
+ *                     Vxx[t] = Qxx + K'Quu K + K'Qux + Qux'K,  then (Vxx[t] + Vxx[t]')/2
+ * No lambda, no box-QP, no divergence test: a pure function of (records, k, K) -- the value model of the policy the handle STORES, whoever
+ * stored it (a backward pass, ilqr_set_gains, a receding-horizon shift).  After ilqr_compute_derivatives + ilqr_backward_pass with
+ * diverge == 0 it equals the reference's members to rounding.  The recursion runs in double on every handle (an fp32 handle's stored float
+ * records and gains are widened), and the output is canonical double on every handle:
+ *     Vx  [B][n_knots][nx]        Vxx [B][n_knots][nx*nx], column-major per knot
+ * Only the window [t0, t0 + n_knots) is stored: it lies inside [0, T] and holds at least one knot (V is carried from knot T down to t0;
+ * Vx[0] is the gradient of the cost-to-go model in the measured state, Vxx[t] at a late knot a terminal cost for a shorter horizon).
+ * Either output may be NULL, not both.  Every model, ILQR_MODEL_HOST included (its records are what the caller set).  The call leaves the
+ * handle as ilqr_get_derivatives at the same point does: later iterations are bit for bit those of a handle that called neither.
+ * ILQR_ERR_INVALID: a bad window, two NULL outputs; ILQR_ERR_STATE: before ilqr_init_traj / ilqr_set_trajectory. */
+/* into host arrays: a window-sized device buffer, copied out; synchronises */
+int ilqr_get_value(ilqr_batch* h, int t0, int n_knots, double* Vx, double* Vxx);
+/* into caller-owned device memory of this handle's device: enqueued on the handle's stream, not waited for (as ilqr_copy_gains_to_device) */
+int ilqr_copy_value_to_device(ilqr_batch* h, int t0, int n_knots, void* Vx_device, void* Vxx_device);
+
 /* ---- per-trajectory model parameters (additive under ABI 6) ----------------------------------------------------------------------
  * A user device twin may declare NTP parameters that differ from trajectory to trajectory (csrc/models.hpp: NTP, set_trajectory_params) --
  * a target that moves between receding-horizon steps, a perturbed model per trajectory.  Once set, every later rollout, derivative sweep

@@ -366,6 +366,19 @@ class BatchILQR {
     check(ilqr_get_cost(h_, c.data()), "ilqr_get_cost");
     return c;
   }
+  // The value model of the stored policy (the reference's members Vx, Vxx; ilqr_get_value) over the knots [t0, t0 + n_knots), n_knots < 0:
+  // up to knot T.  Vx [B][n_knots][nx], Vxx [B][n_knots][nx*nx] (column-major per knot); either pointer may be null, not both.
+  void value(std::vector<double>* Vx, std::vector<double>* Vxx, int t0 = 0, int n_knots = -1) {
+    if (n_knots < 0) n_knots = T_ + 1 - t0;
+    const size_t knots = (size_t)B_ * (n_knots > 0 ? n_knots : 0);
+    if (Vx) Vx->assign(knots * n_, 0.0);
+    if (Vxx) Vxx->assign(knots * n_ * n_, 0.0);
+    check(ilqr_get_value(h_, t0, n_knots, Vx ? Vx->data() : nullptr, Vxx ? Vxx->data() : nullptr), "ilqr_get_value");
+  }
+  // ... or into caller-owned device memory, on the handle's stream, nothing waited for
+  void copy_value_to_device(int t0, int n_knots, void* Vx_device, void* Vxx_device) {
+    check(ilqr_copy_value_to_device(h_, t0, n_knots, Vx_device, Vxx_device), "ilqr_copy_value_to_device");
+  }
   // Every result in one call (ABI 5): the device-to-host copies are enqueued back to back, nothing is waited for until synchronize().
   // The buffers belong to the caller (sizes as the getters above; nullptr = skip); page-lock buffers that are reused across solves once
   // with ilqr_host_register so that the copies are DMA transfers.
@@ -859,6 +872,21 @@ class iLQR {
         for (int a = 0; a < m; a++) out[t](a, j) = K[(size_t)t * m * n + a + (size_t)m * j];
     }
     return out;
+  }
+  // the reference's members Vx, Vxx (ilqr.h:79-80) over the knots [t0, t0 + n_knots), n_knots < 0: up to knot T -- the value model of the
+  // stored policy, recomputed on the device (ilqr_get_value)
+  void value(VecOfVecXd& Vx, VecOfMatXd& Vxx, int t0 = 0, int n_knots = -1) const {
+    const int n = model->x_dims;
+    if (n_knots < 0) n_knots = T + 1 - t0;
+    std::vector<double> vx, vxx;
+    engine_->value(&vx, &vxx, t0, n_knots);
+    Vx = unpack(vx, n_knots, n);
+    Vxx = VecOfMatXd(n_knots);
+    for (int t = 0; t < n_knots; t++) {
+      Vxx[t] = MatrixXd(n, n);
+      for (int j = 0; j < n; j++)
+        for (int a = 0; a < n; a++) Vxx[t](a, j) = vxx[(size_t)t * n * n + a + (size_t)n * j];
+    }
   }
   double cost() const { return engine_->cost()[0]; }
   int iterations() const { return engine_->iterations()[0]; }
