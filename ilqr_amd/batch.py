@@ -35,6 +35,10 @@ def _p(a):
     return a.ctypes.data_as(_dp) if a is not None else None
 
 
+def _pi(a):
+    return a.ctypes.data_as(_ip) if a is not None else None
+
+
 class BatchILQR:
     def __init__(self, model, B, T, dt, u_min=None, u_max=None, goal=None, device=0, flags=0,
                  stream=None, params=None, nx=None, nu=None, lq=None, dtype="f64", lib=None, user_params=None, route=0, assume_cus=0):
@@ -138,15 +142,64 @@ class BatchILQR:
         zeros them; k's tail is zero and xs's is xs[T] under either (include/ilqr_amd.h, enum ilqr_tail)."""
         self._check(self.lib.ilqr_shift_horizon(self.h, int(shift), self._TAILS[tail]))
 
-    def mpc_step(self, x0=None, x0_ptr=None, shift=1, iters=1, tail="hold"):
+    def mpc_step(self, x0=None, x0_ptr=None, shift=1, iters=1, tail="hold", reset_mask=None, reset_mask_ptr=None, reset_nonfinite=False,
+                 reset_lambda_max=False):
         """One receding-horizon step: shift_horizon(shift, tail), warm start from the new state, `iters` iterations.  x0: numpy [B][nx];
-        x0_ptr: a raw device pointer to [B][nx] float64 on the handle's device (torch.Tensor.data_ptr()).  Exactly one of them."""
+        x0_ptr: a raw device pointer to [B][nx] float64 on the handle's device (torch.Tensor.data_ptr()).  Exactly one of them.
+        With one of the reset arguments (ilqr_mpc_step_reset): the trajectories the mask selects (reset_mask: [B], non-zero = reset;
+        reset_mask_ptr: int32 [B] in device memory) start over from the reset controls after the shift; reset_lambda_max: also those the
+        previous step left at status lambda_max; reset_nonfinite: also those whose warm rollout is not finite, which are rolled out again.
+        reset_flags() says who and why.  Without them the call is ilqr_mpc_step."""
         if (x0 is None) == (x0_ptr is None):
             raise ValueError("mpc_step: exactly one of x0 and x0_ptr")
         if x0 is not None:
             x0 = _c(x0)
             assert x0.shape == (self.B, self.nx)
-        self._check(self.lib.ilqr_mpc_step(self.h, _p(x0), x0_ptr, int(shift), self._TAILS[tail], int(iters)))
+        if reset_mask is None and reset_mask_ptr is None and not reset_nonfinite and not reset_lambda_max:
+            self._check(self.lib.ilqr_mpc_step(self.h, _p(x0), x0_ptr, int(shift), self._TAILS[tail], int(iters)))
+            return
+        mask = self._mask(reset_mask)
+        self._check(self.lib.ilqr_mpc_step_reset(self.h, _p(x0), x0_ptr, int(shift), self._TAILS[tail], int(iters), _pi(mask), reset_mask_ptr,
+                                                 self._rules(reset_nonfinite, reset_lambda_max)))
+
+    # ---- single trajectories start over (ilqr_set_reset_controls, ilqr_reset_trajectories, ilqr_get_reset_flags) ----
+    def _mask(self, mask):
+        if mask is None:
+            return None
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.int32)
+        if mask.shape != (self.B,):
+            raise ValueError("reset mask must be [B], got %s" % (mask.shape,))
+        return mask
+
+    @staticmethod
+    def _rules(nonfinite, lambda_max):
+        return (capi.RESET_NONFINITE if nonfinite else 0) | (capi.RESET_LAMBDA_MAX if lambda_max else 0)
+
+    def set_reset_controls(self, u0=None, ptr=None):
+        """The controls a reset trajectory starts from: u0 numpy [B][T][nu], or ptr, a raw device pointer to float64 [B][T][nu]; neither =
+        back to zeros (the default).  Enqueued on the handle's stream."""
+        if u0 is not None:
+            u0 = _c(u0)
+            if u0.shape != (self.B, self.T, self.nu):
+                raise ValueError("set_reset_controls: u0 must be [B][T][nu], got %s" % (u0.shape,))
+        self._check(self.lib.ilqr_set_reset_controls(self.h, _p(u0), ptr))
+
+    def reset_trajectories(self, mask=None, mask_ptr=None, nonfinite=False, lambda_max=False):
+        """Reset now, outside a step: the trajectories the mask selects ([B] numpy, or int32 [B] in device memory), with nonfinite those
+        whose cost is NaN or inf, with lambda_max those at status lambda_max (include/ilqr_amd.h: what a reset is).  Enqueued."""
+        mask = self._mask(mask)
+        self._check(self.lib.ilqr_reset_trajectories(self.h, _pi(mask), mask_ptr, self._rules(nonfinite, lambda_max)))
+
+    def reset_flags(self):
+        """Why the last mpc_step with resets / reset_trajectories reset each trajectory: int32 [B], bits capi.WAS_MASKED, WAS_NONFINITE,
+        WAS_LAMBDA_MAX, 0 = it was not (synchronises)."""
+        flags = np.zeros(self.B, dtype=np.int32)
+        self._check(self.lib.ilqr_get_reset_flags(self.h, flags.ctypes.data_as(_ip)))
+        return flags
+
+    def copy_reset_flags_to_device(self, ptr):
+        """The same flags as int32 [B] into caller-owned device memory `ptr` (raw pointer); enqueued on the handle's stream."""
+        self._check(self.lib.ilqr_copy_reset_flags_to_device(self.h, ptr))
 
     def copy_controls_to_device(self, t0, n, ptr):
         """us[:, t0 : t0 + n, :] as float64 [B][n][nu] into caller-owned device memory `ptr` (raw pointer); enqueued on the handle's stream."""

@@ -748,6 +748,173 @@ int ilqr_copy_controls_to_device(ilqr_batch* h, int t0, int n_knots, void* u_dev
   return to_canonical(h, {h->v.us, h->T, h->nu, t0, n_knots}, (double*)u_device);
 }
 
+// ---- single trajectories start over (additive under ABI 6; reset.hpp) ---------------
+static int* reset_mask_stage(ilqr_batch* h) { return h->reset_ints; }
+static int* reset_sel(ilqr_batch* h) { return h->reset_ints + h->Bp; }
+static int* reset_flags(ilqr_batch* h) { return h->reset_ints + 2 * (size_t)h->Bp; }
+static int ensure_reset_ints(ilqr_batch* h) {
+  if (h->reset_ints) return 0;
+  return dev_alloc(h, &h->reset_ints, 3 * (size_t)h->Bp);
+}
+static int check_reset_args(const int* mask, const void* mask_device, int rules, const char* who) {
+  REQUIRE(!(mask && mask_device), "%s: at most one of mask (host) and mask_device", who);
+  REQUIRE((rules & ~(ILQR_RESET_NONFINITE | ILQR_RESET_LAMBDA_MAX)) == 0, "%s: rules %d: bits of ILQR_RESET_NONFINITE | ILQR_RESET_LAMBDA_MAX", who, rules);
+  return 0;
+}
+// the mask where the kernels read it: a host mask goes to the handle's own buffer on the stream, a device mask is read where it lies
+static int stage_reset_mask(ilqr_batch* h, const int* mask, const void* mask_device, const int** out) {
+  if (int rc = ensure_reset_ints(h)) return rc;
+  *out = (const int*)mask_device;
+  if (mask) {
+    HIPCHK(hipMemcpyAsync(reset_mask_stage(h), mask, (size_t)h->B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    *out = reset_mask_stage(h);
+  }
+  return 0;
+}
+// k_select_reset, then k_reset_nominal for whom it selected.  repeat: the pass after a warm rollout (non-finite costs only; commit_idx says
+// whom the repeated rollout takes).
+static int select_and_reset(ilqr_batch* h, const int* d_mask, int rules, int repeat) {
+  hipLaunchKernelGGL(k_select_reset<double>, dim3((h->Bp + 255) / 256), dim3(256), 0, h->stream, h->v, d_mask, rules, repeat, h->params.lambda_init,
+                     h->params.dlambda_init, reset_sel(h), reset_flags(h), h->commit_idx);
+  HIPCHK(hipGetLastError());
+  const int nx = h->nx, nu = h->nu, T = h->T;
+  const int lanes = h->aos ? 1 : TW;
+  ResetSet set;
+  set.arr[0] = {h->v.xs, nullptr, T + 1, nx * lanes};
+  set.arr[1] = {h->v.us, h->reset_us_set ? h->reset_us : nullptr, T, nu * lanes};
+  set.arr[2] = {h->v.kff, nullptr, T, nu * lanes};
+  set.arr[3] = {h->v.Kfb, nullptr, T, nu * nx * lanes};
+  set.sel = reset_sel(h);
+  set.nseg = h->aos ? h->B : h->ntiles;  // (sel holds Bp = 16 ntiles >= B slots)
+  set.lanes = lanes;
+  const dim3 grid((unsigned)std::min(set.nseg, 65535), 4), block(256);
+  with_real(h, [&](auto r) {
+    hipLaunchKernelGGL(k_reset_nominal<decltype(r)>, grid, block, 0, h->stream, set);
+    return 0;
+  });
+  HIPCHK(hipGetLastError());
+  h->reset_flags_valid = true;
+  return 0;
+}
+
+int ilqr_set_reset_controls(ilqr_batch* h, const double* u0, const void* u0_device) {
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  REQUIRE(!(u0 && u0_device), "ilqr_set_reset_controls: at most one of u0 (host) and u0_device");
+  if (!u0 && !u0_device) {  // back to zeros (the buffer stays for the next set)
+    h->reset_us_set = false;
+    return 0;
+  }
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->reset_us)
+    if (int rc = dev_alloc_real(h, &h->reset_us, dev_elems(h, h->T, h->nu))) return rc;
+  const DevArray dst{h->reset_us, h->T, h->nu};
+  const double* src = (const double*)u0_device;
+  if (u0) {  // the host array's one transfer: straight into place where the handle stores the canonical array, else through a buffer of its own
+    double* stage = h->reset_us;
+    if (!stored_canonical(h, dst)) {
+      if (!h->reset_us_stage)
+        if (int rc = dev_alloc(h, &h->reset_us_stage, (size_t)h->B * h->T * h->nu)) return rc;
+      stage = h->reset_us_stage;
+    }
+    HIPCHK(hipMemcpyAsync(stage, u0, (size_t)h->B * h->T * h->nu * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    src = stage;
+  }
+  if (int rc = from_canonical(h, src, dst)) return rc;
+  h->reset_us_set = true;
+  return 0;
+}
+
+int ilqr_reset_trajectories(ilqr_batch* h, const int* mask, const void* mask_device, int rules) {
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  if (int rc = check_reset_args(mask, mask_device, rules, "ilqr_reset_trajectories")) return rc;
+  if (!h->initialised) return fail(ILQR_ERR_STATE, "reset_trajectories before ilqr_init_traj/ilqr_set_trajectory: there is no trajectory to reset");
+  HIPCHK(hipSetDevice(h->device));
+  if (int rc = flush_commit(h)) return rc;  // an accepted candidate not yet copied belongs to the trajectory as it was (as shift_nominal)
+  h->cands = Cands::none;
+  h->lq_cands_kept = false;
+  if (!h->aos && h->recs == ilqr_batch::REC_VALID) h->recs = ilqr_batch::REC_STALE;
+  const int* d_mask = nullptr;
+  if (int rc = stage_reset_mask(h, mask, mask_device, &d_mask)) return rc;
+  return select_and_reset(h, d_mask, rules, 0);
+}
+
+// ilqr_mpc_step's warm rollout and commit, kernel for kernel.  repeat: commit_idx already says who is rolled out again (k_select_reset);
+// a tiled rollout scores whole tiles, so its costs go through a scratch row (cost_c's first plane: the candidates are nobody's during a step)
+static int warm_rollout_commit(ilqr_batch* h, bool repeat) {
+  AlphaSet al;
+  for (int i = 0; i < NALPHA; i++) al.a[i] = 0.0;
+  if (h->plan.commit != Commit::tiled) {
+    if (!repeat) HIPCHK(hipMemsetAsync(h->commit_idx, 0, (size_t)h->Bp * sizeof(int), h->stream));
+    if (int rc = launch_rollout(h, true, true, al, 1, h->v.cost, 0)) return rc;
+  } else {
+    if (int rc = launch_rollout(h, true, true, al, 1, repeat ? h->v.cost_c : h->v.cost, 0)) return rc;
+    if (!repeat) HIPCHK(hipMemsetAsync(h->commit_idx, 0, (size_t)h->Bp * sizeof(int), h->stream));
+    if (int rc = launch_commit(h)) return rc;
+    if (repeat) {
+      hipLaunchKernelGGL(k_take_reset_cost, dim3((h->B + 255) / 256), dim3(256), 0, h->stream, h->v.cost_c, reset_sel(h), h->v.cost, h->B);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  HIPCHK(hipMemsetAsync(h->commit_idx, 0xFF, (size_t)h->Bp * sizeof(int), h->stream));
+  return 0;
+}
+
+// ilqr_mpc_step with a reset of the selected trajectories between the shift and the warm rollout, and under ILQR_RESET_NONFINITE one more
+// after it for those whose warm rollout did not stay finite
+int ilqr_mpc_step_reset(ilqr_batch* h, const double* x0, const void* x0_device, int shift, int tail, int n_iters, const int* mask,
+                        const void* mask_device, int rules) {
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  if (host_model(h)) return fail(ILQR_ERR_UNSUPPORTED, "ilqr_mpc_step_reset: a host-evaluated model's rollouts run on the host (as for ilqr_warm_start)");
+  REQUIRE((x0 != nullptr) != (x0_device != nullptr), "ilqr_mpc_step_reset: exactly one of x0 (host) and x0_device");
+  if (int rc = check_shift(h, shift, tail)) return rc;
+  REQUIRE(n_iters >= 0, "n_iters %d must be >= 0", n_iters);
+  if (int rc = check_reset_args(mask, mask_device, rules, "ilqr_mpc_step_reset")) return rc;
+  if (!h->initialised) return fail(ILQR_ERR_STATE, "mpc_step_reset needs a previous solve (assert us.size()>0, ilqr_core.cpp:66)");
+  HIPCHK(hipSetDevice(h->device));
+  if (int rc = shift_nominal(h, shift, tail == ILQR_TAIL_HOLD ? SHIFT_TAIL_HOLD : SHIFT_TAIL_ZERO)) return rc;
+  // after the shift: the reset controls are a fresh horizon's, not shifted.  The cost rule waits for the new cost.
+  const int* d_mask = nullptr;
+  if (int rc = stage_reset_mask(h, mask, mask_device, &d_mask)) return rc;
+  if (int rc = select_and_reset(h, d_mask, rules & ILQR_RESET_LAMBDA_MAX, 0)) return rc;
+  const DevArray X0{h->v.x0, 1, h->nx};  // x0 as in ilqr_mpc_step
+  const double* src = (const double*)x0_device;
+  if (x0) {
+    double* dst = stored_canonical(h, X0) ? h->v.x0 : h->x0_stage;
+    HIPCHK(hipMemcpyAsync(dst, x0, (size_t)h->B * h->nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    src = dst;
+  }
+  if (int rc = from_canonical(h, src, X0)) return rc;
+  if (int rc = warm_rollout_commit(h, false)) return rc;
+  if (rules & ILQR_RESET_NONFINITE) {
+    if (int rc = select_and_reset(h, nullptr, ILQR_RESET_NONFINITE, 1)) return rc;
+    if (int rc = warm_rollout_commit(h, true)) return rc;
+  }
+  hipLaunchKernelGGL(k_warm_reset<double>, dim3((h->Bp + 255) / 256), dim3(256), 0, h->stream, h->v);
+  HIPCHK(hipGetLastError());
+  if (n_iters == 0) return 0;
+  return ilqr_iterate(h, n_iters);
+}
+
+int ilqr_copy_reset_flags_to_device(ilqr_batch* h, void* flags_device) {
+  if (!h || !flags_device) return fail(ILQR_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->reset_flags_valid) {  // no reset call yet: nobody was reset
+    HIPCHK(hipMemsetAsync(flags_device, 0, (size_t)h->B * sizeof(int), h->stream));
+    return 0;
+  }
+  HIPCHK(hipMemcpyAsync(flags_device, reset_flags(h), (size_t)h->B * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+  return 0;
+}
+int ilqr_get_reset_flags(ilqr_batch* h, int* flags) {
+  if (!h || !flags) return fail(ILQR_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->reset_flags_valid) {
+    for (int b = 0; b < h->B; b++) flags[b] = 0;
+    return 0;
+  }
+  return scalars_to_host(h, (const int*)reset_flags(h), flags);
+}
+
 // ---- the value model of the stored policy (additive under ABI 6) ---------------------------------
 // every refusal the two calls share, then the records as ilqr_get_derivatives would return them now
 static int prepare_value(ilqr_batch* h, int t0, int n_knots, const void* Vx, const void* Vxx, const char* who) {

@@ -60,6 +60,13 @@ struct ilqr_batch {
   // whether the kernels read them.  Row b is the trajectory in slot b: the generic path never re-packs trajectories (ilqr_generate_trajectory
   // compacts on the persistent routes only) -- whoever brings compaction to this path must move these rows with the trajectories.
   double* traj_params = nullptr;
+  // single trajectories starting over on the device (reset.hpp; ilqr_reset_trajectories, ilqr_mpc_step_reset): allocated by the first call
+  // that needs them (dev_alloc: freed with the handle), nothing per call afterwards
+  int* reset_ints = nullptr;         // [3][Bp]: a host mask's copy, the selection of the pass under way, the flags of the last call
+  double* reset_us = nullptr;        // the reset controls, in the layout and storage type of us; read while reset_us_set (else: zeros)
+  double* reset_us_stage = nullptr;  // canonical [B][T][nu]: a host u0 on its way into that layout (handles that convert)
+  bool reset_us_set = false;
+  bool reset_flags_valid = false;    // one of the two calls has run: the flags describe it
   // v is the view every entry point addresses arrays through; for an fp32 handle its trajectory pointers hold
   // the addresses of FLOAT arrays (never dereferenced as double: kernels get vf, the same addresses typed float*)
   BatchView v;

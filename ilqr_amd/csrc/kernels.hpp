@@ -1,6 +1,7 @@
 // kernels.hpp -- the HIP kernels of the nx = 4 tiled path (gfx950 / MI355X), one header per stage:
 //
 //   layout.hpp           index maps, k_to_canonical / k_from_canonical, k_permute_*, k_reset_state, k_shift_horizon
+//   reset.hpp            k_select_reset, k_reset_nominal: single trajectories start over on the device
 //   rollout.hpp          rollout_tile, k_rollout, accept_one, k_accept, candidate checkpoints
 //   derivatives.hpp      derivatives_of_knot, k_derivatives
 //   backward_thread.hpp  k_backward_t (one thread per trajectory; cross-check)
@@ -13,6 +14,7 @@
 #include "backward_thread.hpp"
 #include "derivatives.hpp"
 #include "layout.hpp"
+#include "reset.hpp"
 #include "rollout.hpp"
 #include "solve_tile.hpp"
 #include "backward_hex.hpp"

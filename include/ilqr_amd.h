@@ -270,11 +270,51 @@ int ilqr_shift_horizon(ilqr_batch* h, int shift, int tail);
  * compaction of finished trajectories.  Exactly one of x0 (host, [B][nx] double) and x0_device (device memory of this handle's device,
  * [B][nx] double) is non-NULL.  A host x0 is the call's one host-to-device transfer: from page-locked memory (ilqr_host_register) it is
  * asynchronous -- the array must then stay unchanged until the stream has passed the step -- from pageable memory the runtime may wait
- * to stage it.  ILQR_ERR_UNSUPPORTED for ILQR_MODEL_HOST (its rollouts are the caller's, as for ilqr_warm_start). */
+ * to stage it.  ILQR_ERR_UNSUPPORTED for ILQR_MODEL_HOST (its rollouts are the caller's, as for ilqr_warm_start).
+ * The warm rollout is committed unconditionally, also when it is not finite: a trajectory whose rollout overflowed (a new x0 far from the
+ * nominal under explicit Euler) holds NaN or inf in xs, us and cost from then on, and no later step of this call repairs it --
+ * ilqr_mpc_step_reset below does, on the device. */
 int ilqr_mpc_step(ilqr_batch* h, const double* x0, const void* x0_device, int shift, int tail, int n_iters);
 /* us[:, t0 : t0 + n_knots, :] as canonical double [B][n_knots][nu] into caller-owned device memory, on the handle's stream (the controls to
  * apply: t0 = 0, n_knots = the shift of the next step).  The window lies inside [0, T) and holds at least one knot. */
 int ilqr_copy_controls_to_device(ilqr_batch* h, int t0, int n_knots, void* u_device);
+
+/* ---- single trajectories start over inside the loop (additive under ABI 6) ---------------------------------------------------------
+ * In a batch of simulated environments episodes end one by one, and a warm rollout that overflows once poisons its trajectory for good.
+ * These calls reset SELECTED trajectories on the device, enqueued on the handle's stream like the step itself; a trajectory that is not
+ * selected keeps its bits.  Resetting trajectory b means:
+ *     us[b]  = the reset controls of b (ilqr_set_reset_controls; zeros by default), rounded to the handle's storage type
+ *     k[b] = 0, K[b] = 0
+ *     xs[b]  = 0      (a finite placeholder: with K = 0 the next rollout computes u = us[t] exactly and overwrites xs)
+ *     lambda[b] = params.lambda_init, dlambda[b] = params.dlambda_init
+ *     status running, iterations 0, flgChange 1, alpha index -1, dV = gnorm = 0
+ *     cost[b] and the derivative records stay: the next rollout / sweep writes them (ilqr_get_derivatives keeps its meaning)
+ * Old values are overwritten, never read.  Masks and flags are int32 [B] in the caller's trajectory order. */
+enum ilqr_reset_rule { ILQR_RESET_NONFINITE = 1, ILQR_RESET_LAMBDA_MAX = 2 };                    /* bits of `rules` */
+enum ilqr_reset_why { ILQR_WAS_MASKED = 1, ILQR_WAS_NONFINITE = 2, ILQR_WAS_LAMBDA_MAX = 4 };   /* bits of a reset flag */
+/* The controls a reset trajectory starts from: canonical double [B][T][nu], host or device (at most one non-NULL; both NULL = back to
+ * zeros, the default).  Kept in the handle in the layout and storage type of us (allocated by the first non-NULL call); enqueued, no
+ * synchronisation (a host array from page-locked memory stays unchanged until the stream has passed the call). */
+int ilqr_set_reset_controls(ilqr_batch* h, const double* u0, const void* u0_device);
+/* Reset now, outside a step.  Trajectory b is selected when mask[b] != 0 (mask: int32 [B], host or device, at most one non-NULL, both NULL =
+ * rules only), or rules & ILQR_RESET_NONFINITE and cost[b] is NaN or inf, or rules & ILQR_RESET_LAMBDA_MAX and status[b] == ILQR_LAMBDA_MAX.
+ * An accepted candidate still waiting to be copied is copied first and the candidate buffers belong to nobody afterwards (as for
+ * ilqr_shift_horizon).  Any handle that stores a trajectory, ILQR_MODEL_HOST included.  ILQR_ERR_INVALID: two masks, unknown rule bits;
+ * ILQR_ERR_STATE before ilqr_init_traj / ilqr_set_trajectory. */
+int ilqr_reset_trajectories(ilqr_batch* h, const int* mask, const void* mask_device, int rules);
+/* ilqr_mpc_step with resets, in this order: shift; reset whom the mask or (under ILQR_RESET_LAMBDA_MAX) a lambda_max exit of the previous
+ * step selects -- after the shift, so reset controls are not shifted --; x0; the warm rollout, committed; only under ILQR_RESET_NONFINITE:
+ * reset every trajectory whose NEW cost is not finite and roll those out again; the new outer loop; n_iters iterations.  It leaves bit
+ * for bit what ilqr_shift_horizon, overwriting the selected rows on the host (ilqr_set_trajectory + ilqr_set_gains + ilqr_set_lambda) and
+ * ilqr_mpc_step(shift = 0) leave; with no mask and rules = 0, what ilqr_mpc_step leaves.  Same handles and refusals as ilqr_mpc_step, and
+ * ILQR_ERR_INVALID for two masks or unknown rule bits.  Which rule when: ILQR_RESET_NONFINITE costs one more selection and rollout per
+ * step and is what keeps a loop alive unattended; ILQR_RESET_LAMBDA_MAX suits callers who would rather restart a trajectory from the reset
+ * controls than keep its last accepted solution when the regularisation ran out. */
+int ilqr_mpc_step_reset(ilqr_batch* h, const double* x0, const void* x0_device, int shift, int tail, int n_iters, const int* mask,
+                        const void* mask_device, int rules);
+/* Why each trajectory was reset by the LAST of the two calls above (0 = it was not; before any such call: all 0): int32 [B] */
+int ilqr_get_reset_flags(ilqr_batch* h, int* flags);                    /* synchronises */
+int ilqr_copy_reset_flags_to_device(ilqr_batch* h, void* flags_device); /* enqueued on the handle's stream */
 
 /* ---- the value model of the stored policy (additive under ABI 6) -------------------------------------------------------------------
  * The reference's backward pass leaves a quadratic cost-to-go model Vx[t], Vxx[t] at every knot beside the gains (members Vx, Vxx;

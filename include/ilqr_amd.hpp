@@ -407,6 +407,41 @@ class BatchILQR {
     if (host_) throw std::logic_error("mpc_step(): a host-evaluated model rolls out on the host; receding-horizon steps need a device twin");
     check(ilqr_mpc_step(h_, nullptr, x0_device, shift, tail, iters), "ilqr_mpc_step");
   }
+  // ---- single trajectories start over inside the loop (include/ilqr_amd.h: what a reset is) ----
+  // The step with resets: mask (int32 [B], non-zero = reset; host vector, or device memory, or neither) and rules (bits of ilqr_reset_rule).
+  void mpc_step_reset(const std::vector<double>& x0, const std::vector<int>& mask, int rules = 0, int shift = 1, int iters = 1, int tail = ILQR_TAIL_HOLD) {
+    require(x0.size() == (size_t)B_ * n_, "mpc_step_reset: x0 [B][nx]");
+    require(mask.empty() || mask.size() == (size_t)B_, "mpc_step_reset: mask [B] (or empty)");
+    if (host_) throw std::logic_error("mpc_step_reset(): a host-evaluated model rolls out on the host; receding-horizon steps need a device twin");
+    check(ilqr_mpc_step_reset(h_, x0.data(), nullptr, shift, tail, iters, mask.empty() ? nullptr : mask.data(), nullptr, rules), "ilqr_mpc_step_reset");
+  }
+  void mpc_step_reset(const void* x0_device, const void* mask_device, int rules = 0, int shift = 1, int iters = 1, int tail = ILQR_TAIL_HOLD) {
+    if (host_) throw std::logic_error("mpc_step_reset(): a host-evaluated model rolls out on the host; receding-horizon steps need a device twin");
+    check(ilqr_mpc_step_reset(h_, nullptr, x0_device, shift, tail, iters, nullptr, mask_device, rules), "ilqr_mpc_step_reset");
+  }
+  // the controls a reset trajectory starts from, [B][T][nu] (an empty vector / a null pointer: back to zeros)
+  void set_reset_controls(const std::vector<double>& u0) {
+    require(u0.empty() || u0.size() == (size_t)B_ * T_ * m_, "set_reset_controls: u0 [B][T][nu] (or empty)");
+    check(ilqr_set_reset_controls(h_, u0.empty() ? nullptr : u0.data(), nullptr), "ilqr_set_reset_controls");
+  }
+  void set_reset_controls(const void* u0_device) { check(ilqr_set_reset_controls(h_, nullptr, u0_device), "ilqr_set_reset_controls"); }
+  // reset now, outside a step (a host-evaluated model keeps host mirrors of its nominal that this would leave behind: refused, as the shift)
+  void reset_trajectories(const std::vector<int>& mask, int rules = 0) {
+    require(mask.empty() || mask.size() == (size_t)B_, "reset_trajectories: mask [B] (or empty)");
+    if (host_) throw std::logic_error("reset_trajectories(): a host-evaluated model's nominal lives on the host as well");
+    check(ilqr_reset_trajectories(h_, mask.empty() ? nullptr : mask.data(), nullptr, rules), "ilqr_reset_trajectories");
+  }
+  void reset_trajectories(const void* mask_device, int rules = 0) {
+    if (host_) throw std::logic_error("reset_trajectories(): a host-evaluated model's nominal lives on the host as well");
+    check(ilqr_reset_trajectories(h_, nullptr, mask_device, rules), "ilqr_reset_trajectories");
+  }
+  // why the last of those calls reset each trajectory (bits of ilqr_reset_why, 0 = it was not)
+  std::vector<int> reset_flags() {
+    std::vector<int> f((size_t)B_);
+    check(ilqr_get_reset_flags(h_, f.data()), "ilqr_get_reset_flags");
+    return f;
+  }
+  void copy_reset_flags_to_device(void* flags_device) { check(ilqr_copy_reset_flags_to_device(h_, flags_device), "ilqr_copy_reset_flags_to_device"); }
   // us[:, t0 : t0 + n_knots, :] as double [B][n_knots][nu] into caller-owned device memory
   void copy_controls_to_device(int t0, int n_knots, void* u_device) {
     check(ilqr_copy_controls_to_device(h_, t0, n_knots, u_device), "ilqr_copy_controls_to_device");
