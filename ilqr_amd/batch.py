@@ -355,6 +355,34 @@ class BatchILQR:
         e.g. torch.Tensor.data_ptr(); either may be None); enqueued on the handle's stream, nothing waited for."""
         self._check(self.lib.ilqr_copy_value_to_device(self.h, int(t0), int(n), Vx_ptr, Vxx_ptr))
 
+    def evaluate_policy(self, x, t0=0, n=None, clamp=False):
+        """The stored feedback policy u = us[t] + K[t](x - xs[t]) applied to the caller's states at knot t0 and rolled through the device
+        model for n knots (n=None: up to knot T).  x: [B][S][nx], S samples per trajectory, or [B][nx] (S = 1).  Returns dict(cost [B][S],
+        x_end [B][S][nx], u_first [B][S][nu]) -- [B], [B][nx], [B][nu] for a [B][nx] input.  The running costs of the window, plus the
+        final cost when it ends at knot T; clamp: controls clamped to the limits (always on a handle with FLAG_REFERENCE_FIXES).  A
+        read-only query: the handle's trajectory, cost and solver state stay as they are (include/ilqr_amd.h, ilqr_evaluate_policy;
+        synchronises)."""
+        x = _c(x)
+        flat = x.ndim == 2
+        if flat:
+            x = x[:, None, :]
+        if x.ndim != 3 or x.shape[0] != self.B or x.shape[2] != self.nx:
+            raise ValueError("evaluate_policy: x must be [B][S][nx] or [B][nx], got %s" % (x.shape,))
+        S = x.shape[1]
+        n = self.T - int(t0) if n is None else int(n)
+        cost, x_end, u_first = np.zeros((self.B, S)), np.zeros((self.B, S, self.nx)), np.zeros((self.B, S, self.nu))
+        self._check(self.lib.ilqr_evaluate_policy(self.h, int(t0), n, S, capi.EVAL_CLAMP if clamp else 0, _p(x), _p(cost), _p(x_end), _p(u_first)))
+        if flat:
+            cost, x_end, u_first = cost[:, 0], x_end[:, 0], u_first[:, 0]
+        return dict(cost=cost, x_end=x_end, u_first=u_first)
+
+    def evaluate_policy_on_device(self, t0, n, S, x_ptr, cost_ptr=None, x_end_ptr=None, u_first_ptr=None, clamp=False):
+        """The same with raw device pointers (torch.Tensor.data_ptr()) to float64 x [B][S][nx], cost [B][S], x_end [B][S][nx], u_first
+        [B][S][nu] on the handle's device; any output may be None, not all three.  Enqueued on the handle's stream, nothing waited for
+        (the stream rule above): x_end of n = shift is the next mpc_step's x0_ptr."""
+        self._check(self.lib.ilqr_evaluate_policy_on_device(self.h, int(t0), int(n), int(S), capi.EVAL_CLAMP if clamp else 0, x_ptr, cost_ptr,
+                                                            x_end_ptr, u_first_ptr))
+
     def derivatives(self):
         n, m, B, T1 = self.nx, self.nu, self.B, self.T + 1
         mem = dict(fx=np.zeros((B, T1, n, n)), fu=np.zeros((B, T1, m, n)), cx=np.zeros((B, T1, n)),

@@ -6,6 +6,7 @@
 
 #include <stdarg.h>
 #include <stdio.h>
+#include <limits.h>
 #include <string.h>
 
 #include <algorithm>
@@ -22,6 +23,7 @@
 #include "kernels.hpp"
 #include "value_thread.hpp"
 #include "value_wave.hpp"
+#include "evaluate.hpp"
 
 using namespace ilqr;
 
@@ -951,6 +953,61 @@ int ilqr_get_value(ilqr_batch* h, int t0, int n_knots, double* Vx, double* Vxx) 
   if (int rc = run_value(h, t0, n_knots, d_vx, d_vxx, "ilqr_get_value")) return rc;
   if (Vx) HIPCHK(hipMemcpyAsync(Vx, d_vx, n_vx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (Vxx) HIPCHK(hipMemcpyAsync(Vxx, d_vxx, n_vxx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// ---- the stored policy applied to caller-given states (additive under ABI 6; evaluate.hpp) ------
+// every refusal the two calls share -- before anything is enqueued --, then an accepted candidate still waiting is copied (as shift_nominal)
+static int prepare_evaluate(ilqr_batch* h, int t0, int n_knots, int n_samples, int flags, const void* x, const void* cost, const void* x_end,
+                            const void* u_first, const char* who) {
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  REQUIRE(x != nullptr, "%s: null x", who);
+  REQUIRE(cost || x_end || u_first, "%s: cost, x_end and u_first are all null", who);
+  REQUIRE(t0 >= 0 && n_knots >= 1 && t0 <= h->T && n_knots <= h->T - t0, "%s: window [%d, %d): inside [0, T = %d], at least one knot", who, t0, t0 + n_knots, h->T);
+  REQUIRE(n_samples >= 1, "%s: n_samples %d must be >= 1", who, n_samples);
+  REQUIRE((long long)h->B * n_samples <= (long long)INT_MAX, "%s: B * n_samples = %d * %d rollouts do not fit an int", who, h->B, n_samples);
+  REQUIRE((flags & ~ILQR_EVAL_CLAMP) == 0, "%s: flags %d: bits of ILQR_EVAL_CLAMP", who, flags);
+  if (host_model(h)) return fail(ILQR_ERR_UNSUPPORTED, "%s: a host-evaluated model exists on the host only (as for ilqr_warm_start)", who);
+  if (!h->initialised) return fail(ILQR_ERR_STATE, "%s before ilqr_init_traj/ilqr_set_trajectory: no policy is stored", who);
+  HIPCHK(hipSetDevice(h->device));
+  return flush_commit(h);
+}
+static int run_evaluate(ilqr_batch* h, const EvalArgs& e, const char* who) {
+  const int rc = launch_evaluate(h, e);
+  if (rc == ILQR_ERR_HIP) {  // (the launch itself was refused: say which kernel)
+    char keep[sizeof(g_err)];
+    memcpy(keep, g_err, sizeof(keep));
+    return fail(rc, "%s: %s: %.400s", who, evaluate_kernel_name(h), keep);
+  }
+  return rc;
+}
+static int eval_clamp(const ilqr_batch* h, int flags) { return ((flags & ILQR_EVAL_CLAMP) || (h->sp.fixes & 1)) ? 1 : 0; }
+
+int ilqr_evaluate_policy_on_device(ilqr_batch* h, int t0, int n_knots, int n_samples, int flags, const void* x_device, void* cost_device,
+                                   void* x_end_device, void* u_first_device) {
+  const char* who = "ilqr_evaluate_policy_on_device";
+  if (int rc = prepare_evaluate(h, t0, n_knots, n_samples, flags, x_device, cost_device, x_end_device, u_first_device, who)) return rc;
+  return run_evaluate(h, {t0, n_knots, n_samples, eval_clamp(h, flags), (const double*)x_device, (double*)cost_device, (double*)x_end_device, (double*)u_first_device}, who);
+}
+
+int ilqr_evaluate_policy(ilqr_batch* h, int t0, int n_knots, int n_samples, int flags, const double* x, double* cost, double* x_end,
+                         double* u_first) {
+  const char* who = "ilqr_evaluate_policy";
+  if (int rc = prepare_evaluate(h, t0, n_knots, n_samples, flags, x, cost, x_end, u_first, who)) return rc;
+  // a call-sized device buffer (the staging buffer: x, then the outputs asked for), copied out and waited for
+  const size_t R = (size_t)h->B * n_samples;
+  const size_t n_x = R * h->nx, n_c = cost ? R : 0, n_e = x_end ? R * h->nx : 0, n_u = u_first ? R * h->nu : 0;
+  if (int rc = ensure_staging(h, n_x + n_c + n_e + n_u)) return rc;
+  double* const d_x = h->staging;
+  double* const d_c = cost ? d_x + n_x : nullptr;
+  double* const d_e = x_end ? d_x + n_x + n_c : nullptr;
+  double* const d_u = u_first ? d_x + n_x + n_c + n_e : nullptr;
+  HIPCHK(hipMemcpyAsync(d_x, x, n_x * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (int rc = run_evaluate(h, {t0, n_knots, n_samples, eval_clamp(h, flags), d_x, d_c, d_e, d_u}, who)) return rc;
+  if (cost) HIPCHK(hipMemcpyAsync(cost, d_c, n_c * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (x_end) HIPCHK(hipMemcpyAsync(x_end, d_e, n_e * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (u_first) HIPCHK(hipMemcpyAsync(u_first, d_u, n_u * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }

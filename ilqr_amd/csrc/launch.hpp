@@ -422,6 +422,32 @@ static int launch_value(ilqr_batch* h, int t0, int nk, double* Vx, double* Vxx, 
   return 0;
 }
 
+// The stored policy applied to caller-given states (ilqr_evaluate_policy / _on_device; evaluate.hpp): picked by the handle's layout alone,
+// as launch_value -- no route bit, no stage timer.  One thread per rollout, B * S of them (the caller has checked that they fit an int).
+static const char* evaluate_kernel_name(const ilqr_batch* h) { return h->aos ? (h->plan.traj_params ? "k_evaluate_g<PT>" : "k_evaluate_g") : "k_evaluate_t"; }
+static int launch_evaluate(ilqr_batch* h, const EvalArgs& e) {
+  const dim3 grid((unsigned)(((size_t)h->B * e.S + 63) / 64)), block(64);
+  if (!h->aos)
+    return with_model(h, [&](auto& v, auto& m, auto&) {
+      hipLaunchKernelGGL((k_evaluate_t<std::decay_t<decltype(m)>>), grid, block, 0, h->stream, v, m, e);
+      HIPCHK(hipGetLastError());
+      return 0;
+    });
+  return with_rollout_model(h, [&](auto& m) {
+    using M = std::decay_t<decltype(m)>;
+    const BatchViewT<typename M::real>& v = view_of<typename M::real>(h);
+    if constexpr (has_trajectory_params<M>::value)
+      if (h->plan.traj_params) {
+        hipLaunchKernelGGL((k_evaluate_g<M, true>), grid, block, 0, h->stream, v, per_trajectory(h, m), e);
+        HIPCHK(hipGetLastError());
+        return 0;
+      }
+    hipLaunchKernelGGL((k_evaluate_g<M>), grid, block, 0, h->stream, v, m, e);
+    HIPCHK(hipGetLastError());
+    return 0;
+  });
+}
+
 static AlphaSet line_search_alphas() {
   AlphaSet a;
   for (int i = 0; i < NALPHA; i++) a.a[i] = kAlphaHost[i];

@@ -341,6 +341,37 @@ int ilqr_get_value(ilqr_batch* h, int t0, int n_knots, double* Vx, double* Vxx);
 /* into caller-owned device memory of this handle's device: enqueued on the handle's stream, not waited for (as ilqr_copy_gains_to_device) */
 int ilqr_copy_value_to_device(ilqr_batch* h, int t0, int n_knots, void* Vx_device, void* Vxx_device);
 
+/* ---- the stored feedback policy applied to caller-given states (additive under ABI 6) -----------------------------------------------
+ * What a solve leaves for a controller is the time-varying law u = us[t] + K[t](x - xs[t]).  These calls apply it to states the CALLER
+ * holds -- n_samples of them per trajectory, at knot t0 -- and roll it through the handle's device model for n_knots knots; a read-only
+ * query: the nominal is read, only the outputs are written.  DEFINITION -- with xs, us, K as ilqr_get_trajectory / ilqr_get_gains would
+ * return them at this moment (an accepted candidate still waiting to be copied is copied first), for trajectory b and sample s:
+ *     x_{t0} = x[b][s]
+ *     t = t0 .. t0 + n_knots - 1:   u_t = us[b][t] + K[b][t](x_t - xs[b][t])          (src/ilqr_core.cpp:316 without alpha k: k is not part of the policy)
+ *                                   clamp:  u_t = min(max(u_t, u_min), u_max)         (ILQR_EVAL_CLAMP, or a handle with ILQR_FLAG_REFERENCE_FIXES)
+ *                                   cost += model.cost(x_t, u_t),  x_{t+1} = x_t + dt model.dynamics(x_t, u_t)
+ *     t0 + n_knots == T:            cost += model.final_cost(x_T)                      (a shorter window carries running costs only)
+ *     cost[b][s],   x_end[b][s] = x_{t0 + n_knots},   u_first[b][s] = u_{t0}  (the clamped value under the clamp)
+ * The arithmetic is the handle's rollout arithmetic, expression for expression: (t0 = 0, n_knots = T, one sample) gives the bits
+ * ilqr_mpc_step(x, shift = 0, n_iters = 0) leaves in cost, xs[T] and us[0].  An fp32 handle rounds x to float where it is loaded, keeps
+ * states and controls in float and sums the costs in double.  Every output is canonical double on every handle:
+ *     x [B][n_samples][nx]     cost [B][n_samples]     x_end [B][n_samples][nx]     u_first [B][n_samples][nu]
+ * Any output may be NULL, not all three.  With per-trajectory parameters set, every sample of trajectory b uses row b.  A rollout that
+ * overflows leaves inf or NaN in its own outputs and nothing else.  x0, cost, the candidates, lambda and status are not touched: later
+ * iterations are bit for bit those of a handle that never called.  Uses: n_knots = 1 -- u_first is the control for a measured state
+ * between re-plans; n_knots = shift -- x_end is a model-based plant's next x0, handed to ilqr_mpc_step(x0_device); n_knots = T - t0 with
+ * many samples -- the closed-loop cost of the policy from perturbed states.
+ * ILQR_ERR_INVALID: null x, three NULL outputs, a window outside [0, T] or without a knot, n_samples < 1, B * n_samples beyond INT_MAX,
+ * unknown flag bits; ILQR_ERR_STATE: before ilqr_init_traj / ilqr_set_trajectory; ILQR_ERR_UNSUPPORTED: ILQR_MODEL_HOST (its model
+ * exists on the host only, as for ilqr_warm_start).  Every refusal happens before anything is enqueued. */
+enum ilqr_eval_flags { ILQR_EVAL_CLAMP = 1 };
+/* host arrays: x goes up into a device buffer of the call's size, the outputs come back from it; synchronises */
+int ilqr_evaluate_policy(ilqr_batch* h, int t0, int n_knots, int n_samples, int flags, const double* x, double* cost, double* x_end,
+                         double* u_first);
+/* device memory of this handle's device: enqueued on the handle's stream, nothing waited for, no staging buffer */
+int ilqr_evaluate_policy_on_device(ilqr_batch* h, int t0, int n_knots, int n_samples, int flags, const void* x_device, void* cost_device,
+                                   void* x_end_device, void* u_first_device);
+
 /* ---- per-trajectory model parameters (additive under ABI 6) ----------------------------------------------------------------------
  * A user device twin may declare NTP parameters that differ from trajectory to trajectory (csrc/models.hpp: NTP, set_trajectory_params) --
  * a target that moves between receding-horizon steps, a perturbed model per trajectory.  Once set, every later rollout, derivative sweep

@@ -379,6 +379,26 @@ class BatchILQR {
   void copy_value_to_device(int t0, int n_knots, void* Vx_device, void* Vxx_device) {
     check(ilqr_copy_value_to_device(h_, t0, n_knots, Vx_device, Vxx_device), "ilqr_copy_value_to_device");
   }
+  // The stored feedback policy u = us[t] + K[t](x - xs[t]) applied to the caller's states at knot t0 and rolled through the device model for
+  // n_knots knots (n_knots < 0: up to knot T; ilqr_evaluate_policy): x [B][S][nx], S = n_samples states per trajectory; cost [B][S], x_end
+  // [B][S][nx], u_first [B][S][nu]; any output pointer may be null, not all three.  A read-only query of the handle.
+  void evaluate_policy(const std::vector<double>& x, int n_samples, std::vector<double>* cost, std::vector<double>* x_end, std::vector<double>* u_first,
+                       int t0 = 0, int n_knots = -1, int flags = 0) {
+    if (n_knots < 0) n_knots = T_ - t0;
+    require(n_samples >= 1 && x.size() == (size_t)B_ * n_samples * n_, "evaluate_policy: x [B][n_samples][nx]");
+    const size_t R = (size_t)B_ * n_samples;
+    if (cost) cost->assign(R, 0.0);
+    if (x_end) x_end->assign(R * n_, 0.0);
+    if (u_first) u_first->assign(R * m_, 0.0);
+    check(ilqr_evaluate_policy(h_, t0, n_knots, n_samples, flags, x.data(), cost ? cost->data() : nullptr, x_end ? x_end->data() : nullptr,
+                               u_first ? u_first->data() : nullptr), "ilqr_evaluate_policy");
+  }
+  // ... with device pointers of the handle's device, on the handle's stream, nothing waited for: x_end of n_knots = shift is the next
+  // mpc_step(x0_device)'s state
+  void evaluate_policy_on_device(int t0, int n_knots, int n_samples, const void* x_device, void* cost_device, void* x_end_device, void* u_first_device,
+                                 int flags = 0) {
+    check(ilqr_evaluate_policy_on_device(h_, t0, n_knots, n_samples, flags, x_device, cost_device, x_end_device, u_first_device), "ilqr_evaluate_policy_on_device");
+  }
   // Every result in one call (ABI 5): the device-to-host copies are enqueued back to back, nothing is waited for until synchronize().
   // The buffers belong to the caller (sizes as the getters above; nullptr = skip); page-lock buffers that are reused across solves once
   // with ilqr_host_register so that the copies are DMA transfers.
@@ -922,6 +942,16 @@ class iLQR {
       for (int j = 0; j < n; j++)
         for (int a = 0; a < n; a++) Vxx[t](a, j) = vxx[(size_t)t * n * n + a + (size_t)n * j];
     }
+  }
+  // the control the stored policy gives at knot t in the state x: us[t] + K[t](x - xs[t]), evaluated on the device (ilqr_evaluate_policy, one knot)
+  VectorXd feedback_control(int t, const VectorXd& x) const {
+    if (!engine_) throw std::logic_error("feedback_control(): no trajectory initialised");
+    const int m = model->u_dims;
+    std::vector<double> xv(x.data(), x.data() + x.size()), u;
+    engine_->evaluate_policy(xv, 1, nullptr, nullptr, &u, t, 1);
+    VectorXd out(m);
+    for (int j = 0; j < m; j++) out(j) = u[j];
+    return out;
   }
   double cost() const { return engine_->cost()[0]; }
   int iterations() const { return engine_->iterations()[0]; }

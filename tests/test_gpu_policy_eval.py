@@ -1,0 +1,399 @@
+"""The stored feedback policy applied to caller-given states on the device (ilqr_evaluate_policy, ilqr_evaluate_policy_on_device;
+k_evaluate_t / k_evaluate_g, csrc/evaluate.hpp).
+
+- (t0 = 0, n = T, one sample) gives the warm start's bits in cost, xs[T] and us[0], on every kind of handle;
+- cost, x_end and u_first agree with the oracle's closed-loop rollout of the window within 1e-9 (fp64; policy_reference below, itself
+  held to its f80 flavour at 1e-10 by tests/test_policy_eval_abi.py), the clamp included; fp32 costs within 1e-5;
+- samples are independent of their neighbours in the wavefront, windows compose, device pointers give the host call's bits;
+- the call is read-only: later iterations are bit for bit those of a handle that never called it;
+- per-trajectory parameter rows reach every sample of their trajectory; what is refused.
+
+Shapes: the small ones of tests/test_gpu_mpc.py (B = 37: no multiple of 16 or 64; T = 45: no multiple of 8); S = 3 packs several ragged
+trajectories into a wavefront, S = 70 lets one trajectory's samples cross a wavefront boundary."""
+import numpy as np
+import pytest
+
+from tests.test_gpu_mpc import B, CHAIN_PARAMS, DT, T, lq_mats, make, problem
+from tests.util import relerr
+
+pytestmark = pytest.mark.gpu
+ERR_INVALID, ERR_STATE, ERR_UNSUPPORTED = -1, -4, -5
+KINDS = ["acrobot_f64", "acrobot_f32", "integrator", "lq_f64", "lq_f32", "lq20", "chain", "twin6"]
+KINDS64 = [k for k in KINDS if not k.endswith("f32")]
+SAMPLES = (1, 3, 70)
+WINDOWS = [(t0, n) for t0 in (0, 7, T - 1) for n in sorted({1, 5, T - t0}) if t0 + n <= T]
+# fp64 against policy_reference.  The reference sits at 3e-15 from its f80 flavour on these inputs (tests/test_policy_eval_abi.py); the device
+# differs from it by contraction and its own sincos, which tests/test_gpu_fixes.py holds to 1e-12 on an open-loop T = 45 rollout: 1e-9
+# leaves three orders for the closed loop's amplification by gains up to |K| = 64, and stays three orders inside the project's 1e-6.
+TOL_ORACLE = 1e-9
+TOL_F32 = 1e-5     # the project's fp32 tolerance, cost only
+
+
+# ---- the problems (CPU side too: tests/test_policy_eval_abi.py imports these) --------------------------------------------------------
+def twin6_mats():
+    from tests.test_gpu_lq_end_to_end import dense_mats
+    return dense_mats(6, 2, seed=5)
+
+
+def kind_problem(kind, libs=None):
+    """(constructor kwargs, x0 [B][nx], nu) of a handle kind; libs: dict(chain=..., twin6=...) of the twins' library paths"""
+    libs = libs or {}
+    if kind == "twin6":  # the n = 6 small twin on its default tiled route
+        mats = twin6_mats()
+        params = np.concatenate([np.ascontiguousarray(a).ravel() for a in mats])
+        x0 = np.random.default_rng(3).uniform(-1, 1, (B, 6))
+        return dict(model="user", lib=libs.get("twin6"), nx=6, nu=2, u_min=-0.4, u_max=0.4, user_params=params), x0, 2
+    return problem(kind, libs.get("chain"))
+
+
+def oracle_model(oracle, kind):
+    if kind.startswith("acrobot"):
+        return oracle.Model("acrobot", u_lim=1.5)
+    if kind.startswith("integrator"):
+        return oracle.Model("integrator", goal=[1, .5, 0, 0])
+    if kind.startswith("lq20"):
+        return oracle.Model("lq", lq=lq_mats(8, 20), u_lim=0.4)
+    if kind.startswith("lq"):
+        return oracle.Model("lq", lq=lq_mats(6, 3), u_lim=0.4)
+    if kind.startswith("chain"):
+        return oracle.Model("chain", chain=(8, CHAIN_PARAMS), u_lim=2.0)
+    if kind == "twin6":
+        return oracle.Model("lq", lq=twin6_mats(), u_lim=0.4)
+    raise KeyError(kind)
+
+
+def initial_controls(nu):
+    return np.zeros((B, T, nu))
+
+
+def draw_samples(xs, t0, S, seed=29):
+    """x = xs[:, t0] + 0.05 N(0, 1): [B][S][nx]"""
+    rng = np.random.default_rng(seed + 1000 * t0 + S)
+    return xs[:, t0][:, None, :] + 0.05 * rng.standard_normal((xs.shape[0], S, xs.shape[2]))
+
+
+def policy_reference(oracle, om, xs, us, K, x, t0, n, dt=DT):
+    """The definition on the oracle: for every (trajectory, sample) pair oracle.batch_rollout of the window's slices around the nominal
+    repeated per sample.  A window that ends before knot T carries running costs only: they are summed knot by knot through the model's
+    own cost(), in the rollout's order -- taking final_cost(x_end) off batch_rollout's total instead cancels (acrobot: a final cost of
+    1e3 against a one-knot running cost of 1e-5 left 5e-8 of the yardstick's own error, against 1e-9 asked of the device).
+    xs [B][T+1][nx], us [B][T][nu], K [B][T][nu][nx], x [B][S][nx]; returns cost [B][S], x_end [B][S][nx], u_first [B][S][nu] in the
+    current flavour's types."""
+    Bn, S, nx = x.shape
+    Tn = us.shape[1]
+    rep = lambda a: np.repeat(np.asarray(a), S, axis=0)
+    xs_o, us_o, cost = oracle.batch_rollout(om, x.reshape(Bn * S, nx), rep(us[:, t0:t0 + n]), dt, xs_nom=rep(xs[:, t0:t0 + n + 1]), K=rep(K[:, t0:t0 + n]))
+    x_end = xs_o[:, n]
+    if t0 + n < Tn:
+        cost = np.zeros_like(cost)
+        for t in range(n):
+            cost += np.array([om.cost(xs_o[r, t], us_o[r, t]) for r in range(Bn * S)], dtype=cost.dtype)
+    return cost.reshape(Bn, S), x_end.reshape(Bn, S, nx), us_o[:, 0].reshape(Bn, S, -1)
+
+
+# ---- handles ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module", autouse=True)
+def torch_device_first():
+    """torch's device is initialised before this module creates any handle (tests/test_gpu_mpc.py)"""
+    import torch
+    assert torch.cuda.is_available()
+    torch.cuda.init()
+
+
+@pytest.fixture(scope="module")
+def libs():
+    from ilqr_amd import _build
+    return dict(chain=_build.build_user(_build.USER_CHAIN_HEADER, _build.USER_CHAIN_LIB),
+                twin6=_build.build_user(_build.USER_EXAMPLE6_HEADER, _build.USER_EXAMPLE6_LIB))
+
+
+def solved(kind, libs, **extra):
+    """a handle of the kind after init_traj(x0, u0) and iterate(3): the policy under test"""
+    kw, x0, nu = kind_problem(kind, libs)
+    g = make(kw, dtype="f32" if kind.endswith("f32") else "f64", **extra)
+    g.init_traj(x0, initial_controls(nu))
+    g.iterate(3)
+    return g
+
+
+@pytest.fixture
+def policies(libs):
+    """policies(kind): a solved handle of the kind with its nominal (xs, us, K), closed when the test ends -- at most a few handles
+    (each with a stream of its own) are alive at a time, as everywhere else in the suite"""
+    made = []
+
+    def get(kind):
+        g = solved(kind, libs)
+        made.append(g)
+        xs, us = g.trajectory()
+        return g, xs, us, g.gains()[1]
+    yield get
+    for g in made:
+        g.close()
+
+
+def state(g):
+    xs, us = g.trajectory()
+    k, K = g.gains()
+    lam, dlam = g.lambdas()
+    return dict(xs=xs, us=us, k=k, K=K, cost=g.cost(), lam=lam, dlam=dlam, status=np.stack(g.status()))
+
+
+def assert_same_state(a, b):
+    for key in a:
+        assert np.array_equal(a[key], b[key]), key
+
+
+# ---- 1. the warm start's bits ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", KINDS + ["acrobot_fixes"])
+def test_full_horizon_single_sample_is_the_warm_start(kind, libs):
+    from ilqr_amd import capi
+    extra = dict(flags=capi.FLAG_REFERENCE_FIXES) if kind == "acrobot_fixes" else {}  # the clamp comes from the handle flag
+    name = "acrobot_f64" if kind == "acrobot_fixes" else kind
+    ga, gb = solved(name, libs, **extra), solved(name, libs, **extra)
+    x_new = ga.trajectory()[0][:, 0] + 0.05 * np.random.default_rng(41).standard_normal((B, ga.nx))
+    r = ga.evaluate_policy(x_new)  # [B][nx]: S = 1, t0 = 0, n = T
+    gb.mpc_step(x0=x_new, shift=0, iters=0)
+    xs_b, us_b = gb.trajectory()
+    assert np.all(np.isfinite(r["cost"]))
+    assert np.array_equal(r["cost"], gb.cost())
+    assert np.array_equal(r["x_end"], xs_b[:, T])
+    assert np.array_equal(r["u_first"], us_b[:, 0])
+    if kind == "acrobot_fixes":
+        assert np.abs(r["u_first"]).max() <= 1.5
+    ga.close()
+    gb.close()
+
+
+# ---- 2. the oracle ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("S", SAMPLES)
+@pytest.mark.parametrize("kind", KINDS64)
+def test_windows_match_the_oracle(oracle, policies, kind, S):
+    g, xs, us, K = policies(kind)
+    om = oracle_model(oracle, kind)
+    worst = 0.0
+    for t0, n in WINDOWS:
+        x = draw_samples(xs, t0, S)
+        got = g.evaluate_policy(x, t0=t0, n=n)
+        want = policy_reference(oracle, om, xs, us, K, x, t0, n)
+        for key, w in zip(("cost", "x_end", "u_first"), want):
+            err = relerr(got[key], w)
+            worst = max(worst, err)
+            print("%s S=%d window (%d, %d) %s relerr %.2e" % (kind, S, t0, n, key, err))
+            assert err < TOL_ORACLE, (kind, S, t0, n, key, err)
+    print("%s S=%d worst %.2e" % (kind, S, worst))
+
+
+@pytest.mark.parametrize("kind", KINDS64)
+def test_clamp_flag_matches_the_oracle_with_the_clamped_rollout(oracle, policies, kind):
+    g, xs, us, K = policies(kind)
+    om = oracle_model(oracle, kind)
+    S, t0, n = 3, 0, T
+    x = draw_samples(xs, t0, S)
+    free = g.evaluate_policy(x, t0=t0, n=n)
+    got = g.evaluate_policy(x, t0=t0, n=n, clamp=True)
+    want_free = policy_reference(oracle, om, xs, us, K, x, t0, n)
+    try:
+        oracle.set_fixes(1)
+        want = policy_reference(oracle, om, xs, us, K, x, t0, n)
+    finally:
+        oracle.set_fixes(0)
+    for key, w in zip(("cost", "x_end", "u_first"), want):
+        err = relerr(got[key], w)
+        print("%s clamp %s relerr %.2e" % (kind, key, err))
+        assert err < TOL_ORACLE, (kind, key, err)
+    lo, hi = om.u_min, om.u_max
+    assert np.all(got["u_first"] >= lo) and np.all(got["u_first"] <= hi)
+    bites = want[0] != want_free[0]  # rollouts on which the clamp changes the oracle's cost
+    print("%s: the clamp bites on %d of %d rollouts" % (kind, bites.sum(), bites.size))
+    assert np.array_equal(got["cost"] != free["cost"], bites)
+    if kind == "acrobot_f64":
+        assert bites.mean() >= 0.5
+
+
+# ---- 3. fp32 -----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", [k for k in KINDS if k.endswith("f32")])
+def test_fp32_costs_against_the_fp64_oracle(oracle, policies, kind):
+    g, xs, us, K = policies(kind)  # the getters widen the stored floats: the handle's own float-rounded nominal
+    om = oracle_model(oracle, kind)
+    for S in SAMPLES:
+        for t0, n in ((0, T), (7, 5)):
+            x = draw_samples(xs, t0, S).astype(np.float32).astype(np.float64)
+            got = g.evaluate_policy(x, t0=t0, n=n)
+            want = policy_reference(oracle, om, xs, us, K, x, t0, n)
+            err = np.max(np.abs(got["cost"] - want[0]) / np.abs(want[0]))
+            print("%s S=%d window (%d, %d) cost relerr %.2e" % (kind, S, t0, n, err))
+            assert err < TOL_F32, (kind, S, t0, n, err)
+            assert np.array_equal(got["x_end"], got["x_end"].astype(np.float32).astype(np.float64))  # float states, widened
+
+
+# ---- 4. samples are independent -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", KINDS)
+def test_a_sample_does_not_depend_on_its_neighbours(policies, kind):
+    g, xs, us, K = policies(kind)
+    x = draw_samples(xs, 0, 70)
+    many = g.evaluate_policy(x)
+    for s in (0, 63, 64, 69):
+        one = g.evaluate_policy(x[:, s])
+        for b in (0, 17, B - 1):
+            for key in ("cost", "x_end", "u_first"):
+                assert np.array_equal(many[key][b, s], one[key][b]), (kind, s, b, key)
+
+
+# ---- 5. windows compose ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", KINDS)
+def test_two_windows_compose_into_the_whole(policies, kind):
+    g, xs, us, K = policies(kind)
+    x = draw_samples(xs, 0, 3)
+    whole = g.evaluate_policy(x)
+    head = g.evaluate_policy(x, t0=0, n=7)
+    tail = g.evaluate_policy(head["x_end"], t0=7, n=T - 7)
+    assert np.array_equal(tail["x_end"], whole["x_end"])
+    assert np.array_equal(head["u_first"], whole["u_first"])
+    if not kind.endswith("f32"):
+        err = np.max(np.abs(head["cost"] + tail["cost"] - whole["cost"]) / np.abs(whole["cost"]))
+        print("%s: cost of two windows against the whole: %.2e" % (kind, err))
+        assert err < 1e-12
+
+
+# ---- 6. device pointers ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["acrobot_f64", "acrobot_f32", "lq_f64", "lq_f32", "chain", "twin6"])
+def test_device_pointers_give_the_host_calls_bits(kind, libs):
+    import torch
+    stream = torch.cuda.Stream()  # (a handle given the null stream makes a stream of its own: tests/test_gpu_mpc.py)
+    with torch.cuda.stream(stream):
+        gh, gd = solved(kind, libs), solved(kind, libs, stream=stream.cuda_stream)
+        nx, nu = gh.nx, gh.nu
+        xs = gh.trajectory()[0]
+        for S, t0, n in ((3, 7, 5), (70, 0, T), (1, 0, 1)):
+            x = draw_samples(xs, t0, S)
+            want = gh.evaluate_policy(x, t0=t0, n=n)
+            xd = torch.from_numpy(x).cuda(non_blocking=True)
+            out = dict(cost=torch.full((B, S), np.nan, dtype=torch.float64, device="cuda"),
+                       x_end=torch.full((B, S, nx), np.nan, dtype=torch.float64, device="cuda"),
+                       u_first=torch.full((B, S, nu), np.nan, dtype=torch.float64, device="cuda"))
+            gd.evaluate_policy_on_device(t0, n, S, xd.data_ptr(), out["cost"].data_ptr(), out["x_end"].data_ptr(), out["u_first"].data_ptr())
+            only = torch.full((B, S, nu), np.nan, dtype=torch.float64, device="cuda")
+            gd.evaluate_policy_on_device(t0, n, S, xd.data_ptr(), None, None, only.data_ptr())  # NULL outputs are skipped
+            stream.synchronize()
+            for key in want:
+                assert np.array_equal(out[key].cpu().numpy(), want[key]), (kind, S, t0, n, key)
+            assert np.array_equal(only.cpu().numpy(), want["u_first"])
+        # the plant step: x_end of n = shift, in device memory, is the next step's x0
+        x = draw_samples(xs, 0, 1)
+        want = gh.evaluate_policy(x, t0=0, n=1)
+        gh.mpc_step(x0=want["x_end"][:, 0], shift=1, iters=1)
+        xd = torch.from_numpy(x).cuda(non_blocking=True)
+        x_next = torch.full((B, 1, nx), np.nan, dtype=torch.float64, device="cuda")
+        gd.evaluate_policy_on_device(0, 1, 1, xd.data_ptr(), None, x_next.data_ptr(), None)
+        gd.mpc_step(x0_ptr=x_next.data_ptr(), shift=1, iters=1)
+        stream.synchronize()
+        assert_same_state(state(gh), state(gd))
+        gh.close()
+        gd.close()
+
+
+# ---- 7. read-only ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", KINDS)
+def test_evaluating_leaves_the_handle_as_it_was(kind, libs):
+    kw, x0, nu = kind_problem(kind, libs)
+    dtype = "f32" if kind.endswith("f32") else "f64"
+    ga, gb = make(kw, dtype=dtype), make(kw, dtype=dtype)
+    for g in (ga, gb):
+        g.init_traj(x0, initial_controls(nu))
+        g.iterate(2)
+    x = draw_samples(ga.trajectory()[0], 0, 70)
+    first = ga.evaluate_policy(x)
+    ga.evaluate_policy(x[:, :3], t0=7, n=5, clamp=True)
+    for g in (ga, gb):
+        g.iterate(2)
+        g.compute_derivatives()
+        g.backward_pass()
+        g.line_search()  # the stage call
+    again = ga.evaluate_policy(x)
+    assert np.all(np.isfinite(first["cost"])) and not np.array_equal(first["cost"], again["cost"])  # (the policy moved in between)
+    assert_same_state(state(ga), state(gb))
+    for g in (ga, gb):
+        g.iterate(1)
+    assert_same_state(state(ga), state(gb))
+    ga.close()
+    gb.close()
+
+
+# ---- 8. per-trajectory parameters -----------------------------------------------------------------------------------------------------
+def test_every_sample_of_a_trajectory_uses_its_row(libs):
+    from tests.test_gpu_traj_params import draw_params, handle
+    lim = 2.0
+    _, x0, nu = kind_problem("chain", libs)
+    params = draw_params(B, 41)
+    g = handle(libs["chain"], B, T, lim)
+    g.set_trajectory_params(params)
+    g.init_traj(x0, initial_controls(nu))
+    g.iterate(3)
+    xs, us = g.trajectory()
+    k, K = g.gains()
+    x = draw_samples(xs, 0, 70)
+    rows = {(t0, n): g.evaluate_policy(x, t0=t0, n=n) for t0, n in ((0, T), (7, 5))}
+    from ilqr_amd import BatchILQR
+    for b in (0, 17, B - 1):  # a handle whose handle-wide parameters are row b, carrying the same policy
+        hb = BatchILQR("user", B, T, DT, u_min=-lim, u_max=lim, lib=libs["chain"], nx=g.nx, nu=g.nu, user_params=params[b])
+        hb.set_trajectory(x0=x0, xs=xs, us=us, cost=g.cost())
+        hb.set_gains(k=k, K=K)
+        for (t0, n), want in rows.items():
+            got = hb.evaluate_policy(x, t0=t0, n=n)
+            for key in want:
+                assert np.array_equal(got[key][b], want[key][b]), (b, t0, n, key)
+        hb.close()
+    g.clear_trajectory_params()
+    plain = g.evaluate_policy(x)
+    assert np.all(plain["cost"] != rows[(0, T)]["cost"])
+    g.close()
+
+
+# ---- 9. refusals ---------------------------------------------------------------------------------------------------------------------
+def test_refusals(libs):
+    import ctypes as C
+    from ilqr_amd import BatchILQR, capi
+    kw, x0, nu = kind_problem("acrobot_f64")
+    g = make(kw)
+    lib, h = g.lib, g.h
+    S = 2
+    x = np.ascontiguousarray(np.repeat(x0[:, None, :], S, axis=1))
+    cost, x_end, u_first = np.zeros((B, S)), np.zeros((B, S, 4)), np.zeros((B, S, 1))
+    p = lambda a: a.ctypes.data_as(capi._dp)
+    call = lambda t0, n, s, fl, xx=x, c=cost, e=x_end, u=u_first: lib.ilqr_evaluate_policy(h, t0, n, s, fl, p(xx) if xx is not None else None,
+                                                                                      p(c) if c is not None else None, p(e) if e is not None else None,
+                                                                                      p(u) if u is not None else None)
+    dev = lambda t0, n, s, fl, xx=x.ctypes.data, c=cost.ctypes.data: lib.ilqr_evaluate_policy_on_device(h, t0, n, s, fl, xx, c, None, None)
+    # (the device call's refusals come before anything is enqueued: host addresses in place of device pointers are never dereferenced)
+    assert call(0, T, S, 0) == ERR_STATE and b"ilqr_evaluate_policy before" in lib.ilqr_last_error()  # before any trajectory
+    assert dev(0, T, S, 0) == ERR_STATE
+    g.init_traj(x0, np.zeros((B, T, nu)))
+    g.iterate(1)
+    ref = state(g)
+    assert lib.ilqr_evaluate_policy(None, 0, T, S, 0, p(x), p(cost), None, None) == ERR_INVALID and b"null handle" in lib.ilqr_last_error()
+    assert lib.ilqr_evaluate_policy_on_device(None, 0, T, S, 0, x.ctypes.data, cost.ctypes.data, None, None) == ERR_INVALID
+    bad = [dict(xx=None), dict(c=None, e=None, u=None)]
+    for kwargs in bad:
+        assert call(0, T, S, 0, **kwargs) == ERR_INVALID, kwargs
+    assert dev(0, T, S, 0, xx=None) == ERR_INVALID and dev(0, T, S, 0, c=None) == ERR_INVALID
+    big = (2 ** 31 - 1) // B + 1  # B * n_samples just past INT_MAX: refused before any buffer of that size is thought of
+    for t0, n, s, fl in ((-1, 1, S, 0), (0, 0, S, 0), (0, -3, S, 0), (0, T + 1, S, 0), (T - 2, 3, S, 0), (T, 1, S, 0), (2 ** 31 - 1, 2, S, 0),
+                         (0, T, 0, 0), (0, T, -1, 0), (0, T, big, 0), (0, T, S, 2), (0, T, S, -1)):
+        assert call(t0, n, s, fl) == ERR_INVALID, (t0, n, s, fl)
+        assert dev(t0, n, s, fl) == ERR_INVALID, (t0, n, s, fl)
+    assert_same_state(state(g), ref)  # nothing refused changed anything
+    assert call(T - 1, 1, S, capi.EVAL_CLAMP) == 0 and call(0, T, S, 0, c=None, e=None) == 0  # ... and the edges are served
+    g.iterate(1)  # the handle still iterates
+    assert np.all(np.isfinite(g.cost()))
+    g.close()
+    hm = BatchILQR("host", B, T, DT, nx=5, nu=3, u_min=-1.0, u_max=1.0)
+    rng = np.random.default_rng(2)
+    hm.set_trajectory(x0=rng.normal(size=(B, 5)), xs=rng.normal(size=(B, T + 1, 5)), us=rng.normal(size=(B, T, 3)))
+    x5 = np.ascontiguousarray(rng.normal(size=(B, 1, 5)))
+    c5 = np.zeros((B, 1))
+    assert hm.lib.ilqr_evaluate_policy(hm.h, 0, T, 1, 0, p(x5), p(c5), None, None) == ERR_UNSUPPORTED
+    assert hm.lib.ilqr_evaluate_policy_on_device(hm.h, 0, T, 1, 0, x5.ctypes.data, c5.ctypes.data, None, None) == ERR_UNSUPPORTED
+    with pytest.raises(capi.ILQRError, match="-5"):
+        hm.evaluate_policy(x5)
+    hm.close()
