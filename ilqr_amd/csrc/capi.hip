@@ -370,8 +370,7 @@ static int plan_and_reset(const ilqr_desc* d, ilqr_batch* h) {
   sp.lambda_factor = p.lambda_factor; sp.lambda_max = p.lambda_max; sp.lambda_min = p.lambda_min;
   sp.fixed_work = (h->flags & ILQR_FLAG_FIXED_WORK) ? 1 : 0;
   sp.fixes = ((h->flags & ILQR_FLAG_REFERENCE_FIXES) ? 3 : 0) | ((h->flags & ILQR_FLAG_REGULARIZE_VXX) ? 4 : 0);
-  hipLaunchKernelGGL(k_reset_state<double>, dim3((h->Bp + 255) / 256), dim3(256), 0, h->stream, h->v, p.lambda_init, p.dlambda_init);
-  HIPCHK(hipGetLastError());
+  if (int rc = launch_per_slot(h, k_reset_state<double>, h->v, p.lambda_init, p.dlambda_init)) return rc;
   if (h->plan.derivatives == Derivatives::fused_lq) {  // both constant records, once (what = 3), in double on every handle
     BatchView cv = h->v;
     if (h->dtype == ILQR_DTYPE_F32) cv.xs = h->const_rec + 2 * rec_of(h);  // (an fp32 handle's xs holds floats: the zero knot behind the records)
@@ -439,16 +438,7 @@ int ilqr_init_traj(ilqr_batch* h, const double* x0, const double* u0, double* co
   HIPCHK(hipSetDevice(h->device));
   if (int rc = upload(h, x0, {h->v.x0, 1, h->nx})) return rc;
   if (int rc = upload(h, u0, {h->v.us, h->T, h->nu})) return rc;  // us = u_0, ilqr_core.cpp:17
-  // ilqr_core.cpp:23-48: zero derivative/gain arrays; statics lambda/dlambda as for a fresh process
-  const size_t T = h->T, T1 = h->T + 1;
-  if (h->v.D) HIPCHK(hipMemsetAsync(h->v.D, 0, dev_elems(h, T1, rec_of(h)) * elem_size(h), h->stream));
-  h->recs = ilqr_batch::REC_ZERO;
-  HIPCHK(hipMemsetAsync(h->v.kff, 0, dev_elems(h, T, h->nu) * elem_size(h), h->stream));
-  HIPCHK(hipMemsetAsync(h->v.Kfb, 0, dev_elems(h, T, h->nu * h->nx) * elem_size(h), h->stream));
-  if (int rc = forget_pending(h)) return rc;
-  hipLaunchKernelGGL(k_reset_state<double>, dim3((h->Bp + 255) / 256), dim3(256), 0, h->stream, h->v, h->params.lambda_init,
-                     h->params.dlambda_init);
-  HIPCHK(hipGetLastError());
+  if (int rc = fresh_trajectory(h)) return rc;
   // ilqr_core.cpp:20: open-loop rollout (K is empty); writes xs, us, cost in place
   AlphaSet al = line_search_alphas();
   if (int rc = launch_rollout(h, false, false, al, 1, h->v.cost, 0)) return rc;
@@ -634,32 +624,38 @@ int ilqr_solve(ilqr_batch* h, const double* x0, const double* u0) {
   return ilqr_generate_trajectory(h);
 }
 
+// The warm rollout, forward_pass(x_0, us) with the stored gains: u = us[t] + K[t](x - xs[t]) (every alpha 0), written into xs / us -- by the
+// rollout itself on the generic path (slot commit_idx = 0 of `al` for everyone), by a commit of slot 0 on the tiled one.  repeat
+// (ilqr_mpc_step_reset's second pass): commit_idx already says who is rolled out again (k_select_reset); a tiled rollout scores whole
+// tiles, so its costs go through a scratch row (cost_c's first plane: the candidates are nobody's during a step)
+static int warm_rollout_commit(ilqr_batch* h, bool repeat) {
+  AlphaSet al;
+  for (int i = 0; i < NALPHA; i++) al.a[i] = 0.0;
+  if (h->plan.commit != Commit::tiled) {
+    if (!repeat) HIPCHK(hipMemsetAsync(h->commit_idx, 0, (size_t)h->Bp * sizeof(int), h->stream));
+    if (int rc = launch_rollout(h, true, true, al, 1, h->v.cost, 0)) return rc;
+  } else {
+    if (int rc = launch_rollout(h, true, true, al, 1, repeat ? h->v.cost_c : h->v.cost, 0)) return rc;
+    if (!repeat) HIPCHK(hipMemsetAsync(h->commit_idx, 0, (size_t)h->Bp * sizeof(int), h->stream));
+    if (int rc = launch_commit(h)) return rc;
+    if (repeat) {
+      hipLaunchKernelGGL(k_take_reset_cost, dim3((h->B + 255) / 256), dim3(256), 0, h->stream, h->v.cost_c, reset_sel(h), h->v.cost, h->B);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  HIPCHK(hipMemsetAsync(h->commit_idx, 0xFF, (size_t)h->Bp * sizeof(int), h->stream));
+  return 0;
+}
+
 int ilqr_warm_start(ilqr_batch* h, const double* x0) {
   if (!h || !x0) return fail(ILQR_ERR_INVALID, "null argument");
   if (host_model(h)) return no_device_model();
   if (!h->initialised) return fail(ILQR_ERR_STATE, "warm start needs a previous solve (assert us.size()>0, ilqr_core.cpp:66)");
   HIPCHK(hipSetDevice(h->device));
   if (int rc = upload(h, x0, {h->v.x0, 1, h->nx})) return rc;
-  // forward_pass(x_0, us) with the stored gains: u = us[t] + K[t](x - xs[t])  (alpha*k term = 0)
-  AlphaSet al;
-  for (int i = 0; i < NALPHA; i++) al.a[i] = 0.0;
-  if (h->plan.commit != Commit::tiled) {  // generic path: the rollout itself overwrites xs/us (slot 0 of `al` for everyone)
-    HIPCHK(hipMemsetAsync(h->commit_idx, 0, (size_t)h->Bp * sizeof(int), h->stream));
-    if (int rc = launch_rollout(h, true, true, al, 1, h->v.cost, 0)) return rc;
-  } else {
-    if (int rc = launch_rollout(h, true, true, al, 1, h->v.cost, 0)) return rc;
-    HIPCHK(hipMemsetAsync(h->commit_idx, 0, (size_t)h->Bp * sizeof(int), h->stream));  // slot 0 for everyone
-    if (int rc = launch_commit(h)) return rc;
-  }
-  HIPCHK(hipMemsetAsync(h->commit_idx, 0xFF, (size_t)h->Bp * sizeof(int), h->stream));
+  if (int rc = warm_rollout_commit(h, false)) return rc;
   // a new outer loop starts: status/iters/flgChange reset, lambda & dlambda persist (file statics)
-  std::vector<double> lam(h->B), dlam(h->B);
-  if (int rc = scalars_to_host(h, h->v.lambda, lam.data())) return rc;
-  if (int rc = scalars_to_host(h, h->v.dlambda, dlam.data())) return rc;
-  hipLaunchKernelGGL(k_reset_state<double>, dim3((h->Bp + 255) / 256), dim3(256), 0, h->stream, h->v, 1.0, 1.0);
-  HIPCHK(hipGetLastError());
-  if (int rc = scalars_to_dev(h, lam.data(), h->v.lambda)) return rc;
-  if (int rc = scalars_to_dev(h, dlam.data(), h->v.dlambda)) return rc;
+  if (int rc = launch_per_slot(h, k_warm_reset<double>, h->v)) return rc;
   return ilqr_generate_trajectory(h);
 }
 
@@ -667,19 +663,13 @@ int ilqr_warm_start(ilqr_batch* h, const double* x0) {
 // Every per-knot array of the nominal (xs, us, k, K) moves `shift` knots toward t = 0 in place (k_shift_horizon, layout.hpp); the tail rule of
 // include/ilqr_amd.h.  Cost, lambda, status and iteration counts stay.  Enqueued on the handle's stream, nothing waited for.
 static int shift_nominal(ilqr_batch* h, int shift, int tail) {
-  if (int rc = flush_commit(h)) return rc;  // an accepted candidate not yet copied into xs / us belongs to the old horizon
-  h->cands = Cands::none;                   // the candidates are rollouts of the old horizon
-  h->lq_cands_kept = false;
-  if (!h->aos && h->recs == ilqr_batch::REC_VALID) h->recs = ilqr_batch::REC_STALE;  // records of the old nominal: recomputed when asked for
+  if (int rc = nominal_changes(h)) return rc;
   if (shift == 0) return 0;
-  const int nx = h->nx, nu = h->nu, T = h->T;
-  const int lanes = h->aos ? 1 : TW;  // elements per (knot, element) of a segment
+  const NominalArrays n = nominal_arrays(h);
+  const int tails[4] = {SHIFT_TAIL_HOLD, tail, SHIFT_TAIL_ZERO, tail};  // xs[T] is repeated under either tail, k's is zero
   ShiftSet set;
-  set.arr[0] = {h->v.xs, T + 1, nx * lanes, SHIFT_TAIL_HOLD};  // xs[T] repeated under either tail
-  set.arr[1] = {h->v.us, T, nu * lanes, tail};
-  set.arr[2] = {h->v.kff, T, nu * lanes, SHIFT_TAIL_ZERO};
-  set.arr[3] = {h->v.Kfb, T, nu * nx * lanes, tail};
-  set.nseg = h->aos ? h->B : h->ntiles;
+  for (int i = 0; i < 4; i++) set.arr[i] = {n.arr[i].p, n.arr[i].S, n.arr[i].W, tails[i]};
+  set.nseg = n.nseg;
   set.shift = shift;
   const dim3 grid((unsigned)std::min(set.nseg, 65535), 4), block(256);
   with_real(h, [&](auto r) {
@@ -703,45 +693,6 @@ int ilqr_shift_horizon(ilqr_batch* h, int shift, int tail) {
   return shift_nominal(h, shift, tail == ILQR_TAIL_HOLD ? SHIFT_TAIL_HOLD : SHIFT_TAIL_ZERO);
 }
 
-// shift -> x0 -> ilqr_warm_start's rollout and commit -> the warm reset on the device -> n_iters iterations: the state ilqr_warm_start leaves
-// on a handle with max_iter = n_iters, without one host synchronisation (ilqr_warm_start reads lambda back and waits per chunk)
-int ilqr_mpc_step(ilqr_batch* h, const double* x0, const void* x0_device, int shift, int tail, int n_iters) {
-  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
-  if (host_model(h)) return fail(ILQR_ERR_UNSUPPORTED, "ilqr_mpc_step: a host-evaluated model's rollouts run on the host (as for ilqr_warm_start)");
-  REQUIRE((x0 != nullptr) != (x0_device != nullptr), "ilqr_mpc_step: exactly one of x0 (host) and x0_device");
-  if (int rc = check_shift(h, shift, tail)) return rc;
-  REQUIRE(n_iters >= 0, "n_iters %d must be >= 0", n_iters);
-  if (!h->initialised) return fail(ILQR_ERR_STATE, "mpc_step needs a previous solve (assert us.size()>0, ilqr_core.cpp:66)");
-  HIPCHK(hipSetDevice(h->device));
-  if (int rc = shift_nominal(h, shift, tail == ILQR_TAIL_HOLD ? SHIFT_TAIL_HOLD : SHIFT_TAIL_ZERO)) return rc;
-  // x0 into the handle's layout: the host array's one transfer goes to a buffer of its own (the shared staging buffer may be reallocated,
-  // which waits); a device x0 is read where it lies
-  const DevArray X0{h->v.x0, 1, h->nx};
-  const double* src = (const double*)x0_device;
-  if (x0) {
-    double* dst = stored_canonical(h, X0) ? h->v.x0 : h->x0_stage;
-    HIPCHK(hipMemcpyAsync(dst, x0, (size_t)h->B * h->nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    src = dst;
-  }
-  if (int rc = from_canonical(h, src, X0)) return rc;
-  // ilqr_warm_start's rollout, kernel for kernel: u = us[t] + K[t](x - xs[t]) (every alpha 0), written into xs / us
-  AlphaSet al;
-  for (int i = 0; i < NALPHA; i++) al.a[i] = 0.0;
-  if (h->plan.commit != Commit::tiled) {
-    HIPCHK(hipMemsetAsync(h->commit_idx, 0, (size_t)h->Bp * sizeof(int), h->stream));
-    if (int rc = launch_rollout(h, true, true, al, 1, h->v.cost, 0)) return rc;
-  } else {
-    if (int rc = launch_rollout(h, true, true, al, 1, h->v.cost, 0)) return rc;
-    HIPCHK(hipMemsetAsync(h->commit_idx, 0, (size_t)h->Bp * sizeof(int), h->stream));
-    if (int rc = launch_commit(h)) return rc;
-  }
-  HIPCHK(hipMemsetAsync(h->commit_idx, 0xFF, (size_t)h->Bp * sizeof(int), h->stream));
-  hipLaunchKernelGGL(k_warm_reset<double>, dim3((h->Bp + 255) / 256), dim3(256), 0, h->stream, h->v);
-  HIPCHK(hipGetLastError());
-  if (n_iters == 0) return 0;
-  return ilqr_iterate(h, n_iters);
-}
-
 int ilqr_copy_controls_to_device(ilqr_batch* h, int t0, int n_knots, void* u_device) {
   if (!h || !u_device) return fail(ILQR_ERR_INVALID, "null argument");
   REQUIRE(t0 >= 0 && n_knots >= 1 && t0 + n_knots <= h->T, "control window [%d, %d): inside [0, T = %d), at least one knot", t0, t0 + n_knots, h->T);
@@ -751,13 +702,6 @@ int ilqr_copy_controls_to_device(ilqr_batch* h, int t0, int n_knots, void* u_dev
 }
 
 // ---- single trajectories start over (additive under ABI 6; reset.hpp) ---------------
-static int* reset_mask_stage(ilqr_batch* h) { return h->reset_ints; }
-static int* reset_sel(ilqr_batch* h) { return h->reset_ints + h->Bp; }
-static int* reset_flags(ilqr_batch* h) { return h->reset_ints + 2 * (size_t)h->Bp; }
-static int ensure_reset_ints(ilqr_batch* h) {
-  if (h->reset_ints) return 0;
-  return dev_alloc(h, &h->reset_ints, 3 * (size_t)h->Bp);
-}
 static int check_reset_args(const int* mask, const void* mask_device, int rules, const char* who) {
   REQUIRE(!(mask && mask_device), "%s: at most one of mask (host) and mask_device", who);
   REQUIRE((rules & ~(ILQR_RESET_NONFINITE | ILQR_RESET_LAMBDA_MAX)) == 0, "%s: rules %d: bits of ILQR_RESET_NONFINITE | ILQR_RESET_LAMBDA_MAX", who, rules);
@@ -765,7 +709,8 @@ static int check_reset_args(const int* mask, const void* mask_device, int rules,
 }
 // the mask where the kernels read it: a host mask goes to the handle's own buffer on the stream, a device mask is read where it lies
 static int stage_reset_mask(ilqr_batch* h, const int* mask, const void* mask_device, const int** out) {
-  if (int rc = ensure_reset_ints(h)) return rc;
+  if (!h->reset_ints)
+    if (int rc = dev_alloc(h, &h->reset_ints, 3 * (size_t)h->Bp)) return rc;
   *out = (const int*)mask_device;
   if (mask) {
     HIPCHK(hipMemcpyAsync(reset_mask_stage(h), mask, (size_t)h->B * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -776,19 +721,16 @@ static int stage_reset_mask(ilqr_batch* h, const int* mask, const void* mask_dev
 // k_select_reset, then k_reset_nominal for whom it selected.  repeat: the pass after a warm rollout (non-finite costs only; commit_idx says
 // whom the repeated rollout takes).
 static int select_and_reset(ilqr_batch* h, const int* d_mask, int rules, int repeat) {
-  hipLaunchKernelGGL(k_select_reset<double>, dim3((h->Bp + 255) / 256), dim3(256), 0, h->stream, h->v, d_mask, rules, repeat, h->params.lambda_init,
-                     h->params.dlambda_init, reset_sel(h), reset_flags(h), h->commit_idx);
-  HIPCHK(hipGetLastError());
-  const int nx = h->nx, nu = h->nu, T = h->T;
-  const int lanes = h->aos ? 1 : TW;
+  if (int rc = launch_per_slot(h, k_select_reset<double>, h->v, d_mask, rules, repeat, h->params.lambda_init, h->params.dlambda_init, reset_sel(h),
+                               reset_flags(h), h->commit_idx))
+    return rc;
+  const NominalArrays n = nominal_arrays(h);
+  const void* const src[4] = {nullptr, h->reset_us_set ? h->reset_us : nullptr, nullptr, nullptr};  // what a selected element becomes (null: zero)
   ResetSet set;
-  set.arr[0] = {h->v.xs, nullptr, T + 1, nx * lanes};
-  set.arr[1] = {h->v.us, h->reset_us_set ? h->reset_us : nullptr, T, nu * lanes};
-  set.arr[2] = {h->v.kff, nullptr, T, nu * lanes};
-  set.arr[3] = {h->v.Kfb, nullptr, T, nu * nx * lanes};
+  for (int i = 0; i < 4; i++) set.arr[i] = {n.arr[i].p, src[i], n.arr[i].S, n.arr[i].W};
   set.sel = reset_sel(h);
-  set.nseg = h->aos ? h->B : h->ntiles;  // (sel holds Bp = 16 ntiles >= B slots)
-  set.lanes = lanes;
+  set.nseg = n.nseg;  // (sel holds Bp = 16 ntiles >= B slots)
+  set.lanes = n.lanes;
   const dim3 grid((unsigned)std::min(set.nseg, 65535), 4), block(256);
   with_real(h, [&](auto r) {
     hipLaunchKernelGGL(k_reset_nominal<decltype(r)>, grid, block, 0, h->stream, set);
@@ -831,70 +773,75 @@ int ilqr_reset_trajectories(ilqr_batch* h, const int* mask, const void* mask_dev
   if (int rc = check_reset_args(mask, mask_device, rules, "ilqr_reset_trajectories")) return rc;
   if (!h->initialised) return fail(ILQR_ERR_STATE, "reset_trajectories before ilqr_init_traj/ilqr_set_trajectory: there is no trajectory to reset");
   HIPCHK(hipSetDevice(h->device));
-  if (int rc = flush_commit(h)) return rc;  // an accepted candidate not yet copied belongs to the trajectory as it was (as shift_nominal)
-  h->cands = Cands::none;
-  h->lq_cands_kept = false;
-  if (!h->aos && h->recs == ilqr_batch::REC_VALID) h->recs = ilqr_batch::REC_STALE;
+  if (int rc = nominal_changes(h)) return rc;
   const int* d_mask = nullptr;
   if (int rc = stage_reset_mask(h, mask, mask_device, &d_mask)) return rc;
   return select_and_reset(h, d_mask, rules, 0);
 }
 
-// ilqr_mpc_step's warm rollout and commit, kernel for kernel.  repeat: commit_idx already says who is rolled out again (k_select_reset);
-// a tiled rollout scores whole tiles, so its costs go through a scratch row (cost_c's first plane: the candidates are nobody's during a step)
-static int warm_rollout_commit(ilqr_batch* h, bool repeat) {
-  AlphaSet al;
-  for (int i = 0; i < NALPHA; i++) al.a[i] = 0.0;
-  if (h->plan.commit != Commit::tiled) {
-    if (!repeat) HIPCHK(hipMemsetAsync(h->commit_idx, 0, (size_t)h->Bp * sizeof(int), h->stream));
-    if (int rc = launch_rollout(h, true, true, al, 1, h->v.cost, 0)) return rc;
-  } else {
-    if (int rc = launch_rollout(h, true, true, al, 1, repeat ? h->v.cost_c : h->v.cost, 0)) return rc;
-    if (!repeat) HIPCHK(hipMemsetAsync(h->commit_idx, 0, (size_t)h->Bp * sizeof(int), h->stream));
-    if (int rc = launch_commit(h)) return rc;
-    if (repeat) {
-      hipLaunchKernelGGL(k_take_reset_cost, dim3((h->B + 255) / 256), dim3(256), 0, h->stream, h->v.cost_c, reset_sel(h), h->v.cost, h->B);
-      HIPCHK(hipGetLastError());
-    }
-  }
-  HIPCHK(hipMemsetAsync(h->commit_idx, 0xFF, (size_t)h->Bp * sizeof(int), h->stream));
-  return 0;
-}
-
-// ilqr_mpc_step with a reset of the selected trajectories between the shift and the warm rollout, and under ILQR_RESET_NONFINITE one more
-// after it for those whose warm rollout did not stay finite
-int ilqr_mpc_step_reset(ilqr_batch* h, const double* x0, const void* x0_device, int shift, int tail, int n_iters, const int* mask,
-                        const void* mask_device, int rules) {
-  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
-  if (host_model(h)) return fail(ILQR_ERR_UNSUPPORTED, "ilqr_mpc_step_reset: a host-evaluated model's rollouts run on the host (as for ilqr_warm_start)");
-  REQUIRE((x0 != nullptr) != (x0_device != nullptr), "ilqr_mpc_step_reset: exactly one of x0 (host) and x0_device");
-  if (int rc = check_shift(h, shift, tail)) return rc;
-  REQUIRE(n_iters >= 0, "n_iters %d must be >= 0", n_iters);
-  if (int rc = check_reset_args(mask, mask_device, rules, "ilqr_mpc_step_reset")) return rc;
-  if (!h->initialised) return fail(ILQR_ERR_STATE, "mpc_step_reset needs a previous solve (assert us.size()>0, ilqr_core.cpp:66)");
-  HIPCHK(hipSetDevice(h->device));
-  if (int rc = shift_nominal(h, shift, tail == ILQR_TAIL_HOLD ? SHIFT_TAIL_HOLD : SHIFT_TAIL_ZERO)) return rc;
-  // after the shift: the reset controls are a fresh horizon's, not shifted.  The cost rule waits for the new cost.
-  const int* d_mask = nullptr;
-  if (int rc = stage_reset_mask(h, mask, mask_device, &d_mask)) return rc;
-  if (int rc = select_and_reset(h, d_mask, rules & ILQR_RESET_LAMBDA_MAX, 0)) return rc;
-  const DevArray X0{h->v.x0, 1, h->nx};  // x0 as in ilqr_mpc_step
+// ---- the MPC step (ABI 6), with or without a reset of single trajectories ------------------------------
+// x0 into the handle's layout: the host array's one transfer goes to a buffer of its own (the shared staging buffer may be reallocated,
+// which waits); a device x0 is read where it lies
+static int stage_x0(ilqr_batch* h, const double* x0, const void* x0_device) {
+  const DevArray X0{h->v.x0, 1, h->nx};
   const double* src = (const double*)x0_device;
   if (x0) {
     double* dst = stored_canonical(h, X0) ? h->v.x0 : h->x0_stage;
     HIPCHK(hipMemcpyAsync(dst, x0, (size_t)h->B * h->nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
     src = dst;
   }
-  if (int rc = from_canonical(h, src, X0)) return rc;
+  return from_canonical(h, src, X0);
+}
+// every refusal the two step calls share, in the order tests/test_mpc_abi.py pins; each goes on with its own checks
+static int check_step_args(ilqr_batch* h, const double* x0, const void* x0_device, int shift, int tail, int n_iters, const char* who) {
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  if (host_model(h)) return fail(ILQR_ERR_UNSUPPORTED, "%s: a host-evaluated model's rollouts run on the host (as for ilqr_warm_start)", who);
+  REQUIRE((x0 != nullptr) != (x0_device != nullptr), "%s: exactly one of x0 (host) and x0_device", who);
+  if (int rc = check_shift(h, shift, tail)) return rc;
+  REQUIRE(n_iters >= 0, "n_iters %d must be >= 0", n_iters);
+  return 0;
+}
+// The step: shift -> [reset of the selected] -> x0 -> ilqr_warm_start's rollout and commit -> [under ILQR_RESET_NONFINITE: reset and roll out
+// again those whose warm rollout did not stay finite] -> the warm reset -> n_iters iterations.  Everything is enqueued, nothing waited for.
+// reset: null for the plain step, which then touches neither reset_ints nor reset_flags_valid and launches no reset kernel.
+struct ResetRequest {
+  const int* mask;
+  const void* mask_device;
+  int rules;
+};
+static int warm_restart(ilqr_batch* h, const double* x0, const void* x0_device, int shift, int tail, int n_iters, const ResetRequest* reset) {
+  HIPCHK(hipSetDevice(h->device));
+  if (int rc = shift_nominal(h, shift, tail == ILQR_TAIL_HOLD ? SHIFT_TAIL_HOLD : SHIFT_TAIL_ZERO)) return rc;
+  if (reset) {  // after the shift: the reset controls are a fresh horizon's, not shifted.  The cost rule waits for the new cost.
+    const int* d_mask = nullptr;
+    if (int rc = stage_reset_mask(h, reset->mask, reset->mask_device, &d_mask)) return rc;
+    if (int rc = select_and_reset(h, d_mask, reset->rules & ILQR_RESET_LAMBDA_MAX, 0)) return rc;
+  }
+  if (int rc = stage_x0(h, x0, x0_device)) return rc;
   if (int rc = warm_rollout_commit(h, false)) return rc;
-  if (rules & ILQR_RESET_NONFINITE) {
+  if (reset && (reset->rules & ILQR_RESET_NONFINITE)) {
     if (int rc = select_and_reset(h, nullptr, ILQR_RESET_NONFINITE, 1)) return rc;
     if (int rc = warm_rollout_commit(h, true)) return rc;
   }
-  hipLaunchKernelGGL(k_warm_reset<double>, dim3((h->Bp + 255) / 256), dim3(256), 0, h->stream, h->v);
-  HIPCHK(hipGetLastError());
-  if (n_iters == 0) return 0;
-  return ilqr_iterate(h, n_iters);
+  if (int rc = launch_per_slot(h, k_warm_reset<double>, h->v)) return rc;
+  return n_iters ? ilqr_iterate(h, n_iters) : 0;
+}
+
+// the state ilqr_warm_start leaves on a handle with max_iter = n_iters, without one host synchronisation (ilqr_warm_start waits for its
+// x0 and per chunk of iterations)
+int ilqr_mpc_step(ilqr_batch* h, const double* x0, const void* x0_device, int shift, int tail, int n_iters) {
+  if (int rc = check_step_args(h, x0, x0_device, shift, tail, n_iters, "ilqr_mpc_step")) return rc;
+  if (!h->initialised) return fail(ILQR_ERR_STATE, "mpc_step needs a previous solve (assert us.size()>0, ilqr_core.cpp:66)");
+  return warm_restart(h, x0, x0_device, shift, tail, n_iters, nullptr);
+}
+
+int ilqr_mpc_step_reset(ilqr_batch* h, const double* x0, const void* x0_device, int shift, int tail, int n_iters, const int* mask,
+                        const void* mask_device, int rules) {
+  if (int rc = check_step_args(h, x0, x0_device, shift, tail, n_iters, "ilqr_mpc_step_reset")) return rc;
+  if (int rc = check_reset_args(mask, mask_device, rules, "ilqr_mpc_step_reset")) return rc;
+  if (!h->initialised) return fail(ILQR_ERR_STATE, "mpc_step_reset needs a previous solve (assert us.size()>0, ilqr_core.cpp:66)");
+  const ResetRequest reset{mask, mask_device, rules};
+  return warm_restart(h, x0, x0_device, shift, tail, n_iters, &reset);
 }
 
 int ilqr_copy_reset_flags_to_device(ilqr_batch* h, void* flags_device) {
@@ -927,15 +874,17 @@ static int prepare_value(ilqr_batch* h, int t0, int n_knots, const void* Vx, con
   HIPCHK(hipSetDevice(h->device));
   return materialise_records(h);
 }
+// a launch that was itself refused says which kernel (run_value, run_evaluate)
+static int name_refused_kernel(int rc, const char* who, const char* kernel) {
+  if (rc != ILQR_ERR_HIP) return rc;
+  char keep[sizeof(g_err)];
+  memcpy(keep, g_err, sizeof(keep));
+  return fail(rc, "%s: %s: %.400s", who, kernel, keep);
+}
 static int run_value(ilqr_batch* h, int t0, int n_knots, double* Vx, double* Vxx, const char* who) {
   const char* kernel = "";
   const int rc = launch_value(h, t0, n_knots, Vx, Vxx, &kernel);
-  if (rc == ILQR_ERR_HIP) {  // (the launch itself was refused: say which kernel)
-    char keep[sizeof(g_err)];
-    memcpy(keep, g_err, sizeof(keep));
-    return fail(rc, "%s: %s: %.400s", who, kernel, keep);
-  }
-  return rc;
+  return name_refused_kernel(rc, who, kernel);
 }
 
 int ilqr_copy_value_to_device(ilqr_batch* h, int t0, int n_knots, void* Vx_device, void* Vxx_device) {
@@ -974,13 +923,7 @@ static int prepare_evaluate(ilqr_batch* h, int t0, int n_knots, int n_samples, i
   return flush_commit(h);
 }
 static int run_evaluate(ilqr_batch* h, const EvalArgs& e, const char* who) {
-  const int rc = launch_evaluate(h, e);
-  if (rc == ILQR_ERR_HIP) {  // (the launch itself was refused: say which kernel)
-    char keep[sizeof(g_err)];
-    memcpy(keep, g_err, sizeof(keep));
-    return fail(rc, "%s: %s: %.400s", who, evaluate_kernel_name(h), keep);
-  }
-  return rc;
+  return name_refused_kernel(launch_evaluate(h, e), who, evaluate_kernel_name(h));
 }
 static int eval_clamp(const ilqr_batch* h, int flags) { return ((flags & ILQR_EVAL_CLAMP) || (h->sp.fixes & 1)) ? 1 : 0; }
 
@@ -1067,35 +1010,33 @@ int ilqr_clear_trajectory_params(ilqr_batch* h) {
 }
 
 // ---- stages --------------------------------------------------------------------------------
-int ilqr_compute_derivatives(ilqr_batch* h) {
+// what every stage call checks first; device_model: the stage runs the model on the device, which a host-evaluated handle has not got
+static int begin_stage(ilqr_batch* h, bool device_model) {
   if (!h) return fail(ILQR_ERR_INVALID, "null handle");
-  if (host_model(h)) return no_device_model();
+  if (device_model && host_model(h)) return no_device_model();
   HIPCHK(hipSetDevice(h->device));
   if (!h->initialised) return fail(ILQR_ERR_STATE, "stage call before ilqr_init_traj/ilqr_set_trajectory (the reference asserts, ilqr_core.cpp:80-82)");
+  return 0;
+}
+int ilqr_compute_derivatives(ilqr_batch* h) {
+  if (int rc = begin_stage(h, true)) return rc;
   return launch_derivatives(h, 1);
 }
 
 int ilqr_backward_pass(ilqr_batch* h, int* diverge_out) {
-  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
-  HIPCHK(hipSetDevice(h->device));
-  if (!h->initialised) return fail(ILQR_ERR_STATE, "stage call before ilqr_init_traj/ilqr_set_trajectory (the reference asserts, ilqr_core.cpp:80-82)");
+  if (int rc = begin_stage(h, false)) return rc;
   if (int rc = launch_backward(h, 0)) return rc;
   if (diverge_out) return scalars_to_host(h, h->v.diverge, diverge_out);
   return 0;
 }
 
 int ilqr_backward_step(ilqr_batch* h) {
-  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
-  HIPCHK(hipSetDevice(h->device));
-  if (!h->initialised) return fail(ILQR_ERR_STATE, "stage call before ilqr_init_traj/ilqr_set_trajectory (the reference asserts, ilqr_core.cpp:80-82)");
+  if (int rc = begin_stage(h, false)) return rc;
   return launch_backward(h, 1);
 }
 
 int ilqr_rollout_candidates(ilqr_batch* h, double* cost_out) {
-  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
-  if (host_model(h)) return no_device_model();
-  HIPCHK(hipSetDevice(h->device));
-  if (!h->initialised) return fail(ILQR_ERR_STATE, "stage call before ilqr_init_traj/ilqr_set_trajectory (the reference asserts, ilqr_core.cpp:80-82)");
+  if (int rc = begin_stage(h, true)) return rc;
   if (int rc = do_rollout_candidates(h, 0)) return rc;
   if (cost_out) {
     std::vector<double> tmp((size_t)NALPHA * h->Bp);
@@ -1108,10 +1049,7 @@ int ilqr_rollout_candidates(ilqr_batch* h, double* cost_out) {
 }
 
 int ilqr_line_search(ilqr_batch* h) {
-  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
-  if (host_model(h)) return no_device_model();
-  HIPCHK(hipSetDevice(h->device));
-  if (!h->initialised) return fail(ILQR_ERR_STATE, "stage call before ilqr_init_traj/ilqr_set_trajectory (the reference asserts, ilqr_core.cpp:80-82)");
+  if (int rc = begin_stage(h, true)) return rc;
   if (int rc = flush_commit(h)) return rc;
   if (int rc = do_rollout_candidates(h, 1)) return rc;
   if (int rc = launch_accept(h)) return rc;
@@ -1121,8 +1059,7 @@ int ilqr_line_search(ilqr_batch* h) {
 int ilqr_accept_candidates(ilqr_batch* h, const double* cost_c, int* accepted) {
   if (!h || !cost_c || !accepted) return fail(ILQR_ERR_INVALID, "null argument");
   if (!h->v.cost_c) return fail(ILQR_ERR_UNSUPPORTED, "this handle has no candidate-cost buffer");
-  HIPCHK(hipSetDevice(h->device));
-  if (!h->initialised) return fail(ILQR_ERR_STATE, "stage call before ilqr_init_traj/ilqr_set_trajectory (the reference asserts, ilqr_core.cpp:80-82)");
+  if (int rc = begin_stage(h, false)) return rc;
   if (int rc = flush_commit(h)) return rc;
   std::vector<double> tmp((size_t)NALPHA * h->Bp, 0.0);
   for (int b = 0; b < h->B; b++)
@@ -1143,28 +1080,8 @@ int ilqr_reset_state(ilqr_batch* h, int warm) {
   if (!h) return fail(ILQR_ERR_INVALID, "null handle");
   HIPCHK(hipSetDevice(h->device));
   if (int rc = flush_commit(h)) return rc;
-  std::vector<double> lam, dlam;
-  if (warm) {
-    lam.resize(h->B);
-    dlam.resize(h->B);
-    if (int rc = scalars_to_host(h, h->v.lambda, lam.data())) return rc;
-    if (int rc = scalars_to_host(h, h->v.dlambda, dlam.data())) return rc;
-  } else {
-    const size_t T = h->T, T1 = h->T + 1;
-    if (h->v.D) HIPCHK(hipMemsetAsync(h->v.D, 0, dev_elems(h, T1, rec_of(h)) * elem_size(h), h->stream));
-    h->recs = ilqr_batch::REC_ZERO;
-    HIPCHK(hipMemsetAsync(h->v.kff, 0, dev_elems(h, T, h->nu) * elem_size(h), h->stream));
-    HIPCHK(hipMemsetAsync(h->v.Kfb, 0, dev_elems(h, T, h->nu * h->nx) * elem_size(h), h->stream));
-    if (int rc = forget_pending(h)) return rc;
-  }
-  hipLaunchKernelGGL(k_reset_state<double>, dim3((h->Bp + 255) / 256), dim3(256), 0, h->stream, h->v, h->params.lambda_init,
-                     h->params.dlambda_init);
-  HIPCHK(hipGetLastError());
-  if (warm) {
-    if (int rc = scalars_to_dev(h, lam.data(), h->v.lambda)) return rc;
-    if (int rc = scalars_to_dev(h, dlam.data(), h->v.dlambda)) return rc;
-  }
-  return 0;
+  // warm: a new outer loop on the stored solution -- lambda, dlambda and the gains persist, on the device (k_warm_reset)
+  return warm ? launch_per_slot(h, k_warm_reset<double>, h->v) : fresh_trajectory(h);
 }
 
 // ---- state exchange --------------------------------------------------------------------------

@@ -129,6 +129,9 @@ struct ilqr_batch {
   hipEvent_t chain_event = nullptr;
 };
 
+static int* reset_mask_stage(ilqr_batch* h) { return h->reset_ints; }  // the three rows of reset_ints
+static int* reset_sel(ilqr_batch* h) { return h->reset_ints + h->Bp; }
+static int* reset_flags(ilqr_batch* h) { return h->reset_ints + 2 * (size_t)h->Bp; }
 static int rec_of(const ilqr_batch* h) { return rec_size(h->nx, h->nu); }
 static size_t elem_size(const ilqr_batch* h) { return h->dtype == ILQR_DTYPE_F32 ? sizeof(float) : sizeof(double); }
 // the float view of an fp32 handle: same addresses as v, typed

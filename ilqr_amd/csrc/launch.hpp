@@ -6,6 +6,14 @@
 // ------------------------------------------------------------------------------------------
 // kernel launchers (dispatch on the device model)
 // ------------------------------------------------------------------------------------------
+// one thread per slot of the padded batch (k_reset_state, k_warm_reset, k_select_reset, k_accept: scalars only)
+template <class... P, class... A>
+static int launch_per_slot(ilqr_batch* h, void (*kernel)(P...), const A&... a) {
+  hipLaunchKernelGGL(kernel, dim3((h->Bp + 255) / 256), dim3(256), 0, h->stream, static_cast<P>(a)...);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // cand = true: controls + checkpoint states go to the candidate buffers; false: straight into xs/us (init)
 template <class V, class M>
 static int launch_rollout_t(ilqr_batch* h, const V& v, const M& m, bool gains, bool cand, const AlphaSet& al, int n_alpha,
@@ -174,6 +182,37 @@ static int forget_pending(ilqr_batch* h) {
   HIPCHK(hipMemsetAsync(h->commit_idx, 0xFF, (size_t)h->Bp * sizeof(int), h->stream));  // all -1
   return 0;
 }
+// A fresh trajectory, all of init_traj but x0, u0 and the rollout (ilqr_core.cpp:23-48): zero derivative records and gains, nothing
+// pending, lambda / dlambda (the reference's file statics) as for a fresh process
+static int fresh_trajectory(ilqr_batch* h) {
+  const size_t T = h->T, T1 = h->T + 1;
+  if (h->v.D) HIPCHK(hipMemsetAsync(h->v.D, 0, dev_elems(h, T1, rec_of(h)) * elem_size(h), h->stream));
+  h->recs = ilqr_batch::REC_ZERO;
+  HIPCHK(hipMemsetAsync(h->v.kff, 0, dev_elems(h, T, h->nu) * elem_size(h), h->stream));
+  HIPCHK(hipMemsetAsync(h->v.Kfb, 0, dev_elems(h, T, h->nu * h->nx) * elem_size(h), h->stream));
+  if (int rc = forget_pending(h)) return rc;
+  return launch_per_slot(h, k_reset_state<double>, h->v, h->params.lambda_init, h->params.dlambda_init);
+}
+// The nominal is about to change under the handle (a shift, a reset of single trajectories): an accepted candidate not yet copied into
+// xs / us belongs to the old one and is copied now; the candidates are rollouts of the old one; its records are recomputed when asked for
+static int nominal_changes(ilqr_batch* h) {
+  if (int rc = flush_commit(h)) return rc;
+  h->cands = Cands::none;
+  h->lq_cands_kept = false;
+  if (!h->aos && h->recs == ilqr_batch::REC_VALID) h->recs = ilqr_batch::REC_STALE;
+  return 0;
+}
+// The nominal's four arrays as k_shift_horizon and k_reset_nominal take them (layout.hpp): nseg segments -- tiles, or trajectories of the
+// trajectory-contiguous layout -- of S knots of W contiguous elements, `lanes` trajectories interleaved in a segment
+struct NominalArrays {
+  struct { void* p; int S, W; } arr[4];  // xs, us, k, K
+  int nseg, lanes;
+};
+static NominalArrays nominal_arrays(const ilqr_batch* h) {
+  const int nx = h->nx, nu = h->nu, T = h->T, lanes = h->aos ? 1 : TW;
+  return {{{h->v.xs, T + 1, nx * lanes}, {h->v.us, T, nu * lanes}, {h->v.kff, T, nu * lanes}, {h->v.Kfb, T, nu * nx * lanes}},
+          h->aos ? h->B : h->ntiles, lanes};
+}
 
 static int launch_derivatives(ilqr_batch* h, int force) {
   const Derivatives route = h->plan.derivatives;
@@ -340,8 +379,7 @@ static int launch_sweep_backward(ilqr_batch* h, int mode, int force) {
 static int launch_accept(ilqr_batch* h) {
   std::pair<hipEvent_t, hipEvent_t> ev;
   if (int rc = timer_begin(h, ILQR_STAGE_ACCEPT, &ev)) return rc;
-  hipLaunchKernelGGL(k_accept<double>, dim3((h->Bp + 255) / 256), dim3(256), 0, h->stream, h->v, h->sp, h->commit_idx);  // (scalars only)
-  HIPCHK(hipGetLastError());
+  if (int rc = launch_per_slot(h, k_accept<double>, h->v, h->sp, h->commit_idx)) return rc;
   h->commit_pending = true;
   return timer_end(h, ILQR_STAGE_ACCEPT, ev);
 }

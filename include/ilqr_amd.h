@@ -266,7 +266,7 @@ int ilqr_shift_horizon(ilqr_batch* h, int shift, int tail);
  * into xs / us, then a new outer loop (status, iteration counts and flgChange restart; lambda and dlambda persist), then n_iters iterations
  * (ilqr_iterate; n_iters = 0 stops after the warm start's rollout).  It leaves bit for bit the state that shifting on the host,
  * ilqr_set_trajectory + ilqr_set_gains and ilqr_warm_start(x0) on a handle with params.max_iter = n_iters leave (status and iteration
- * counts too when this handle's own max_iter is n_iters), with no host synchronisation: no lambda round trip, no wait per chunk, no
+ * counts too when this handle's own max_iter is n_iters), with no host synchronisation: no wait for x0, no wait per chunk, no
  * compaction of finished trajectories.  Exactly one of x0 (host, [B][nx] double) and x0_device (device memory of this handle's device,
  * [B][nx] double) is non-NULL.  A host x0 is the call's one host-to-device transfer: from page-locked memory (ilqr_host_register) it is
  * asynchronous -- the array must then stay unchanged until the stream has passed the step -- from pageable memory the runtime may wait
