@@ -923,7 +923,9 @@ static int prepare_evaluate(ilqr_batch* h, int t0, int n_knots, int n_samples, i
   return flush_commit(h);
 }
 static int run_evaluate(ilqr_batch* h, const EvalArgs& e, const char* who) {
-  return name_refused_kernel(launch_evaluate(h, e), who, evaluate_kernel_name(h));
+  const char* kernel = "";
+  const int rc = launch_evaluate(h, e, &kernel);
+  return name_refused_kernel(rc, who, kernel);
 }
 static int eval_clamp(const ilqr_batch* h, int flags) { return ((flags & ILQR_EVAL_CLAMP) || (h->sp.fixes & 1)) ? 1 : 0; }
 
@@ -1208,13 +1210,11 @@ int ilqr_get_candidate(ilqr_batch* h, int a, double* xs, double* us) {
   const dim3 grid(grid_for((size_t)h->B * (h->T + 1), 256)), block(256);
   if (int rc = with_model(h, [&](auto& v, auto& m, auto&) {
         using MM = std::decay_t<decltype(m)>;
-        if constexpr (MM::NX == 4 && MM::NU == 1)
-          if (h->cands == Cands::grouped) {
-            hipLaunchKernelGGL((k_unpack_cand<MM, true>), grid, block, 0, h->stream, v, m, a, dxs, dus);
-            return 0;
-          }
-        hipLaunchKernelGGL((k_unpack_cand<MM>), grid, block, 0, h->stream, v, m, a, dxs, dus);
-        return 0;
+        constexpr bool kHexModel = MM::NX == 4 && MM::NU == 1;  // k_solve_hex's, the one kernel that groups its candidates
+        return with_bool(h->cands == Cands::grouped, [&](auto grouped) {
+          hipLaunchKernelGGL((k_unpack_cand<MM, kHexModel && decltype(grouped)::value>), grid, block, 0, h->stream, v, m, a, dxs, dus);
+          return 0;
+        });
       }))
     return rc;
   HIPCHK(hipGetLastError());

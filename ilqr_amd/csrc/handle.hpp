@@ -151,15 +151,26 @@ static int with_real(ilqr_batch* h, F&& f) {
   if (h->dtype == ILQR_DTYPE_F32) return f(float());
   return f(double());
 }
-// f(view) with the handle's view typed by its storage: h->v (double) or h->vf (float)
+// the handle's view typed by a storage type, h->v (double) or h->vf (float), and f(view) with the handle's own
+template <class R>
+static const BatchViewT<R>& view_of(const ilqr_batch* h) {
+  if constexpr (std::is_same<R, float>::value) return h->vf; else return h->v;
+}
 template <class F>
 static int with_view(ilqr_batch* h, F&& f) {
-  return with_real(h, [&](auto r) {
-    if constexpr (std::is_same_v<decltype(r), float>)
-      return f(h->vf);
-    else
-      return f(h->v);
-  });
+  return with_real(h, [&](auto r) { return f(view_of<decltype(r)>(h)); });
+}
+// f(std::bool_constant<b>()): a launch-time bool as a template argument
+template <class F>
+static int with_bool(bool b, F&& f) {
+  return b ? f(std::true_type()) : f(std::false_type());
+}
+// f(std::integral_constant<int, I>()) for the I of Is... that i equals: a launch-time int as a template argument
+template <int... Is, class F>
+static int with_int(int i, F&& f) {
+  int rc = 0;
+  const bool found = ((i == Is && ((rc = f(std::integral_constant<int, Is>())), true)) || ...);
+  return found ? rc : fail(ILQR_ERR_STATE, "no kernel is built for the value %d of a launch-time switch", i);
 }
 // f(view, model, model the finite differences are taken in) for the handle's device model and arithmetic
 template <class F>
@@ -396,20 +407,16 @@ static int materialise_records(ilqr_batch* h) {
     if (h->recs == ilqr_batch::REC_STALE) return launch_derivatives(h, 1);
     return 0;
   }
-  if (h->lq_fused_stale) {  // the fused LQ route never wrote D: whole exact records of the current nominal, now
-    h->lq_fused_stale = false;
-    h->records_partial = false;
-    const int nchunk = (h->T + 1 + kAnalyticChunk - 1) / kAnalyticChunk;
-    with_view(h, [&](auto& v) {
-      hipLaunchKernelGGL((k_analytic_lq<std::remove_pointer_t<decltype(v.D)>>), dim3(h->B * nchunk), dim3(64), 0, h->stream, v, h->lq, 1, 0, h->const_rec, kAnalyticChunk);
-      return 0;
-    });
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  if (!h->records_partial) return 0;  // (never on an fp32 handle: its sweep writes whole records)
+  // the fused LQ route never wrote D: whole exact records of the current nominal, now (what = 0).  Else a partial sweep's records lack
+  // the constant matrices (what = 2; never on an fp32 handle: its sweep writes whole records)
+  const bool whole = h->lq_fused_stale;
+  if (!whole && !h->records_partial) return 0;
+  if (whole) h->lq_fused_stale = h->records_partial = false;
   const int nchunk = (h->T + 1 + kAnalyticChunk - 1) / kAnalyticChunk;
-  hipLaunchKernelGGL(k_analytic_lq<double>, dim3(h->B * nchunk), dim3(64), 0, h->stream, h->v, h->lq, 1, 2, h->const_rec, kAnalyticChunk);
+  with_view(h, [&](auto& v) {
+    hipLaunchKernelGGL((k_analytic_lq<std::remove_pointer_t<decltype(v.D)>>), dim3(h->B * nchunk), dim3(64), 0, h->stream, v, h->lq, 1, whole ? 0 : 2, h->const_rec, kAnalyticChunk);
+    return 0;
+  });
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -1,10 +1,13 @@
-// launch.hpp -- kernel launchers of the C ABI: dispatch on the handle's device model and arithmetic, and on its route plan (which of
-// several equivalent kernels it runs: route.hpp).  Included once, by capi.hip.
+// launch.hpp -- kernel launchers of the C ABI.  Every kernel template is named in one launch expression; what picks its instantiation
+// at launch -- the handle's device model and arithmetic, its route plan (which of several equivalent kernels it runs: route.hpp,
+// DESIGN.md 3.2), its sizes -- reaches that expression as a type, through the with_* dispatchers here and in handle.hpp.  Where only
+// some combinations of a kernel's switches are built, the `if constexpr` beside the launch is the list of them: a generic lambda
+// instantiates whatever it is handed, so a combination that is not excluded there is compiled.  Included once, by capi.hip.
 #pragma once
 #include "handle.hpp"
 
 // ------------------------------------------------------------------------------------------
-// kernel launchers (dispatch on the device model)
+// kernel launchers
 // ------------------------------------------------------------------------------------------
 // one thread per slot of the padded batch (k_reset_state, k_warm_reset, k_select_reset, k_accept: scalars only)
 template <class... P, class... A>
@@ -14,27 +17,21 @@ static int launch_per_slot(ilqr_batch* h, void (*kernel)(P...), const A&... a) {
   return 0;
 }
 
-// cand = true: controls + checkpoint states go to the candidate buffers; false: straight into xs/us (init)
+// cand = true: controls + checkpoint states go to the candidate buffers; false: straight into xs/us (init).  The candidate rollouts alone
+// have deep-prefetch and accepting instantiations: the init rollout's two switches are pinned in the template arguments themselves
 template <class V, class M>
 static int launch_rollout_t(ilqr_batch* h, const V& v, const M& m, bool gains, bool cand, const AlphaSet& al, int n_alpha,
                             double* cost_out, int mode, bool with_accept) {
+  if (gains != cand) return fail(ILQR_ERR_INVALID, "unsupported rollout variant");
   const int aw = (n_alpha + 3) / 4;  // wavefronts per tile: 4 alphas each
-  dim3 grid(h->ntiles), block(64 * aw);
-  const bool deep = h->ntiles <= h->num_cus;  // one block per CU: deep prefetch (see k_rollout)
-  if (gains && cand && with_accept && deep)
-    hipLaunchKernelGGL((k_rollout<M, true, true, kDeepPrefetch<M>, true>), grid, block, 0, h->stream, v, m, al, n_alpha, cost_out, mode, h->sp, h->commit_idx);
-  else if (gains && cand && with_accept)
-    hipLaunchKernelGGL((k_rollout<M, true, true, 4, true>), grid, block, 0, h->stream, v, m, al, n_alpha, cost_out, mode, h->sp, h->commit_idx);
-  else if (gains && cand && deep)
-    hipLaunchKernelGGL((k_rollout<M, true, true, kDeepPrefetch<M>>), grid, block, 0, h->stream, v, m, al, n_alpha, cost_out, mode, h->sp, nullptr);
-  else if (gains && cand)
-    hipLaunchKernelGGL((k_rollout<M, true, true, 4>), grid, block, 0, h->stream, v, m, al, n_alpha, cost_out, mode, h->sp, nullptr);
-  else if (!gains && !cand)
-    hipLaunchKernelGGL((k_rollout<M, false, false>), grid, block, 0, h->stream, v, m, al, n_alpha, cost_out, mode, h->sp, nullptr);
-  else
-    return fail(ILQR_ERR_INVALID, "unsupported rollout variant");
-  HIPCHK(hipGetLastError());
-  return 0;
+  const int depth = h->ntiles <= h->num_cus ? kDeepPrefetch<M> : 4;  // one block per CU: deep prefetch (see k_rollout)
+  return with_bool(gains, [&](auto g) { return with_bool(with_accept, [&](auto acc) { return with_int<kDeepPrefetch<M>, 4>(depth, [&](auto pd) {
+    constexpr bool G = decltype(g)::value, ACCEPT = G && decltype(acc)::value;
+    hipLaunchKernelGGL((k_rollout<M, G, G, G ? decltype(pd)::value : 4, ACCEPT>), dim3(h->ntiles), dim3(64 * aw), 0, h->stream, v, m, al, n_alpha,
+                       cost_out, mode, h->sp, ACCEPT ? h->commit_idx : nullptr);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }); }); });
 }
 // f(model) for the handle's generic device twin (fp32 handle: the double twin its finite differences are taken in)
 template <class F>
@@ -57,15 +54,7 @@ static int with_rollout_model(ilqr_batch* h, F&& f) {
 #endif
   return fail(ILQR_ERR_UNSUPPORTED, "model %d has no fp32 generic device kernels", h->model);
 }
-template <class R>
-static const BatchViewT<R>& view_of(const ilqr_batch* h) {
-  if constexpr (std::is_same<R, float>::value) return h->vf; else return h->v;
-}
-// generic path (generic.hpp): what = RG_INIT / RG_SEARCH / RG_COMMIT.  The LQ model rolls out on the
-// matrix cores (k_rollout_lq, one wavefront per trajectory); ILQR_ROUTE_LQ_THREAD_ROLLOUT selects the
-// generic thread-per-rollout kernel (same results bit for bit; kept as the cross-check and as the
-// template for device models without matrix structure).
-// the model with the handle's per-trajectory rows behind it: what the PT instantiations of k_rollout_g / k_derivatives_g take
+// the model with the handle's per-trajectory rows behind it: what the PT instantiations of k_rollout_g / k_derivatives_g / k_evaluate_g take
 template <class M>
 static PerTrajectory<M> per_trajectory(const ilqr_batch* h, const M& m) {
   PerTrajectory<M> pm;
@@ -73,49 +62,41 @@ static PerTrajectory<M> per_trajectory(const ilqr_batch* h, const M& m) {
   pm.traj_params = h->traj_params;
   return pm;
 }
-template <class M>
-static int launch_rollout_g(ilqr_batch* h, const M& m, int what, const AlphaSet& al, double* cost_out, int mode, int write_cost, bool with_accept = false) {
+// f(model argument, PT) for a kernel with a PT instantiation: (per_trajectory(h, m), true) while the handle holds per-trajectory parameters
+// -- every lane's model copy is then set from its trajectory's row --, else (m, false)
+template <class M, class F>
+static int with_trajectory_params(const ilqr_batch* h, const M& m, F&& f) {
+  if constexpr (has_trajectory_params<M>::value)
+    if (h->plan.traj_params) return f(per_trajectory(h, m), std::true_type());
+  return f(m, std::false_type());
+}
+// generic path (generic.hpp): WHAT = RG_INIT / RG_SEARCH / RG_COMMIT.  The LQ model rolls out on the
+// matrix cores (k_rollout_lq, one wavefront per trajectory); ILQR_ROUTE_LQ_THREAD_ROLLOUT selects the
+// generic thread-per-rollout kernel (same results bit for bit; kept as the cross-check and as the
+// template for device models without matrix structure).
+template <int WHAT, class M>
+static int launch_rollout_g(ilqr_batch* h, const M& m, const AlphaSet& al, double* cost_out, int mode, int write_cost, bool with_accept = false) {
+  constexpr bool search = WHAT == RG_SEARCH, commit = WHAT == RG_COMMIT;
+  const int md = search ? mode : 0, wc = search ? 0 : commit ? write_cost : 1;  // (the search scores only; the init rollout always writes its cost)
   if constexpr (std::is_same<M, LqModel>::value)
   if (h->plan.rollout != Rollout::generic) {
-    const dim3 grid(h->B), block(64);
     const bool keeps = h->plan.rollout == Rollout::lq_accept;  // candidate buffers: the commit of what the next accept chooses is a copy (launch_commit)
-    if (what == RG_SEARCH && with_accept && keeps)
-      hipLaunchKernelGGL((k_rollout_lq<RG_SEARCH, true>), grid, block, 0, h->stream, h->v, m, al, cost_out, h->commit_idx, mode, 0, h->sp);
-    else if (what == RG_SEARCH)
-      hipLaunchKernelGGL((k_rollout_lq<RG_SEARCH>), grid, block, 0, h->stream, h->v, m, al, cost_out, nullptr, mode, 0, h->sp);
-    else if (what == RG_INIT)
-      hipLaunchKernelGGL((k_rollout_lq<RG_INIT>), grid, block, 0, h->stream, h->v, m, al, cost_out, nullptr, 0, 1, h->sp);
-    else
-      hipLaunchKernelGGL((k_rollout_lq<RG_COMMIT>), grid, block, 0, h->stream, h->v, m, al, cost_out, h->commit_idx, 0, write_cost, h->sp);
-    if (what == RG_SEARCH) h->lq_cands_kept = keeps;
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  const BatchViewT<typename M::real>& v = view_of<typename M::real>(h);
-  if constexpr (has_trajectory_params<M>::value)
-    if (h->plan.traj_params) {  // the same three launches with every lane's model copy set from its trajectory's row
-      const PerTrajectory<M> pm = per_trajectory(h, m);
-      if (what == RG_SEARCH)
-        hipLaunchKernelGGL((k_rollout_g<M, RG_SEARCH, true>), dim3((h->B + kSearchTraj - 1) / kSearchTraj), dim3(64), 0, h->stream, v, pm, al,
-                           cost_out, nullptr, mode, 0, h->sp.fixes);
-      else if (what == RG_INIT)
-        hipLaunchKernelGGL((k_rollout_g<M, RG_INIT, true>), dim3((h->B + 63) / 64), dim3(64), 0, h->stream, v, pm, al, cost_out, nullptr, 0, 1, h->sp.fixes);
-      else
-        hipLaunchKernelGGL((k_rollout_g<M, RG_COMMIT, true>), dim3((h->B + 63) / 64), dim3(64), 0, h->stream, v, pm, al, cost_out,
-                           h->commit_idx, 0, write_cost, h->sp.fixes);
+    if (search) h->lq_cands_kept = keeps;
+    return with_bool(search && with_accept && keeps, [&](auto acc) {
+      constexpr bool ACCEPT = search && decltype(acc)::value;
+      hipLaunchKernelGGL((k_rollout_lq<WHAT, ACCEPT>), dim3(h->B), dim3(64), 0, h->stream, h->v, m, al, cost_out,
+                         (ACCEPT || commit) ? h->commit_idx : nullptr, md, wc, h->sp);
       HIPCHK(hipGetLastError());
       return 0;
-    }
-  if (what == RG_SEARCH)
-    hipLaunchKernelGGL((k_rollout_g<M, RG_SEARCH>), dim3((h->B + kSearchTraj - 1) / kSearchTraj), dim3(64), 0, h->stream, v, m, al,
-                       cost_out, nullptr, mode, 0, h->sp.fixes);
-  else if (what == RG_INIT)
-    hipLaunchKernelGGL((k_rollout_g<M, RG_INIT>), dim3((h->B + 63) / 64), dim3(64), 0, h->stream, v, m, al, cost_out, nullptr, 0, 1, h->sp.fixes);
-  else
-    hipLaunchKernelGGL((k_rollout_g<M, RG_COMMIT>), dim3((h->B + 63) / 64), dim3(64), 0, h->stream, v, m, al, cost_out,
-                       h->commit_idx, 0, write_cost, h->sp.fixes);
-  HIPCHK(hipGetLastError());
-  return 0;
+    });
+  }
+  const dim3 grid(search ? (h->B + kSearchTraj - 1) / kSearchTraj : (h->B + 63) / 64);
+  return with_trajectory_params(h, m, [&](const auto& pm, auto pt) {
+    hipLaunchKernelGGL((k_rollout_g<M, WHAT, decltype(pt)::value>), grid, dim3(64), 0, h->stream, view_of<typename M::real>(h), pm, al, cost_out,
+                       commit ? h->commit_idx : nullptr, md, wc, h->sp.fixes);
+    HIPCHK(hipGetLastError());
+    return 0;
+  });
 }
 
 // with_accept (tiled models, 11-alpha search): the rollout kernel also does STEP 3/4 for its tile
@@ -125,9 +106,9 @@ static int launch_rollout(ilqr_batch* h, bool gains, bool cand, const AlphaSet& 
   if (int rc = timer_begin(h, ILQR_STAGE_ROLLOUT, &ev)) return rc;
   const int rc = (h->plan.rollout != Rollout::tiled)
       ? with_rollout_model(h, [&](auto& m) {
-          if (!gains) return launch_rollout_g(h, m, RG_INIT, al, cost_out, 0, 1);
-          if (n_alpha == NALPHA) return launch_rollout_g(h, m, RG_SEARCH, al, cost_out, mode, 0, with_accept);
-          return launch_rollout_g(h, m, RG_COMMIT, al, cost_out, 0, 1);  // a single closed-loop rollout written in place (warm start): slot commit_idx of `al`
+          if (!gains) return launch_rollout_g<RG_INIT>(h, m, al, cost_out, 0, 1);
+          if (n_alpha == NALPHA) return launch_rollout_g<RG_SEARCH>(h, m, al, cost_out, mode, 0, with_accept);
+          return launch_rollout_g<RG_COMMIT>(h, m, al, cost_out, 0, 1);  // a single closed-loop rollout written in place (warm start): slot commit_idx of `al`
         })
       : with_model(h, [&](auto& v, auto& m, auto&) { return launch_rollout_t(h, v, m, gains, cand, al, n_alpha, cost_out, mode, with_accept); });
   if (rc) return rc;
@@ -147,7 +128,7 @@ static int launch_commit(ilqr_batch* h) {
     return 0;
   }
   if (h->plan.commit != Commit::tiled)  // no stored candidates otherwise on the generic path: re-run the accepted rollout in place
-    return with_rollout_model(h, [&](auto& m) { return launch_rollout_g(h, m, RG_COMMIT, line_search_alphas(), h->v.cost, 0, 0); });
+    return with_rollout_model(h, [&](auto& m) { return launch_rollout_g<RG_COMMIT>(h, m, line_search_alphas(), h->v.cost, 0, 0); });
   if (int rc = refuse_grouped_cands(h)) return rc;
   dim3 grid((h->T + 1 + 15) / 16, h->ntiles), block(256);
   if (int rc = with_model(h, [&](auto& v, auto& m, auto&) {
@@ -214,6 +195,20 @@ static NominalArrays nominal_arrays(const ilqr_batch* h) {
           h->aos ? h->B : h->ntiles, lanes};
 }
 
+// the generic finite-difference sweep (k_derivatives_g): a wavefront per knot, or with t_only >= 0 per trajectory for that knot alone
+template <class M>
+static int launch_derivatives_g(ilqr_batch* h, const M& m, int force, int t_only) {
+  const dim3 grid(t_only < 0 ? h->B * (h->T + 1) : h->B);
+  return with_trajectory_params(h, m, [&](const auto& pm, auto pt) { return with_view(h, [&](auto& v) {
+    using S = std::remove_pointer_t<decltype(v.D)>;
+    if constexpr (std::is_same_v<S, float> && (M::NU > WM)) {  // float records: twins of at most WM controls (ilqr_create lets no fp32 handle have more)
+      return fail(ILQR_ERR_UNSUPPORTED, "k_derivatives_g: no fp32 handle has more than %d controls", WM);
+    } else {
+      hipLaunchKernelGGL((k_derivatives_g<M, S, decltype(pt)::value>), grid, dim3(64), 0, h->stream, v, pm, force, t_only);
+      return 0;
+    }
+  }); });
+}
 static int launch_derivatives(ilqr_batch* h, int force) {
   const Derivatives route = h->plan.derivatives;
   if (route != Derivatives::tiled)  // the generic sweep has no fused commit: rebuild the accepted rollout first
@@ -233,48 +228,27 @@ static int launch_derivatives(ilqr_batch* h, int force) {
   const int* ci = h->commit_pending ? h->commit_idx : nullptr;
   if (route != Derivatives::tiled) {
     // fp32 handles: the same kernels' float-storage instantiations (float knots widened, double arithmetic, float records)
-    const bool f32 = h->dtype == ILQR_DTYPE_F32;
+    int rc = 0;
     if (route == Derivatives::analytic_lq) {
-      const int what = (h->route.full_records || f32) ? 0 : 1;  // (A/B runs and the bit-identity test; fp32: whole records -- const_rec is double)
+      const int what = (h->route.full_records || h->dtype == ILQR_DTYPE_F32) ? 0 : 1;  // (A/B runs and the bit-identity test; fp32: whole records -- const_rec is double)
       const int chunk = (what == 1) ? 4 * kAnalyticChunk : kAnalyticChunk;
       const int nchunk = (h->T + 1 + chunk - 1) / chunk;
-      if (f32)
-        hipLaunchKernelGGL(k_analytic_lq<float>, dim3(h->B * nchunk), dim3(64), 0, h->stream, h->vf, h->lq, force, what, h->const_rec, chunk);
-      else
-        hipLaunchKernelGGL(k_analytic_lq<double>, dim3(h->B * nchunk), dim3(64), 0, h->stream, h->v, h->lq, force, what, h->const_rec, chunk);
+      rc = with_view(h, [&](auto& v) {
+        hipLaunchKernelGGL((k_analytic_lq<std::remove_pointer_t<decltype(v.D)>>), dim3(h->B * nchunk), dim3(64), 0, h->stream, v, h->lq, force, what, h->const_rec, chunk);
+        return 0;
+      });
       h->records_partial = (what == 1);
     } else if (route == Derivatives::lq) {
       // the LQ twin: every perturbed point of the knots t < T evaluated by what moved (k_derivatives_lq), knot T by the generic sweep
       const int nchunk = (h->T + kLqKnotsPerWave - 1) / kLqKnotsPerWave;
-      with_view(h, [&](auto& v) {
-        using S = std::remove_pointer_t<decltype(v.D)>;
-        hipLaunchKernelGGL(k_derivatives_lq<S>, dim3(h->B * nchunk), dim3(64), 0, h->stream, v, h->lq, force);
-        hipLaunchKernelGGL((k_derivatives_g<LqModel, S>), dim3(h->B), dim3(64), 0, h->stream, v, h->lq, force, h->T);
-        return 0;
+      rc = with_view(h, [&](auto& v) {
+        hipLaunchKernelGGL((k_derivatives_lq<std::remove_pointer_t<decltype(v.D)>>), dim3(h->B * nchunk), dim3(64), 0, h->stream, v, h->lq, force);
+        return launch_derivatives_g(h, h->lq, force, h->T);
       });
-    } else if (int rc = with_generic_model(h, [&](auto& m) {
-                 using M = std::decay_t<decltype(m)>;
-                 if constexpr (has_trajectory_params<M>::value)
-                   if (h->plan.traj_params) {
-                     const dim3 grid(h->B * (h->T + 1)), block(64);
-                     if constexpr (M::NU <= WM)
-                       if (f32) {
-                         hipLaunchKernelGGL((k_derivatives_g<M, float, true>), grid, block, 0, h->stream, h->vf, per_trajectory(h, m), force, -1);
-                         return 0;
-                       }
-                     hipLaunchKernelGGL((k_derivatives_g<M, double, true>), grid, block, 0, h->stream, h->v, per_trajectory(h, m), force, -1);
-                     return 0;
-                   }
-                 if constexpr (M::NU <= WM) {
-                   if (f32) {
-                     hipLaunchKernelGGL((k_derivatives_g<M, float>), dim3(h->B * (h->T + 1)), dim3(64), 0, h->stream, h->vf, m, force, -1);
-                     return 0;
-                   }
-                 }
-                 hipLaunchKernelGGL((k_derivatives_g<M>), dim3(h->B * (h->T + 1)), dim3(64), 0, h->stream, h->v, m, force, -1);
-                 return 0;
-               }))
-      return rc;
+    } else {
+      rc = with_generic_model(h, [&](auto& m) { return launch_derivatives_g(h, m, force, -1); });
+    }
+    if (rc) return rc;
     HIPCHK(hipGetLastError());
     return timer_end(h, ILQR_STAGE_DERIVATIVES, ev);
   }
@@ -290,6 +264,33 @@ static int launch_derivatives(ilqr_batch* h, int force) {
   return timer_end(h, ILQR_STAGE_DERIVATIVES, ev);
 }
 
+// The register-resident backward kernels of the generic layout, one wavefront per trajectory.  k_backward_w2<NT> (fp64 alone: ilqr_create), or
+// the k_backward_w3 that `w` describes.  The `if constexpr` below is the list of the k_backward_w3 that exist: FULL only over two row tiles;
+// REGV (ILQR_FLAG_REGULARIZE_VXX) on whole, masked records; two control tiles in fp64 and without any of the three.  What it excludes
+// route.hpp never asks for (tests/test_route_plan.py), and refusing it here is what keeps it from being compiled.
+static int launch_backward_w(ilqr_batch* h, const WaveVariant& w, bool w2, int mode, const double* crec) {
+  const dim3 grid(h->B), block(64);
+  if (w2)
+    return with_int<1, 2>(w.nt, [&](auto nt) {
+      hipLaunchKernelGGL(k_backward_w2<decltype(nt)::value>, grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec);
+      return 0;
+    });
+  return with_int<1, 2>(w.nt, [&](auto nt) { return with_int<1, 2>(w.mt, [&](auto mt) { return with_bool(w.full, [&](auto full) {
+    return with_bool(w.lqf, [&](auto lqf) { return with_bool(w.regv, [&](auto regv) { return with_bool(w.f32, [&](auto f32) {
+      constexpr int NT = decltype(nt)::value, MT = decltype(mt)::value;
+      constexpr bool FULL = decltype(full)::value, LQF = decltype(lqf)::value, REGV = decltype(regv)::value, F32 = decltype(f32)::value;
+      if constexpr ((FULL && NT != 2) || (REGV && (FULL || LQF)) || (MT == 2 && (FULL || LQF || REGV || F32))) {
+        return fail(ILQR_ERR_STATE, "k_backward_w3<%d, %d, %d, %d, %d, %s> is not built", NT, FULL, LQF, REGV, MT, F32 ? "float" : "double");
+      } else {
+        using S = std::conditional_t<F32, float, double>;
+        hipLaunchKernelGGL((k_backward_w3<NT, FULL, LQF, REGV, MT, S>), grid, block, 0, h->stream, view_of<S>(h), h->nx, h->nu, h->d_umin, h->d_umax,
+                           h->sp, mode, crec);
+        return 0;
+      }
+    }); }); });
+  }); }); });
+}
+
 static int launch_backward(ilqr_batch* h, int mode) {
   if (!h->aos)
     if (int rc = materialise_records(h)) return rc;
@@ -303,50 +304,16 @@ static int launch_backward(ilqr_batch* h, int mode) {
     if (!fused)
       if (int rc = ensure_records(h)) return rc;
     const double* crec = (fused || h->records_partial) ? h->const_rec : nullptr;
-    const dim3 grid(h->B), block(64);
-    const bool full = h->nu == WM && (h->nx == 16 || h->nx == 32);
-    const bool f32 = h->dtype == ILQR_DTYPE_F32;  // float storage: the <.., float> instantiations on h->vf (never W2 or two control tiles: ilqr_create)
-#define ILQR_W3_F64(...) hipLaunchKernelGGL((k_backward_w3<__VA_ARGS__>), grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec)
-#define ILQR_W3(NT_, FULL_, LQF_, REGV_)                                                                                                      \
-    do {                                                                                                                                    \
-      if (f32)                                                                                                                              \
-        hipLaunchKernelGGL((k_backward_w3<NT_, FULL_, LQF_, REGV_, 1, float>), grid, block, 0, h->stream, h->vf, h->nx, h->nu, h->d_umin,    \
-                           h->d_umax, h->sp, mode, crec);                                                                                   \
-      else                                                                                                                                  \
-        ILQR_W3_F64(NT_, FULL_, LQF_, REGV_);                                                                                               \
-    } while (0)
-    if (route == Backward::w3_two_tiles) {  // nu > 16, or ILQR_ROUTE_TWO_CONTROL_TILES (never the fused LQ route; ilqr_create keeps W2 and REGULARIZE_VXX off here)
-      if (h->nx > 16) ILQR_W3_F64(2, false, false, false, 2); else ILQR_W3_F64(1, false, false, false, 2);
-    } else if (route == Backward::w2 && h->nx > 16)
-      hipLaunchKernelGGL(k_backward_w2<2>, grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec);
-    else if (route == Backward::w2)
-      hipLaunchKernelGGL(k_backward_w2<1>, grid, block, 0, h->stream, h->v, h->nx, h->nu, h->d_umin, h->d_umax, h->sp, mode, crec);
-    else if (route == Backward::w3_regv) {  // ILQR_FLAG_REGULARIZE_VXX: the bounds-checked instantiations on whole records (never the fused LQ route)
-      if (h->nx > 16) ILQR_W3(2, false, false, true); else ILQR_W3(1, false, false, true);
-    } else if (h->nx > 16) {
-      if (fused) { if (full) ILQR_W3(2, true, true, false); else ILQR_W3(2, false, true, false); }
-      else { if (full) ILQR_W3(2, true, false, false); else ILQR_W3(2, false, false, false); }
-    } else {
-      if (fused) ILQR_W3(1, false, true, false); else ILQR_W3(1, false, false, false);
-    }
-#undef ILQR_W3
-#undef ILQR_W3_F64
-  } else if (route == Backward::quad) {
-    dim3 grid(h->ntiles), block(64);  // one wavefront = one tile of 16 trajectories x 4 lanes
-    if (int rc = with_model(h, [&](auto& v, auto& m, auto&) {
-          if constexpr (std::decay_t<decltype(m)>::NX == 4)
-            hipLaunchKernelGGL((k_backward_q<std::decay_t<decltype(m)>>), grid, block, 0, h->stream, v, m, h->sp, mode);
-          return 0;
-        }))
-      return rc;
-  } else {
-    dim3 grid(h->Bp / 64), block(64);
-    if (int rc = with_model(h, [&](auto& v, auto& m, auto&) {
-          hipLaunchKernelGGL((k_backward_t<std::decay_t<decltype(m)>>), grid, block, 0, h->stream, v, m, h->sp, mode);
-          return 0;
-        }))
-      return rc;
-  }
+    if (int rc = launch_backward_w(h, backward_wave_variant(route, h->nx, h->nu, h->dtype, fused), route == Backward::w2, mode, crec)) return rc;
+  } else if (int rc = with_model(h, [&](auto& v, auto& m, auto&) {
+               using MM = std::decay_t<decltype(m)>;
+               if (route == Backward::thread)
+                 hipLaunchKernelGGL((k_backward_t<MM>), dim3(h->Bp / 64), dim3(64), 0, h->stream, v, m, h->sp, mode);
+               else if constexpr (MM::NX == 4)  // one wavefront = one tile of 16 trajectories x 4 lanes
+                 hipLaunchKernelGGL((k_backward_q<MM>), dim3(h->ntiles), dim3(64), 0, h->stream, v, m, h->sp, mode);
+               return 0;
+             }))
+    return rc;
   HIPCHK(hipGetLastError());
   return timer_end(h, ILQR_STAGE_BACKWARD, ev);
 }
@@ -359,12 +326,12 @@ static int launch_sweep_backward(ilqr_batch* h, int mode, int force) {
   if (int rc = with_model(h, [&](auto& v, auto& m, auto& fdm) {
         using MM = std::decay_t<decltype(m)>;
         using MF = std::decay_t<decltype(fdm)>;
-        if constexpr (MM::NX == 4) {
-          if (h->plan.sweep == Sweep::one_producer)
-            hipLaunchKernelGGL((k_sweep_backward<MM, 1, kRingKbTwoBlocks, MF>), dim3(h->ntiles), dim3(64 * 2), 0, h->stream, v, m, fdm, h->sp, mode, force, ci);
-          else
-            hipLaunchKernelGGL((k_sweep_backward<MM, kProducers, ILQR_RING_KB, MF>), dim3(h->ntiles), dim3(64 * (1 + kProducers)), 0, h->stream, v, m, fdm, h->sp, mode, force, ci);
-        }
+        if constexpr (MM::NX == 4)
+          return with_bool(h->plan.sweep == Sweep::one_producer, [&](auto one) {
+            constexpr int P = decltype(one)::value ? 1 : kProducers, KB = decltype(one)::value ? kRingKbTwoBlocks : ILQR_RING_KB;
+            hipLaunchKernelGGL((k_sweep_backward<MM, P, KB, MF>), dim3(h->ntiles), dim3(64 * (1 + P)), 0, h->stream, v, m, fdm, h->sp, mode, force, ci);
+            return 0;
+          });
         return 0;
       }))
     return rc;
@@ -400,18 +367,19 @@ static int launch_solve_tiles(ilqr_batch* h, int n_iters) {
         if constexpr (MM::NX != 4) {
           return fail(ILQR_ERR_STATE, "persistent tiles are nx = 4 kernels");
         } else {
-#define ILQR_SOLVE(K, blocks, threads) hipLaunchKernelGGL(K, dim3(blocks), dim3(threads), 0, h->stream, v, m, fdm, al, h->sp, n_iters, h->sp.fixed_work, h->commit_idx, pending, ticks)
+          auto solve_with = [&](auto kernel, int blocks, int threads) {
+            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, h->stream, v, m, fdm, al, h->sp, n_iters, h->sp.fixed_work, h->commit_idx, pending, ticks);
+          };
           const int wide_blocks = (grid_tiles + 3) / 4;  // (wide tiles: one per CU while they fit, else two -- or as ILQR_ROUTE_WIDE_ONE/TWO_PER_CU says)
           const bool wide_one = h->route.wide_occ == 1 || (h->route.wide_occ == 0 && wide_blocks <= h->num_cus);
           switch (solve) {
-            case Solve::wide: if constexpr (MM::NU == 1) { if (wide_one) ILQR_SOLVE((k_solve_wide<MM, MF, 1>), wide_blocks, 512); else ILQR_SOLVE((k_solve_wide<MM, MF, 2>), wide_blocks, 256); } break;
-            case Solve::wide2: if constexpr (MM::NU == 2) ILQR_SOLVE((k_solve_wide2<MM, MF>), wide_blocks, 256); break;
-            case Solve::hex: if constexpr (MM::NU == 1) ILQR_SOLVE((k_solve_hex<MM, MF>), grid_tiles, 512); break;
-            case Solve::tile1: ILQR_SOLVE((k_solve_tile<MM, MF, 1>), grid_tiles, 256); break;
-            case Solve::tile2: ILQR_SOLVE((k_solve_tile<MM, MF, 2>), grid_tiles, 256); break;
+            case Solve::wide: if constexpr (MM::NU == 1) { if (wide_one) solve_with(k_solve_wide<MM, MF, 1>, wide_blocks, 512); else solve_with(k_solve_wide<MM, MF, 2>, wide_blocks, 256); } break;
+            case Solve::wide2: if constexpr (MM::NU == 2) solve_with(k_solve_wide2<MM, MF>, wide_blocks, 256); break;
+            case Solve::hex: if constexpr (MM::NU == 1) solve_with(k_solve_hex<MM, MF>, grid_tiles, 512); break;
+            case Solve::tile1: solve_with(k_solve_tile<MM, MF, 1>, grid_tiles, 256); break;
+            case Solve::tile2: solve_with(k_solve_tile<MM, MF, 2>, grid_tiles, 256); break;
             case Solve::none: break;
           }
-#undef ILQR_SOLVE
         }
         return 0;
       }))
@@ -427,12 +395,10 @@ static int launch_solve_tiles(ilqr_batch* h, int n_iters) {
 // The value model of the stored policy (ilqr_get_value / ilqr_copy_value_to_device; value_wave.hpp, value_thread.hpp): picked by the
 // handle's layout and sizes alone -- no route bit, no stage timer.  The caller has materialised the records.  Vx [B][nk][nx], Vxx
 // [B][nk][nx * nx]: canonical double in device memory, either may be null.
-static const char* value_kernel_name(const ilqr_batch* h) {
-  if (!h->aos) return "k_value_t";
-  return h->nu > WM ? (h->nx > 16 ? "k_value_w<2, 2>" : "k_value_w<1, 2>") : (h->nx > 16 ? "k_value_w<2, 1>" : "k_value_w<1, 1>");
-}
+// `name`: the kernel, for the caller's message should the launch itself be refused (route.hpp: value_kernel_name)
 static int launch_value(ilqr_batch* h, int t0, int nk, double* Vx, double* Vxx, const char** name) {
-  *name = value_kernel_name(h);
+  const WaveVariant w = value_wave_variant(h->nx, h->nu, h->dtype);
+  *name = value_kernel_name(h->aos, w);
   if (!h->aos) {
     const dim3 grid(h->Bp / 64), block(64);
     if (int rc = with_model(h, [&](auto& v, auto& m, auto&) {
@@ -440,50 +406,39 @@ static int launch_value(ilqr_batch* h, int t0, int nk, double* Vx, double* Vxx, 
           return 0;
         }))
       return rc;
-  } else {
-    const dim3 grid(h->B), block(64);
-    const bool f32 = h->dtype == ILQR_DTYPE_F32;  // float storage (never with two control tiles: ilqr_create)
-#define ILQR_VALUE_W(NT_, MT_)                                                                                                          \
-    do {                                                                                                                                \
-      if (f32 && MT_ == 1)                                                                                                              \
-        hipLaunchKernelGGL((k_value_w<NT_, 1, float>), grid, block, 0, h->stream, h->vf, h->nx, h->nu, t0, nk, Vx, Vxx);                  \
-      else if (f32)                                                                                                                     \
-        return fail(ILQR_ERR_UNSUPPORTED, "%s: no fp32 handle has more than %d controls", *name, WM);                                   \
-      else                                                                                                                              \
-        hipLaunchKernelGGL((k_value_w<NT_, MT_, double>), grid, block, 0, h->stream, h->v, h->nx, h->nu, t0, nk, Vx, Vxx);               \
-    } while (0)
-    if (h->nu > WM) { if (h->nx > 16) ILQR_VALUE_W(2, 2); else ILQR_VALUE_W(1, 2); }
-    else { if (h->nx > 16) ILQR_VALUE_W(2, 1); else ILQR_VALUE_W(1, 1); }
-#undef ILQR_VALUE_W
-  }
+  } else if (int rc = with_int<1, 2>(w.nt, [&](auto nt) { return with_int<1, 2>(w.mt, [&](auto mt) { return with_bool(w.f32, [&](auto f32) {
+               constexpr int MT = decltype(mt)::value;
+               using S = std::conditional_t<decltype(f32)::value, float, double>;
+               if constexpr (MT == 2 && decltype(f32)::value) {  // float storage: never with two control tiles (ilqr_create)
+                 return fail(ILQR_ERR_UNSUPPORTED, "%s: no fp32 handle has more than %d controls", *name, WM);
+               } else {
+                 hipLaunchKernelGGL((k_value_w<decltype(nt)::value, MT, S>), dim3(h->B), dim3(64), 0, h->stream, view_of<S>(h), h->nx, h->nu, t0, nk, Vx, Vxx);
+                 return 0;
+               }
+             }); }); }))
+    return rc;
   HIPCHK(hipGetLastError());
   return 0;
 }
 
 // The stored policy applied to caller-given states (ilqr_evaluate_policy / _on_device; evaluate.hpp): picked by the handle's layout alone,
 // as launch_value -- no route bit, no stage timer.  One thread per rollout, B * S of them (the caller has checked that they fit an int).
-static const char* evaluate_kernel_name(const ilqr_batch* h) { return h->aos ? (h->plan.traj_params ? "k_evaluate_g<PT>" : "k_evaluate_g") : "k_evaluate_t"; }
-static int launch_evaluate(ilqr_batch* h, const EvalArgs& e) {
+static int launch_evaluate(ilqr_batch* h, const EvalArgs& e, const char** name) {
   const dim3 grid((unsigned)(((size_t)h->B * e.S + 63) / 64)), block(64);
   if (!h->aos)
     return with_model(h, [&](auto& v, auto& m, auto&) {
+      *name = evaluate_kernel_name(false, false);
       hipLaunchKernelGGL((k_evaluate_t<std::decay_t<decltype(m)>>), grid, block, 0, h->stream, v, m, e);
       HIPCHK(hipGetLastError());
       return 0;
     });
-  return with_rollout_model(h, [&](auto& m) {
+  return with_rollout_model(h, [&](auto& m) { return with_trajectory_params(h, m, [&](const auto& pm, auto pt) {
     using M = std::decay_t<decltype(m)>;
-    const BatchViewT<typename M::real>& v = view_of<typename M::real>(h);
-    if constexpr (has_trajectory_params<M>::value)
-      if (h->plan.traj_params) {
-        hipLaunchKernelGGL((k_evaluate_g<M, true>), grid, block, 0, h->stream, v, per_trajectory(h, m), e);
-        HIPCHK(hipGetLastError());
-        return 0;
-      }
-    hipLaunchKernelGGL((k_evaluate_g<M>), grid, block, 0, h->stream, v, m, e);
+    *name = evaluate_kernel_name(true, decltype(pt)::value);
+    hipLaunchKernelGGL((k_evaluate_g<M, decltype(pt)::value>), grid, block, 0, h->stream, view_of<typename M::real>(h), pm, e);
     HIPCHK(hipGetLastError());
     return 0;
-  });
+  }); });
 }
 
 static AlphaSet line_search_alphas() {

@@ -27,10 +27,32 @@ struct RoutePlan {  // (the defaults: what ilqr_stage_kernel_name reports for a 
   Backward backward = Backward::thread;
   Rollout rollout = Rollout::tiled;
   Commit commit = Commit::tiled;
-  // per-trajectory model parameters are set (ilqr_set_trajectory_params ... ilqr_clear_trajectory_params): every launcher that hands the
-  // user twin to k_rollout_g / k_derivatives_g takes their PT instantiations.  The one part of the plan that changes after ilqr_create.
+  // per-trajectory model parameters are set (ilqr_set_trajectory_params ... ilqr_clear_trajectory_params): every launch that hands the
+  // user twin to k_rollout_g / k_derivatives_g / k_evaluate_g takes the PT instantiation (launch.hpp: with_trajectory_params).  The one
+  // part of the plan that changes after ilqr_create.
   bool traj_params = false;
 };
+
+// Which instantiation of a wavefront-per-trajectory kernel a handle of these sizes runs, as plain data (launch.hpp turns it into template
+// arguments and says which combinations are built).  nt: 16-row tiles covering nx; mt: 16-column control tiles covering nu, or two by
+// route bit; full: no masked rows or columns (nx = 32, nu = 16); lqf: cx, cu formed from the knot (the fused LQ route).
+struct WaveVariant {
+  int nt, mt;
+  bool full, lqf, regv, f32;
+};
+inline WaveVariant backward_wave_variant(Backward b, int nx, int nu, int dtype, bool fused) {  // k_backward_w3, and nt of k_backward_w2
+  const bool plain = b == Backward::w3;
+  return {nx > 16 ? 2 : 1, b == Backward::w3_two_tiles ? 2 : 1, plain && nx == 32 && nu == 16, plain && fused, b == Backward::w3_regv,
+          dtype == ILQR_DTYPE_F32};
+}
+inline WaveVariant value_wave_variant(int nx, int nu, int dtype) {  // k_value_w
+  return {nx > 16 ? 2 : 1, nu > 16 ? 2 : 1, false, false, false, dtype == ILQR_DTYPE_F32};
+}
+inline const char* value_kernel_name(bool aos, const WaveVariant& w) {
+  static const char* const kWave[2][2] = {{"k_value_w<1, 1>", "k_value_w<1, 2>"}, {"k_value_w<2, 1>", "k_value_w<2, 2>"}};
+  return aos ? kWave[w.nt - 1][w.mt - 1] : "k_value_t";
+}
+inline const char* evaluate_kernel_name(bool aos, bool traj_params) { return !aos ? "k_evaluate_t" : traj_params ? "k_evaluate_g<PT>" : "k_evaluate_g"; }
 
 struct RouteInputs {
   int model, nx, nu, flags, route, ntiles, num_cus;  // (num_cus after ilqr_desc.assume_cus)

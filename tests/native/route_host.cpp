@@ -12,6 +12,17 @@ extern "C" void route_kernel_names(int model, int nx, int nu, int flags, int rou
   for (int s = 0; s < ILQR_NUM_STAGES; s++) names[s] = stage_kernel_name(p, s);
 }
 
+// out[6] = {nt, mt, full, lqf, regv, f32}: the k_backward_w3 instantiation (nt: also k_backward_w2's) of a generic handle created from
+// these inputs, while its backward pass reads the model's own records (no ilqr_set_derivatives); returns the value kernel's name
+extern "C" const char* route_wave_variants(int model, int nx, int nu, int flags, int route, int dtype, int* out) {
+  const bool cands = lq_matrix_core_search(model, nu, route) && !(route & ILQR_ROUTE_LQ_RECOMMIT);
+  const RoutePlan p = plan_route({model, nx, nu, flags, route, 4, 256, false, false, cands, dtype});
+  const WaveVariant w = backward_wave_variant(p.backward, nx, nu, dtype, p.derivatives == Derivatives::fused_lq);
+  const int fields[6] = {w.nt, w.mt, w.full, w.lqf, w.regv, w.f32};
+  for (int i = 0; i < 6; i++) out[i] = fields[i];
+  return value_kernel_name(generic_layout(model, route, false, false), value_wave_variant(nx, nu, dtype));
+}
+
 // ... for a null handle
 extern "C" void route_default_names(const char** names) {
   for (int s = 0; s < ILQR_NUM_STAGES; s++) names[s] = stage_kernel_name(RoutePlan{}, s);

@@ -29,6 +29,8 @@ def lib():
     lib = C.CDLL(SO)
     lib.route_kernel_names.argtypes = [C.c_int] * 10 + [C.POINTER(C.c_char_p)]
     lib.route_default_names.argtypes = [C.POINTER(C.c_char_p)]
+    lib.route_wave_variants.argtypes = [C.c_int] * 6 + [C.POINTER(C.c_int)]
+    lib.route_wave_variants.restype = C.c_char_p
     return lib
 
 
@@ -135,6 +137,44 @@ def test_more_than_16_controls(lib):
             n = names(lib, model, nx, nu, 6, flags=flags, user=user)
             assert (n["derivatives"], n["backward"], n["rollout"]) == (b"k_derivatives_g", b"k_backward_w3w", b"k_rollout_g")
     assert names(lib, HOST, 24, 20, 6)["backward"] == b"k_backward_w3w"
+
+
+ANALYTIC, REGV = capi.FLAG_ANALYTIC_DERIVATIVES, capi.FLAG_REGULARIZE_VXX
+
+
+@pytest.mark.parametrize("nx,nu,flags,route,dtype,variant,value", [
+    # (nt, mt, FULL, LQF, REGV, float storage) of k_backward_w3; FULL: nothing masked, 32 states and 16 controls
+    (32, 16, 0, 0, capi.DTYPE_F64, (2, 1, 1, 0, 0, 0), b"k_value_w<2, 1>"),
+    (16, 16, 0, 0, capi.DTYPE_F64, (1, 1, 0, 0, 0, 0), b"k_value_w<1, 1>"),
+    (6, 3, 0, 0, capi.DTYPE_F64, (1, 1, 0, 0, 0, 0), b"k_value_w<1, 1>"),
+    (24, 16, 0, 0, capi.DTYPE_F64, (2, 1, 0, 0, 0, 0), b"k_value_w<2, 1>"),
+    (24, 20, 0, 0, capi.DTYPE_F64, (2, 2, 0, 0, 0, 0), b"k_value_w<2, 2>"),  # two control tiles
+    (32, 32, ANALYTIC, 0, capi.DTYPE_F64, (2, 2, 0, 0, 0, 0), b"k_value_w<2, 2>"),  # ... never fused, never FULL
+    (6, 3, 0, capi.ROUTE_TWO_CONTROL_TILES, capi.DTYPE_F64, (1, 2, 0, 0, 0, 0), b"k_value_w<1, 1>"),  # ... by route bit: the backward pass alone
+    (32, 16, ANALYTIC, 0, capi.DTYPE_F64, (2, 1, 1, 1, 0, 0), b"k_value_w<2, 1>"),  # the fused LQ route
+    (6, 3, ANALYTIC, 0, capi.DTYPE_F64, (1, 1, 0, 1, 0, 0), b"k_value_w<1, 1>"),
+    (32, 16, ANALYTIC, capi.ROUTE_FULL_RECORDS, capi.DTYPE_F64, (2, 1, 1, 0, 0, 0), b"k_value_w<2, 1>"),
+    (32, 16, REGV, 0, capi.DTYPE_F64, (2, 1, 0, 0, 1, 0), b"k_value_w<2, 1>"),  # REGULARIZE_VXX: masked, never fused
+    (6, 3, ANALYTIC | REGV, 0, capi.DTYPE_F64, (1, 1, 0, 0, 1, 0), b"k_value_w<1, 1>"),
+    (32, 16, 0, 0, capi.DTYPE_F32, (2, 1, 1, 0, 0, 1), b"k_value_w<2, 1>"),  # fp32: every one-tile variant again, on float storage
+    (6, 3, ANALYTIC, 0, capi.DTYPE_F32, (1, 1, 0, 1, 0, 1), b"k_value_w<1, 1>"),
+    (6, 3, REGV, 0, capi.DTYPE_F32, (1, 1, 0, 0, 1, 1), b"k_value_w<1, 1>"),
+    (32, 16, 0, capi.ROUTE_BACKWARD_W2, capi.DTYPE_F64, (2, 1, 0, 0, 0, 0), b"k_value_w<2, 1>"),  # k_backward_w2<nt>
+    (6, 3, 0, capi.ROUTE_BACKWARD_W2, capi.DTYPE_F64, (1, 1, 0, 0, 0, 0), b"k_value_w<1, 1>"),
+])
+def test_wave_kernel_variants(lib, nx, nu, flags, route, dtype, variant, value):
+    """tests/test_gpu_generic_backward.py, test_gpu_wide_controls.py, test_gpu_generic_fp32.py, test_gpu_analytic.py, test_gpu_value.py: which
+    instantiation of the wavefront-per-trajectory backward and value kernels an LQ handle of these sizes launches"""
+    out = (C.c_int * 6)()
+    name = lib.route_wave_variants(LQ, nx, nu, flags, route, dtype, out)
+    assert (tuple(out), name) == (variant, value)
+    # what launch.hpp builds of k_backward_w3: FULL over two row tiles only; REGV masked and unfused; two control tiles plain and in fp64
+    nt, mt, full, lqf, regv, f32 = variant
+    assert not (full and nt != 2) and not (regv and (full or lqf)) and not (mt == 2 and (full or lqf or regv or f32))
+
+
+def test_tiled_handles_run_the_thread_value_kernel(lib):
+    assert lib.route_wave_variants(ACROBOT, 4, 1, 0, 0, capi.DTYPE_F64, (C.c_int * 6)()) == b"k_value_t"
 
 
 def test_host_evaluated_models(lib):
