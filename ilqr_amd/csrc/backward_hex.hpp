@@ -30,6 +30,11 @@ namespace ilqr {
 #define ILQR_COMMIT_ROLLED 1
 #endif
 
+#ifndef ILQR_COMMIT_BATCH
+#define ILQR_COMMIT_BATCH 2   // tasks of the commit whose loads a thread issues together (1: one task at a time, A/B)
+#endif
+constexpr int kCommitBatch = ILQR_COMMIT_BATCH;
+
 constexpr int HT = 4;  // trajectories per sub-tile (= per chain wavefront)
 #ifndef ILQR_HEX_SLOT_PAD
 #define ILQR_HEX_SLOT_PAD 8
@@ -41,6 +46,10 @@ constexpr int HT = 4;  // trajectories per sub-tile (= per chain wavefront)
 #define ILQR_HEX_CAND_T 1   // the kernel's candidates in groups per trajectory (rollout.hpp: CANDT); 0: one element per trajectory, the stage kernels' layout (A/B)
 #endif
 constexpr bool kHexCandT = ILQR_HEX_CAND_T != 0;
+#ifndef ILQR_HEX_QUAD_ROLLOUT
+#define ILQR_HEX_QUAD_ROLLOUT 1   // the kernel's rollouts as one quad x eleven alphas per SIMD (rollout.hpp: QUAD); 0: 16 trajectories x 4 alphas on three SIMDs (A/B)
+#endif
+constexpr bool kHexQuadRollout = ILQR_HEX_QUAD_ROLLOUT != 0;
 
 // One pair's ring: a slot holds one knot of the sub-tile's 4 trajectories, pair-interleaved like the HBM records:
 // [pair][trajectory lp][2].
@@ -544,16 +553,27 @@ __device__ __forceinline__ void commit_tile_chunks(const BatchViewT<typename M::
   using real = typename M::real;
   constexpr int NX = M::NX, NU = M::NU;
   static_assert(!CANDT || (NX == 4 && NU == 1 && CT == 8 && CG == 4), "grouped candidates: nx = 4, nu = 1");
+  static_assert(HT == kQuad, "a chain wavefront rolls out its own sub-tile");
   const int T = v.T;
   const real dt = (real)v.dt;
   const int ntask = v.nch * TW;
-  for (int task = threadIdx.x; task < ntask; task += blockDim.x) {
+  struct Task {
+    int l, c;                // trajectory of the tile and chunk; c < 0: nothing to commit
+    real x[NX], uq[CT][NU];  // the checkpoint and the chunk's controls: one memory round trip, then the steps
+  };
+  auto load = [&](int task, Task& k) __attribute__((always_inline)) {
+    k.l = 0;
+    k.c = -1;
+    if (task < 0) return;
     const int l = task & (TW - 1), c = task >> 4;
     const int b = tile * TW + l;
     const int ci = (b < v.B) ? commit_of_lane[l] : -1;
-    if (ci < 0) continue;
+    if (ci < 0) return;
+    k.l = l;
+    k.c = c;
     const int ta = ci * v.ntiles + tile;
-    real x[NX], uq[CT][NU];  // the checkpoint and the chunk's controls: one memory round trip, then the steps
+    real* const x = k.x;
+    real(*const uq)[NU] = k.uq;
     if constexpr (CANDT) {
       typedef real real4v __attribute__((ext_vector_type(4)));
       const real4v xv = *reinterpret_cast<const real4v*>(v.cand_x + cand_g_x(ta, c, l, v.nch, NX));
@@ -583,6 +603,12 @@ __device__ __forceinline__ void commit_tile_chunks(const BatchViewT<typename M::
       for (int jj = 0; jj < NU; jj++) uq[q][jj] = v.cand_u[tidx(ta, tq, jj, l, T, NU)];
     }
     }
+  };
+  auto steps = [&](Task& k) __attribute__((always_inline)) {
+    if (k.c < 0) return;
+    const int l = k.l, c = k.c;
+    real* const x = k.x;
+    real(*const uq)[NU] = k.uq;
 #if ILQR_COMMIT_ROLLED
     // ONE copy of the step in the instruction stream (a rolled loop; the chunk's controls move down a register per trip so that
     // every index stays static): 1 KB instead of 7 KB of code that runs once per iteration between two long loops.  Same time as the
@@ -628,6 +654,16 @@ __device__ __forceinline__ void commit_tile_chunks(const BatchViewT<typename M::
       }
     }
 #endif
+  };
+  // Tasks in DESCENDING order (the top of the horizon, where the next backward pass begins, is committed first), kCommitBatch per thread
+  // and trip: the loads of all of them are issued before the Euler steps of the first, so that a thread with two tasks (T = 499: 1 008
+  // tasks on 512 threads) waits for memory once, not twice.  Each task is what it was: the same bits.
+  for (int first = ntask - 1 - (int)threadIdx.x; first >= 0; first -= kCommitBatch * (int)blockDim.x) {
+    Task k[kCommitBatch];
+#pragma unroll
+    for (int j = 0; j < kCommitBatch; j++) load(first - j * (int)blockDim.x, k[j]);
+#pragma unroll
+    for (int j = 0; j < kCommitBatch; j++) steps(k[j]);
   }
 }
 
@@ -661,7 +697,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     __syncthreads();
     if (simd_count[0] == 2 && simd_count[1] == 2 && simd_count[2] == 2 && simd_count[3] == 2) role = simd + 4 * slot;
   }
-  const int rwave = (role < 3) ? role : 3;  // the chains of pairs 0..2 roll out (one per SIMD); rwave 3 has no alphas
+  // the chain wavefront of pair s rolls out the pair's own four trajectories under every alpha: one quad per SIMD; 4: no rollouts
+  // (!kHexQuadRollout: the chains of pairs 0..2 roll out four alphas of the whole tile each; rwave 3 has no alphas)
+  const int rwave = kHexQuadRollout ? ((role < 4) ? role : 4) : ((role < 3) ? role : 3);
   const int tile = blockIdx.x;
   constexpr int kShareReals = 4 * ((2 * M::NU + M::NU * M::NX + M::NX + 3) / 4) * TW;
   static_assert(kShareReals <= (int)(sizeof(pairs[0].ring) / sizeof(real)), "a pair's ring holds a wavefront's rollout rows");
@@ -688,7 +726,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       t_sweep += t1 - t0;
       t0 = t1;
     }
-    rollout_tile<M, true, true, kDeepPrefetch<M>, true, true, true, 1, kHexCandT>(v, model, alphas, NALPHA, v.cost_c, 1, sp, commit_idx, tile, lds_cost, /*count_running=*/it == n_iters - 1, rwave,
+    rollout_tile<M, true, true, kDeepPrefetch<M>, true, true, true, 1, kHexCandT, kHexQuadRollout>(v, model, alphas, NALPHA, v.cost_c, 1, sp, commit_idx, tile, lds_cost, /*count_running=*/it == n_iters - 1, rwave,
                                                pairs[role & 3].ring);
 #ifdef ILQR_HEX_SECTIONS  // experiment builds (scripts/hex_sections.sh): the "backward" clock runs up to mark ILQR_HEX_SECTIONS, the "rollout" clock from there
 #define ILQR_HEX_MARK(n)                                   \

@@ -2,6 +2,7 @@
 // (STEP 3/4, :185-282), candidate checkpoints and their re-integration.
 #pragma once
 #include "layout.hpp"
+#include "quad_lanes.hpp"
 
 namespace ilqr {
 
@@ -134,7 +135,13 @@ static_assert(CT % CG == 0, "a chunk of the commit is a whole number of control 
 __host__ __device__ inline int cand_groups(int T) { return (T + CT + CG - 1) / CG; }   // groups per plane row: whole chunks past T - 1
 __host__ __device__ inline size_t cand_g_u(int ta, int grp, int l, int T) { return (((size_t)ta * cand_groups(T) + grp) * TW + l) * CG; }
 __host__ __device__ inline size_t cand_g_x(int ta, int c, int l, int nch, int NX) { return (((size_t)ta * nch + c) * TW + l) * NX; }
-template <class M, bool GAINS, bool CAND, int PD, bool ACCEPT, bool SHARE = false, bool NOFIX = false, int NG = 1, bool CANDT = false>
+// QUAD (k_solve_hex): the tile cut the other way -- a wavefront is the FOUR trajectories of sub-tile `rwave` x ALL alphas (lane = 4 alpha + q,
+// quad_lanes.hpp; rwave >= 4: no rollouts) instead of sixteen trajectories x four alphas.  Its step needs the 4 x NROWS rows of its own quad
+// and nothing else: ONE load, one LDS write and one pointer increment per lane and step (lane 4 row + q) where the 16 x 4 wavefront has three
+// of each, a register ring of one value per depth instead of three, and every row of the tile is fetched by one wavefront instead of by all
+// three.  The lanes behind the last alpha's (44..63) sit the whole rollout out: no arithmetic, no stores.  Each rollout is the expression
+// sequence of every other mapping, its cost lands in the same lds_cost / cost_out element, its candidate in the same plane: the same bits.
+template <class M, bool GAINS, bool CAND, int PD, bool ACCEPT, bool SHARE = false, bool NOFIX = false, int NG = 1, bool CANDT = false, bool QUAD = false>
 __device__ __forceinline__ void rollout_tile(const BatchViewT<typename M::real>& v, const M& model, const AlphaSet& alphas, int n_alpha,
                                              double* __restrict__ cost_out, int mode, const SolverParams& sp,
                                              int* __restrict__ commit_idx, int tile, double* lds_cost, bool count_running = true, int rwave = -1,
@@ -142,10 +149,13 @@ __device__ __forceinline__ void rollout_tile(const BatchViewT<typename M::real>&
   using real = typename M::real;
   constexpr int NX = M::NX, NU = M::NU;
   static_assert(NG == 1 || (SHARE && GAINS && !ACCEPT), "several alpha groups per wavefront: the shared-row rollout of the wide tiles");
+  static_assert(!QUAD || (SHARE && GAINS && NG == 1 && quad_rollout_lanes(NALPHA) <= 64 && kQuad * rollout_rows(NX, NU) <= quad_rollout_lanes(NALPHA)),
+                "quad rollouts: every alpha of four trajectories in one wavefront, whose lanes also fetch the quad's rows");
   static_assert(!CANDT || (CAND && SHARE && GAINS && NU == 1 && NX == 4 && PD % CG == 0), "grouped candidates: the matrix-core kernel's rollouts (nx = 4, nu = 1)");
-  const int wave = (rwave >= 0) ? rwave : (int)(threadIdx.x >> 6);  // which four alphas this wavefront rolls out (>= 3: none)
+  const int wave = (rwave >= 0) ? rwave : (int)(threadIdx.x >> 6);  // which four alphas this wavefront rolls out (>= 3: none); QUAD: which sub-tile (>= 4: none)
   const int lane = threadIdx.x & 63;
-  const int l = lane & (TW - 1);
+  const int l = QUAD ? quad_traj(wave & 3, quad_lane_q(lane)) : lane & (TW - 1);
+  const bool idle = QUAD && lane >= quad_rollout_lanes(NALPHA);  // QUAD: a lane behind the last alpha's
   const int a_sub = lane >> 4;
   const int b = tile * TW + l;
   // NG alpha groups per wavefront (the wide tiles' NG = 3: every lane carries the rollouts of alphas a_sub, 4 + a_sub, 8 + a_sub of its
@@ -157,15 +167,15 @@ __device__ __forceinline__ void rollout_tile(const BatchViewT<typename M::real>&
   const bool eligible = (b < v.B) && (mode != 1 || (v.status[b < v.B ? b : 0] == 0 && v.backpass_done[b < v.B ? b : 0]));
 #pragma unroll
   for (int g = 0; g < NG; g++) {
-    a[g] = (wave + g) * 4 + a_sub;
-    active[g] = eligible && (a[g] < n_alpha);
+    a[g] = QUAD ? quad_lane_alpha(lane) : (wave + g) * 4 + a_sub;
+    active[g] = eligible && (a[g] < n_alpha) && (!QUAD || wave < 4);
     any_active = any_active || active[g];
   }
   // SHARE: every lane of a wavefront with work fetches its rows and runs the steps (an alpha group without an alpha, the
   // lanes of a finished trajectory: their arithmetic is discarded); `active` only decides who stores
   const bool run = (SHARE && GAINS) ? (__ballot(any_active) != 0ull) : any_active;
   if (!ACCEPT && !run) return;
-  if (run) {
+  if (run && !idle) {
   const int T = v.T;
   real alpha[NG];
 #pragma unroll
@@ -298,16 +308,18 @@ __device__ __forceinline__ void rollout_tile(const BatchViewT<typename M::real>&
     static_assert(PD % 2 == 0 || PD == 1, "static ring indices");
     static_assert((size_t)PD * NU * NX * TW <= rollout_fetch_slack_elems(NX, NU), "PD knots past the end");
     constexpr int NROWS = 2 * NU + NU * NX + NX;  // u, k, K, xs
-    constexpr int NLD = (NROWS + 3) / 4;          // rows per alpha group
+    static_assert(NROWS == rollout_rows(NX, NU), "quad_lanes.hpp counts the same rows");
+    constexpr int NLD = QUAD ? 1 : (NROWS + 3) / 4;  // rows per alpha group; QUAD: per lane
     struct Raw {
       real r[NLD];
     };
     // this lane's rows: a_sub, a_sub + 4, ... (past the end: the last row again, parked in a dummy LDS row)
+    // QUAD: row lane / 4 of trajectory l (past the end: the last row again, into that row's own slot -- the value it holds anyway)
     const real* rbase[NLD];
     unsigned rstride[NLD];  // elements from step t to step t + 1
 #pragma unroll
     for (int j = 0; j < NLD; j++) {
-      const int row = (a_sub + 4 * j < NROWS) ? a_sub + 4 * j : NROWS - 1;
+      const int row = QUAD ? quad_fetch_row(lane, NROWS) : (a_sub + 4 * j < NROWS) ? a_sub + 4 * j : NROWS - 1;
       if (row < NU) {
         rbase[j] = v.us + tidx(tile, 0, row, l, T, NU);
         rstride[j] = NU * TW;
@@ -337,12 +349,12 @@ __device__ __forceinline__ void rollout_tile(const BatchViewT<typename M::real>&
     // (fp32: 8-byte) LDS instruction, five per step for the acrobot's ten rows instead of ten
     typedef real real2_t __attribute__((ext_vector_type(2)));
     constexpr int NPAIR = (NROWS + 1) / 2;
-    real* const mine = share + (((a_sub >> 1) * TW + l) * 2 + (a_sub & 1));  // row a_sub + 4 j: 4 j TW further on
+    real* const mine = share + (QUAD ? rollout_share_slot(quad_fetch_row(lane, NROWS), l) : rollout_share_slot(a_sub, l));  // row a_sub + 4 j: 4 j TW further on
     auto put = [&](const Raw& d) __attribute__((always_inline)) {
 #pragma unroll
       for (int j = 0; j < NLD; j++) mine[4 * j * TW] = d.r[j];
     };
-    const real2_t* const row0 = reinterpret_cast<const real2_t*>(share + 2 * l);
+    const real2_t* const row0 = reinterpret_cast<const real2_t*>(share + rollout_share_pair(0, l));
     auto get = [&](StepIn& d) __attribute__((always_inline)) {
       real rows[2 * NPAIR];
 #pragma unroll
@@ -423,7 +435,7 @@ __device__ __forceinline__ void rollout_tile(const BatchViewT<typename M::real>&
       if (ACCEPT) lds_cost[a[g] * TW + l] = total[g];
     }
   }
-  }  // if (run)
+  }  // if (run && !idle)
   if constexpr (ACCEPT) {
     __syncthreads();
     if (threadIdx.x < TW)
