@@ -201,6 +201,45 @@ class BatchILQR:
         """The same flags as int32 [B] into caller-owned device memory `ptr` (raw pointer); enqueued on the handle's stream."""
         self._check(self.lib.ilqr_copy_reset_flags_to_device(self.h, ptr))
 
+    # ---- multi-start groups (ilqr_select_best, ilqr_clone_trajectories, ilqr_clone_best, ilqr_get_clone_flags) ----
+    def select_best(self, group, ptr=None):
+        """The winner of every group of `group` consecutive trajectories (the lowest finite cost; ties: the lowest index; a group without a
+        finite cost: everyone itself) as a map: returns int32 [B] (synchronises), or with ptr -- a raw device pointer to int32 [B] --
+        writes it there, enqueued on the handle's stream, and returns None.  Reads the costs only."""
+        if ptr is not None:
+            self._check(self.lib.ilqr_select_best(self.h, int(group), None, ptr))
+            return None
+        src = np.zeros(self.B, dtype=np.int32)
+        self._check(self.lib.ilqr_select_best(self.h, int(group), _pi(src), None))
+        return src
+
+    def clone_trajectories(self, src=None, src_ptr=None, du_ptr=None):
+        """Trajectory b takes the state of trajectory src[b] (include/ilqr_amd.h: what a clone is, and the source rule: a source keeps
+        itself).  src: int [B] numpy; src_ptr: int32 [B] in device memory.  Exactly one of them.  du_ptr: float64 [B][T][nu] in device
+        memory, added to the controls of the cloned trajectories (their cost is not re-evaluated: mpc_step next).  Enqueued."""
+        if (src is None) == (src_ptr is None):
+            raise ValueError("clone_trajectories: exactly one of src and src_ptr")
+        if src is not None:
+            src = np.ascontiguousarray(src, dtype=np.int32)
+            if src.shape != (self.B,):
+                raise ValueError("clone_trajectories: src must be [B], got %s" % (src.shape,))
+        self._check(self.lib.ilqr_clone_trajectories(self.h, _pi(src), src_ptr, du_ptr))
+
+    def clone_best(self, group, du_ptr=None):
+        """select_best(group) into a buffer of the handle, then clone_trajectories by it: every group becomes copies of its best member
+        (plus du).  Enqueued on the handle's stream, nothing waited for."""
+        self._check(self.lib.ilqr_clone_best(self.h, int(group), du_ptr))
+
+    def clone_flags(self):
+        """What the last clone call did to each trajectory: int32 [B], capi.WAS_CLONED, capi.CLONE_REFUSED or 0 (synchronises)."""
+        flags = np.zeros(self.B, dtype=np.int32)
+        self._check(self.lib.ilqr_get_clone_flags(self.h, flags.ctypes.data_as(_ip)))
+        return flags
+
+    def copy_clone_flags_to_device(self, ptr):
+        """The same flags as int32 [B] into caller-owned device memory `ptr` (raw pointer); enqueued on the handle's stream."""
+        self._check(self.lib.ilqr_copy_clone_flags_to_device(self.h, ptr))
+
     def copy_controls_to_device(self, t0, n, ptr):
         """us[:, t0 : t0 + n, :] as float64 [B][n][nu] into caller-owned device memory `ptr` (raw pointer); enqueued on the handle's stream."""
         self._check(self.lib.ilqr_copy_controls_to_device(self.h, int(t0), int(n), ptr))

@@ -11,6 +11,7 @@ DTYPE_F64, DTYPE_F32 = 0, 1
 TAIL_HOLD, TAIL_ZERO = 0, 1  # enum ilqr_tail: what fills the knots a receding-horizon shift frees
 RESET_NONFINITE, RESET_LAMBDA_MAX = 1, 2  # enum ilqr_reset_rule: bits of `rules`
 WAS_MASKED, WAS_NONFINITE, WAS_LAMBDA_MAX = 1, 2, 4  # enum ilqr_reset_why: bits of a reset flag
+WAS_CLONED, CLONE_REFUSED = 1, 2  # enum ilqr_clone_why: a clone flag
 EVAL_CLAMP = 1  # enum ilqr_eval_flags: bits of ilqr_evaluate_policy's `flags`
 # enum ilqr_route (include/ilqr_amd.h): which of several equivalent kernels a handle uses; 0 = by batch size
 ROUTE_TILE_PER_CU, ROUTE_TWO_TILES_PER_CU, ROUTE_WIDE_TILES = 1, 2, 3
@@ -64,6 +65,11 @@ SYMBOLS = {
     "ilqr_mpc_step_reset": (C.c_int, [_H, _dp, C.c_void_p, C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, C.c_int]),
     "ilqr_get_reset_flags": (C.c_int, [_H, _ip]),
     "ilqr_copy_reset_flags_to_device": (C.c_int, [_H, C.c_void_p]),
+    "ilqr_select_best": (C.c_int, [_H, C.c_int, _ip, C.c_void_p]),
+    "ilqr_clone_trajectories": (C.c_int, [_H, _ip, C.c_void_p, C.c_void_p]),
+    "ilqr_clone_best": (C.c_int, [_H, C.c_int, C.c_void_p]),
+    "ilqr_get_clone_flags": (C.c_int, [_H, _ip]),
+    "ilqr_copy_clone_flags_to_device": (C.c_int, [_H, C.c_void_p]),
     "ilqr_get_value": (C.c_int, [_H, C.c_int, C.c_int, _dp, _dp]),
     "ilqr_copy_value_to_device": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ilqr_evaluate_policy": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),

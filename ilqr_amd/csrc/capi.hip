@@ -24,6 +24,7 @@
 #include "value_thread.hpp"
 #include "value_wave.hpp"
 #include "evaluate.hpp"
+#include "clone.hpp"
 
 using namespace ilqr;
 
@@ -862,6 +863,99 @@ int ilqr_get_reset_flags(ilqr_batch* h, int* flags) {
     return 0;
   }
   return scalars_to_host(h, (const int*)reset_flags(h), flags);
+}
+
+// ---- multi-start groups: the best of a group, cloned over the others (additive under ABI 6; clone.hpp) ---------------
+static int check_group(const ilqr_batch* h, int group, const char* who) {
+  REQUIRE(group >= 1 && h->B % group == 0, "%s: group %d: at least 1, and a divisor of B = %d", who, group, h->B);
+  return 0;
+}
+static int ensure_clone_ints(ilqr_batch* h) {
+  if (h->clone_ints) return 0;
+  return dev_alloc(h, &h->clone_ints, 3 * (size_t)h->Bp);
+}
+// k_select_best into d_src (int32 [B], device memory): one wavefront per group
+static int launch_select_best(ilqr_batch* h, int group, int* d_src) {
+  const int ngroups = h->B / group;
+  hipLaunchKernelGGL(k_select_best, dim3((ngroups + 3) / 4), dim3(256), 0, h->stream, (const double*)h->v.cost, h->B, group, d_src);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// k_select_clone on the map d_src (who is cloned, and the scalars), then k_clone_nominal for whom it selected
+static int select_and_clone(ilqr_batch* h, const int* d_src, const double* du) {
+  if (int rc = nominal_changes(h)) return rc;
+  if (int rc = launch_per_slot(h, k_select_clone<double>, h->v, d_src, clone_sel(h), clone_flags(h))) return rc;
+  const NominalArrays n = nominal_arrays(h);
+  CloneSet set;
+  set.arr[0] = {h->v.x0, 1, h->nx * n.lanes, nullptr};
+  for (int i = 0; i < 4; i++) set.arr[i + 1] = {n.arr[i].p, n.arr[i].S, n.arr[i].W, i == 1 ? du : nullptr};  // (du: the controls' alone)
+  set.sel = clone_sel(h);
+  set.nseg = n.nseg;  // (sel holds Bp = 16 ntiles >= B slots)
+  set.lanes = n.lanes;
+  const dim3 grid((unsigned)std::min(set.nseg, 65535), 5), block(256);
+  with_real(h, [&](auto r) {
+    hipLaunchKernelGGL(k_clone_nominal<decltype(r)>, grid, block, 0, h->stream, set);
+    return 0;
+  });
+  HIPCHK(hipGetLastError());
+  h->clone_flags_valid = true;
+  return 0;
+}
+
+int ilqr_select_best(ilqr_batch* h, int group, int* src, void* src_device) {
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  REQUIRE((src != nullptr) != (src_device != nullptr), "ilqr_select_best: exactly one of src (host) and src_device");
+  if (int rc = check_group(h, group, "ilqr_select_best")) return rc;
+  if (!h->initialised) return fail(ILQR_ERR_STATE, "select_best before ilqr_init_traj/ilqr_set_trajectory: there is no cost to compare");
+  HIPCHK(hipSetDevice(h->device));
+  if (src_device) return launch_select_best(h, group, (int*)src_device);
+  if (int rc = ensure_clone_ints(h)) return rc;
+  if (int rc = launch_select_best(h, group, clone_map(h))) return rc;
+  return scalars_to_host(h, (const int*)clone_map(h), src);
+}
+
+int ilqr_clone_trajectories(ilqr_batch* h, const int* src, const void* src_device, const void* du_device) {
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  REQUIRE((src != nullptr) != (src_device != nullptr), "ilqr_clone_trajectories: exactly one of src (host) and src_device");
+  if (!h->initialised) return fail(ILQR_ERR_STATE, "clone_trajectories before ilqr_init_traj/ilqr_set_trajectory: there is no trajectory to clone");
+  HIPCHK(hipSetDevice(h->device));
+  if (int rc = ensure_clone_ints(h)) return rc;
+  const int* d_src = (const int*)src_device;
+  if (src) {  // a host map goes to the handle's own buffer on the stream (as stage_reset_mask)
+    HIPCHK(hipMemcpyAsync(clone_map(h), src, (size_t)h->B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    d_src = clone_map(h);
+  }
+  return select_and_clone(h, d_src, (const double*)du_device);
+}
+
+int ilqr_clone_best(ilqr_batch* h, int group, const void* du_device) {
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  if (int rc = check_group(h, group, "ilqr_clone_best")) return rc;
+  if (!h->initialised) return fail(ILQR_ERR_STATE, "clone_best before ilqr_init_traj/ilqr_set_trajectory: there is no trajectory to clone");
+  HIPCHK(hipSetDevice(h->device));
+  if (int rc = ensure_clone_ints(h)) return rc;
+  if (int rc = launch_select_best(h, group, clone_map(h))) return rc;
+  return select_and_clone(h, clone_map(h), (const double*)du_device);
+}
+
+int ilqr_copy_clone_flags_to_device(ilqr_batch* h, void* flags_device) {
+  if (!h || !flags_device) return fail(ILQR_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->clone_flags_valid) {  // no clone call yet: nobody was cloned
+    HIPCHK(hipMemsetAsync(flags_device, 0, (size_t)h->B * sizeof(int), h->stream));
+    return 0;
+  }
+  HIPCHK(hipMemcpyAsync(flags_device, clone_flags(h), (size_t)h->B * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+  return 0;
+}
+int ilqr_get_clone_flags(ilqr_batch* h, int* flags) {
+  if (!h || !flags) return fail(ILQR_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->clone_flags_valid) {
+    for (int b = 0; b < h->B; b++) flags[b] = 0;
+    return 0;
+  }
+  return scalars_to_host(h, (const int*)clone_flags(h), flags);
 }
 
 // ---- the value model of the stored policy (additive under ABI 6) ---------------------------------

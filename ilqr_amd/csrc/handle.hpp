@@ -67,6 +67,9 @@ struct ilqr_batch {
   double* reset_us_stage = nullptr;  // canonical [B][T][nu]: a host u0 on its way into that layout (handles that convert)
   bool reset_us_set = false;
   bool reset_flags_valid = false;    // one of the two calls has run: the flags describe it
+  // multi-start groups (clone.hpp; ilqr_select_best, ilqr_clone_trajectories, ilqr_clone_best): allocated by the first call that needs them
+  int* clone_ints = nullptr;         // [3][Bp]: the map (a host map's copy, or the handle's own best-of-group map), the sources of the call under way, the flags of the last call
+  bool clone_flags_valid = false;    // a clone call has run: the flags describe it
   // v is the view every entry point addresses arrays through; for an fp32 handle its trajectory pointers hold
   // the addresses of FLOAT arrays (never dereferenced as double: kernels get vf, the same addresses typed float*)
   BatchView v;
@@ -132,6 +135,9 @@ struct ilqr_batch {
 static int* reset_mask_stage(ilqr_batch* h) { return h->reset_ints; }  // the three rows of reset_ints
 static int* reset_sel(ilqr_batch* h) { return h->reset_ints + h->Bp; }
 static int* reset_flags(ilqr_batch* h) { return h->reset_ints + 2 * (size_t)h->Bp; }
+static int* clone_map(ilqr_batch* h) { return h->clone_ints; }  // the three rows of clone_ints
+static int* clone_sel(ilqr_batch* h) { return h->clone_ints + h->Bp; }
+static int* clone_flags(ilqr_batch* h) { return h->clone_ints + 2 * (size_t)h->Bp; }
 static int rec_of(const ilqr_batch* h) { return rec_size(h->nx, h->nu); }
 static size_t elem_size(const ilqr_batch* h) { return h->dtype == ILQR_DTYPE_F32 ? sizeof(float) : sizeof(double); }
 // the float view of an fp32 handle: same addresses as v, typed

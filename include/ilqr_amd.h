@@ -316,6 +316,46 @@ int ilqr_mpc_step_reset(ilqr_batch* h, const double* x0, const void* x0_device, 
 int ilqr_get_reset_flags(ilqr_batch* h, int* flags);                    /* synchronises */
 int ilqr_copy_reset_flags_to_device(ilqr_batch* h, void* flags_device); /* enqueued on the handle's stream */
 
+/* ---- multi-start groups: the best trajectory of a group, cloned over the others (additive under ABI 6) ------------------------------
+ * iLQR is a local method; the usual remedy on a non-convex problem is several plans per environment (B = environments x plans, a group
+ * = G consecutive trajectories), the best of which replaces the others after every step, often with a perturbation added.  These calls
+ * do that on the device, enqueued on the handle's stream like the step itself.  Maps and flags are int32 [B] in the caller's trajectory
+ * order.  DEFINITION -- trajectory b takes the state of trajectory s = src[b] (b is CLONED) when
+ *     0 <= s < B,  s != b,  and the source keeps itself: src[s] == s or src[s] < 0;
+ * src[b] < 0 or src[b] == b: b keeps its bits (flag 0); anything else -- src[b] >= B, a source that is itself asked to change -- is REFUSED
+ * and b keeps its bits too.  The device is the one judge of a map (a map in device memory cannot be checked without waiting for it), so
+ * the same rule holds for a host map.  No source is a destination: the copy runs in place, with no scratch copy.  Cloning b from s means:
+ *     x0[b], xs[b], k[b], K[b] = the source's, bit for bit, in the handle's storage type
+ *     us[b] = us[s]                                            without du
+ *     us[b][t][e] = (storage type)((double)us[s][t][e] + du[b][t][e])      with du: canonical double [B][T][nu] in device memory; rows of
+ *                                                               trajectories that are not cloned are not read
+ *     cost, lambda, dlambda, dV, gnorm, status, iteration count, alpha index, and the divergence / backward-pass marks = the source's
+ *     flgChange[b] = 1: the derivative records stay the slot's own, so the next sweep recomputes them from the copied nominal (the bits
+ *                  the source's own records hold) instead of taking the slot's old records for them
+ * From then on b is its source: later iterations leave the two identical, bit for bit.  A perturbation du does NOT re-evaluate the stored
+ * cost or trajectory: xs, k, K and cost stay the source's, and a caller who perturbs calls ilqr_warm_start or ilqr_mpc_step next (both roll
+ * u = us + K(x - xs) out and cost again).  NOT copied, because they belong to the slot: per-trajectory model parameters
+ * (ilqr_set_trajectory_params), the reset controls (ilqr_set_reset_controls), and the derivative records -- on the record-keeping generic
+ * routes they stay what the slot's own last sweep left (as after a reset or a shift): a caller who wants ilqr_get_derivatives or
+ * ilqr_get_value of a cloned trajectory calls ilqr_compute_derivatives first.  An accepted candidate still waiting to be copied is copied
+ * first and the candidate buffers belong to nobody afterwards (as for ilqr_shift_horizon).  Any handle that stores a trajectory,
+ * ILQR_MODEL_HOST included, both dtypes.  Every refusal happens before anything is enqueued. */
+enum ilqr_clone_why { ILQR_WAS_CLONED = 1, ILQR_CLONE_REFUSED = 2 };
+/* src[b] = the winner of b's group for every b: the member with the lowest finite cost (a NaN or inf never wins; among equal costs the
+ * lowest index; a group without a finite cost maps every member to itself).  group >= 1 divides B.  Exactly one of src (host: synchronises)
+ * and src_device (int32 [B] in device memory: enqueued, nothing waited for) is non-NULL.  Reads cost only and changes nothing in the handle.
+ * ILQR_ERR_INVALID: both or neither pointer, group < 1, B % group != 0; ILQR_ERR_STATE before ilqr_init_traj / ilqr_set_trajectory. */
+int ilqr_select_best(ilqr_batch* h, int group, int* src, void* src_device);
+/* Clone by the map src (the definition above).  Exactly one of src (host; copied to a buffer of the handle on the stream) and src_device is
+ * non-NULL; du_device may be NULL.  ILQR_ERR_INVALID: both or neither map; ILQR_ERR_STATE before ilqr_init_traj / ilqr_set_trajectory. */
+int ilqr_clone_trajectories(ilqr_batch* h, const int* src, const void* src_device, const void* du_device);
+/* ilqr_select_best into a buffer of the handle, then ilqr_clone_trajectories by it (the best-of-group map always satisfies the source rule):
+ * both enqueued, no host synchronisation.  Refusals as the two calls'. */
+int ilqr_clone_best(ilqr_batch* h, int group, const void* du_device);
+/* What the LAST clone call did to each trajectory (0 = it kept its bits unasked; before any such call: all 0): int32 [B] */
+int ilqr_get_clone_flags(ilqr_batch* h, int* flags);                    /* synchronises */
+int ilqr_copy_clone_flags_to_device(ilqr_batch* h, void* flags_device); /* enqueued on the handle's stream */
+
 /* ---- the value model of the stored policy (additive under ABI 6) -------------------------------------------------------------------
  * The reference's backward pass leaves a quadratic cost-to-go model Vx[t], Vxx[t] at every knot beside the gains (members Vx, Vxx;
  * src/ilqr_core.cpp:353-354, 391-393).  The kernels here carry it in registers and drop it; these calls recompute it on the device for a

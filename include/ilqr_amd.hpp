@@ -462,6 +462,41 @@ class BatchILQR {
     return f;
   }
   void copy_reset_flags_to_device(void* flags_device) { check(ilqr_copy_reset_flags_to_device(h_, flags_device), "ilqr_copy_reset_flags_to_device"); }
+  // ---- multi-start groups (include/ilqr_amd.h: what a clone is, and the source rule) ----
+  // the winner of every group of `group` consecutive trajectories, as a map int32 [B]: returned (synchronises), or into device memory (enqueued)
+  std::vector<int> select_best(int group) {
+    if (host_) throw std::logic_error("select_best(): a host-evaluated model's nominal and cost live on the host as well");
+    std::vector<int> src((size_t)B_);
+    check(ilqr_select_best(h_, group, src.data(), nullptr), "ilqr_select_best");
+    return src;
+  }
+  void select_best(int group, void* src_device) {
+    if (host_) throw std::logic_error("select_best(): a host-evaluated model's nominal and cost live on the host as well");
+    check(ilqr_select_best(h_, group, nullptr, src_device), "ilqr_select_best");
+  }
+  // trajectory b takes the state of trajectory src[b]; du_device: double [B][T][nu] added to the cloned controls, or null (a host-evaluated
+  // model keeps host mirrors of its nominal that this would leave behind: refused, as the reset)
+  void clone_trajectories(const std::vector<int>& src, const void* du_device = nullptr) {
+    require(src.size() == (size_t)B_, "clone_trajectories: src [B]");
+    if (host_) throw std::logic_error("clone_trajectories(): a host-evaluated model's nominal lives on the host as well");
+    check(ilqr_clone_trajectories(h_, src.data(), nullptr, du_device), "ilqr_clone_trajectories");
+  }
+  void clone_trajectories(const void* src_device, const void* du_device = nullptr) {
+    if (host_) throw std::logic_error("clone_trajectories(): a host-evaluated model's nominal lives on the host as well");
+    check(ilqr_clone_trajectories(h_, nullptr, src_device, du_device), "ilqr_clone_trajectories");
+  }
+  // select_best into a buffer of the handle, then the clone by it: nothing waited for
+  void clone_best(int group, const void* du_device = nullptr) {
+    if (host_) throw std::logic_error("clone_best(): a host-evaluated model's nominal lives on the host as well");
+    check(ilqr_clone_best(h_, group, du_device), "ilqr_clone_best");
+  }
+  // what the last clone call did to each trajectory (ilqr_clone_why, 0 = it kept its bits unasked)
+  std::vector<int> clone_flags() {
+    std::vector<int> f((size_t)B_);
+    check(ilqr_get_clone_flags(h_, f.data()), "ilqr_get_clone_flags");
+    return f;
+  }
+  void copy_clone_flags_to_device(void* flags_device) { check(ilqr_copy_clone_flags_to_device(h_, flags_device), "ilqr_copy_clone_flags_to_device"); }
   // us[:, t0 : t0 + n_knots, :] as double [B][n_knots][nu] into caller-owned device memory
   void copy_controls_to_device(int t0, int n_knots, void* u_device) {
     check(ilqr_copy_controls_to_device(h_, t0, n_knots, u_device), "ilqr_copy_controls_to_device");
