@@ -422,6 +422,35 @@ class BatchILQR:
         self._check(self.lib.ilqr_evaluate_policy_on_device(self.h, int(t0), int(n), int(S), capi.EVAL_CLAMP if clamp else 0, x_ptr, cost_ptr,
                                                             x_end_ptr, u_first_ptr))
 
+    def _cov_input(self, M):
+        """[B][nx][nx] or one (nx, nx) matrix for all -> canonical [B][nx*nx], column-major per matrix (None stays None)."""
+        if M is None:
+            return None
+        M = np.broadcast_to(np.asarray(M, dtype=np.float64), (self.B, self.nx, self.nx))
+        return np.ascontiguousarray(np.swapaxes(M, -1, -2))
+
+    def covariance(self, Sigma0=None, W=None, t0=0, n=None, Su=False, expected_cost=False):
+        """The state covariance of the linearised closed loop x[t+1] - xs[t+1] = (fx + fu K)(x[t] - xs[t]) + w, w ~ (0, W), from
+        x[0] - xs[0] ~ (0, Sigma0), over the knots [t0, t0 + n) (n=None: up to knot T, up to knot T - 1 with Su): Sigma [B][n][nx][nx].
+        Sigma0, W: [B][nx][nx] or one (nx, nx) matrix for all; None = zero.  Su=True: also the covariance of the feedback controls,
+        [B][n][nu][nu]; expected_cost=True: also the expected cost above the nominal's, [B].  Returns Sigma alone, or the tuple
+        (Sigma, Su, expected_cost) without the members not asked for (include/ilqr_amd.h, ilqr_get_covariance: recomputed on the device
+        from the current records and the stored gains; synchronises)."""
+        n = self.T + (0 if Su else 1) - int(t0) if n is None else int(n)
+        S0, Wc = self._cov_input(Sigma0), self._cov_input(W)
+        Sg = np.zeros((self.B, max(n, 0), self.nx, self.nx))  # memory: column-major nx x nx
+        U = np.zeros((self.B, max(n, 0), self.nu, self.nu)) if Su else None
+        J = np.zeros(self.B) if expected_cost else None
+        self._check(self.lib.ilqr_get_covariance(self.h, int(t0), n, _p(S0), _p(Wc), _p(Sg), _p(U), _p(J)))
+        out = [np.swapaxes(Sg, -1, -2)] + ([np.swapaxes(U, -1, -2)] if Su else []) + ([J] if expected_cost else [])
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def copy_covariance_to_device(self, t0, n, Sigma0_ptr=None, W_ptr=None, Sigma_ptr=None, Su_ptr=None, expected_cost_ptr=None):
+        """The same with raw device pointers (e.g. torch.Tensor.data_ptr()) to float64 Sigma0, W [B][nx*nx] (None = zero), Sigma
+        [B][n][nx*nx], Su [B][n][nu*nu] (column-major per matrix), expected_cost [B]; any output may be None, not all three.  Enqueued on
+        the handle's stream, nothing waited for."""
+        self._check(self.lib.ilqr_copy_covariance_to_device(self.h, int(t0), int(n), Sigma0_ptr, W_ptr, Sigma_ptr, Su_ptr, expected_cost_ptr))
+
     def derivatives(self):
         n, m, B, T1 = self.nx, self.nu, self.B, self.T + 1
         mem = dict(fx=np.zeros((B, T1, n, n)), fu=np.zeros((B, T1, m, n)), cx=np.zeros((B, T1, n)),

@@ -72,6 +72,8 @@ SYMBOLS = {
     "ilqr_copy_clone_flags_to_device": (C.c_int, [_H, C.c_void_p]),
     "ilqr_get_value": (C.c_int, [_H, C.c_int, C.c_int, _dp, _dp]),
     "ilqr_copy_value_to_device": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "ilqr_get_covariance": (C.c_int, [_H, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "ilqr_copy_covariance_to_device": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ilqr_evaluate_policy": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
     "ilqr_evaluate_policy_on_device": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ilqr_trajectory_params_count": (C.c_int, []),

@@ -23,6 +23,8 @@
 #include "kernels.hpp"
 #include "value_thread.hpp"
 #include "value_wave.hpp"
+#include "covariance_thread.hpp"
+#include "covariance_wave.hpp"
 #include "evaluate.hpp"
 #include "clone.hpp"
 
@@ -996,6 +998,52 @@ int ilqr_get_value(ilqr_batch* h, int t0, int n_knots, double* Vx, double* Vxx) 
   if (int rc = run_value(h, t0, n_knots, d_vx, d_vxx, "ilqr_get_value")) return rc;
   if (Vx) HIPCHK(hipMemcpyAsync(Vx, d_vx, n_vx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (Vxx) HIPCHK(hipMemcpyAsync(Vxx, d_vxx, n_vxx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// ---- the closed-loop covariance of the stored policy (additive under ABI 6; covariance_wave.hpp) ------
+// every refusal the two calls share -- before anything is enqueued --, then the records as ilqr_get_derivatives would return them now
+static int prepare_covariance(ilqr_batch* h, int t0, int n_knots, const void* Sigma, const void* Su, const void* expected_cost, const char* who) {
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  REQUIRE(t0 >= 0 && n_knots >= 1 && t0 <= h->T && n_knots <= h->T + 1 - t0, "%s: window [%d, %d): inside [0, T = %d], at least one knot", who, t0, t0 + n_knots, h->T);
+  REQUIRE(!Su || n_knots <= h->T - t0, "%s: window [%d, %d) with Su: knot T = %d has no control", who, t0, t0 + n_knots, h->T);
+  REQUIRE(Sigma || Su || expected_cost, "%s: Sigma, Su and expected_cost are all null", who);
+  if (!h->initialised) return fail(ILQR_ERR_STATE, "%s before ilqr_init_traj/ilqr_set_trajectory: no policy is stored", who);
+  HIPCHK(hipSetDevice(h->device));
+  return materialise_records(h);
+}
+static int run_covariance(ilqr_batch* h, const CovArgs& q, const char* who) {
+  const char* kernel = "";
+  const int rc = launch_covariance(h, q, &kernel);
+  return name_refused_kernel(rc, who, kernel);
+}
+
+int ilqr_copy_covariance_to_device(ilqr_batch* h, int t0, int n_knots, const void* Sigma0_device, const void* W_device, void* Sigma_device,
+                                   void* Su_device, void* expected_cost_device) {
+  const char* who = "ilqr_copy_covariance_to_device";
+  if (int rc = prepare_covariance(h, t0, n_knots, Sigma_device, Su_device, expected_cost_device, who)) return rc;
+  return run_covariance(h, {t0, n_knots, (const double*)Sigma0_device, (const double*)W_device, (double*)Sigma_device, (double*)Su_device, (double*)expected_cost_device}, who);
+}
+
+int ilqr_get_covariance(ilqr_batch* h, int t0, int n_knots, const double* Sigma0, const double* W, double* Sigma, double* Su, double* expected_cost) {
+  const char* who = "ilqr_get_covariance";
+  if (int rc = prepare_covariance(h, t0, n_knots, Sigma, Su, expected_cost, who)) return rc;
+  // a call-sized device buffer (the staging buffer: Sigma0, W, then the outputs asked for), copied out and waited for
+  const size_t nn = (size_t)h->B * h->nx * h->nx;
+  const size_t n_s0 = Sigma0 ? nn : 0, n_w = W ? nn : 0, n_s = Sigma ? nn * n_knots : 0, n_u = Su ? (size_t)h->B * n_knots * h->nu * h->nu : 0, n_j = expected_cost ? h->B : 0;
+  if (int rc = ensure_staging(h, n_s0 + n_w + n_s + n_u + n_j)) return rc;
+  double* const d_s0 = Sigma0 ? h->staging : nullptr;
+  double* const d_w = W ? h->staging + n_s0 : nullptr;
+  double* const d_s = Sigma ? h->staging + n_s0 + n_w : nullptr;
+  double* const d_u = Su ? h->staging + n_s0 + n_w + n_s : nullptr;
+  double* const d_j = expected_cost ? h->staging + n_s0 + n_w + n_s + n_u : nullptr;
+  if (Sigma0) HIPCHK(hipMemcpyAsync(d_s0, Sigma0, n_s0 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (W) HIPCHK(hipMemcpyAsync(d_w, W, n_w * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (int rc = run_covariance(h, {t0, n_knots, d_s0, d_w, d_s, d_u, d_j}, who)) return rc;
+  if (Sigma) HIPCHK(hipMemcpyAsync(Sigma, d_s, n_s * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (Su) HIPCHK(hipMemcpyAsync(Su, d_u, n_u * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (expected_cost) HIPCHK(hipMemcpyAsync(expected_cost, d_j, n_j * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }

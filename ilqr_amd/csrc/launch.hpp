@@ -421,6 +421,34 @@ static int launch_value(ilqr_batch* h, int t0, int nk, double* Vx, double* Vxx, 
   return 0;
 }
 
+// The closed-loop covariance of the stored policy (ilqr_get_covariance / ilqr_copy_covariance_to_device; covariance_wave.hpp,
+// covariance_thread.hpp): as launch_value, picked by the handle's layout and sizes alone -- no route bit, no stage timer.  The caller
+// has materialised the records and checked the window.
+static int launch_covariance(ilqr_batch* h, const CovArgs& q, const char** name) {
+  const WaveVariant w = value_wave_variant(h->nx, h->nu, h->dtype);
+  *name = covariance_kernel_name(h->aos, w);
+  if (!h->aos) {
+    const dim3 grid(h->Bp / 64), block(64);
+    if (int rc = with_model(h, [&](auto& v, auto& m, auto&) {
+          hipLaunchKernelGGL((k_covariance_t<std::decay_t<decltype(m)>>), grid, block, 0, h->stream, v, q);
+          return 0;
+        }))
+      return rc;
+  } else if (int rc = with_int<1, 2>(w.nt, [&](auto nt) { return with_int<1, 2>(w.mt, [&](auto mt) { return with_bool(w.f32, [&](auto f32) {
+               constexpr int MT = decltype(mt)::value;
+               using S = std::conditional_t<decltype(f32)::value, float, double>;
+               if constexpr (MT == 2 && decltype(f32)::value) {  // float storage: never with two control tiles (ilqr_create)
+                 return fail(ILQR_ERR_UNSUPPORTED, "%s: no fp32 handle has more than %d controls", *name, WM);
+               } else {
+                 hipLaunchKernelGGL((k_covariance_w<decltype(nt)::value, MT, S>), dim3(h->B), dim3(64), 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
+                 return 0;
+               }
+             }); }); }))
+    return rc;
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // The stored policy applied to caller-given states (ilqr_evaluate_policy / _on_device; evaluate.hpp): picked by the handle's layout alone,
 // as launch_value -- no route bit, no stage timer.  One thread per rollout, B * S of them (the caller has checked that they fit an int).
 static int launch_evaluate(ilqr_batch* h, const EvalArgs& e, const char** name) {

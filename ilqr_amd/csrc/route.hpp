@@ -52,6 +52,10 @@ inline const char* value_kernel_name(bool aos, const WaveVariant& w) {
   static const char* const kWave[2][2] = {{"k_value_w<1, 1>", "k_value_w<1, 2>"}, {"k_value_w<2, 1>", "k_value_w<2, 2>"}};
   return aos ? kWave[w.nt - 1][w.mt - 1] : "k_value_t";
 }
+inline const char* covariance_kernel_name(bool aos, const WaveVariant& w) {  // k_covariance_w: the variants value_wave_variant yields
+  static const char* const kWave[2][2] = {{"k_covariance_w<1, 1>", "k_covariance_w<1, 2>"}, {"k_covariance_w<2, 1>", "k_covariance_w<2, 2>"}};
+  return aos ? kWave[w.nt - 1][w.mt - 1] : "k_covariance_t";
+}
 inline const char* evaluate_kernel_name(bool aos, bool traj_params) { return !aos ? "k_evaluate_t" : traj_params ? "k_evaluate_g<PT>" : "k_evaluate_g"; }
 
 struct RouteInputs {

@@ -381,6 +381,40 @@ int ilqr_get_value(ilqr_batch* h, int t0, int n_knots, double* Vx, double* Vxx);
 /* into caller-owned device memory of this handle's device: enqueued on the handle's stream, not waited for (as ilqr_copy_gains_to_device) */
 int ilqr_copy_value_to_device(ilqr_batch* h, int t0, int n_knots, void* Vx_device, void* Vxx_device);
 
+/* ---- the closed-loop covariance of the stored policy (additive under ABI 6) --------------------------------------------------------
+ * The forward twin of the value model: how far the closed loop u = us[t] + K[t](x - xs[t]) drifts from the nominal under an uncertain
+ * initial state and additive process noise, knot by knot, and what that costs in expectation -- the linear-Gaussian part (the G) of iLQG,
+ * which the reference does not have.  DEFINITION -- from the derivative records ilqr_get_derivatives would return at this moment (see
+ * there for which trajectory they describe) and the stored gains K; k, us and xs are not read:
+ *     Sigma[0] = Sigma0[b]                                                  (as given, not symmetrised; NULL = zero)
+ *     t = 0 .. T-1:   A     = fx[t] + fu[t] K[t]
+ *                     Z     = Sigma[t] K[t]'                                (n x m)
+ *                     Su[t] = sym(K[t] Z)                                   (m x m;  sym(M) = (M + M')/2)
+ *                     J    += 1/2 (<cxx[t], Sigma[t]> + <cuu[t], Su[t]> + 2 <cxu[t], Z>)     (<,> = sum of elementwise products)
+ *                     Sigma[t+1] = sym(A Sigma[t] A' + W[b])                (W NULL = zero)
+ *     J += 1/2 <cxx[T], Sigma[T]>
+ * Sigma[t] is the covariance of x[t] - xs[t], Su[t] that of the feedback part of u[t], J the expected cost above the nominal's, to
+ * second order.  What this is NOT: it is the covariance of the LINEARISED closed loop about the nominal.  Rows of K that the box-QP
+ * zeroed (clamped controls) are in K already, but saturation of the feedback itself is not modelled -- Su[t] beside the control box tells
+ * how likely it is.  Noise enters through the state only and is the same at every knot.  A pure function of (records, K, Sigma0, W);
+ * by the identity J = 1/2 <Vxx[0], Sigma0> + 1/2 sum_t <Vxx[t+1], W> it agrees with ilqr_get_value.
+ * The recursion runs in double on every handle (an fp32 handle's stored float records and gains are widened); every array is canonical
+ * double on every handle, matrices column-major:
+ *     Sigma0, W [B][nx*nx]     Sigma [B][n_knots][nx*nx]     Su [B][n_knots][nu*nu]     expected_cost [B]
+ * Only the window [t0, t0 + n_knots) of Sigma and Su is stored: it lies inside [0, T] and holds at least one knot; with Su requested it
+ * lies inside [0, T) (knot T has no control).  The recursion runs from knot 0 to the last knot anything needs: T when expected_cost is
+ * requested, else t0 + n_knots - 1.  Any output may be NULL, not all three.  Every model, ILQR_MODEL_HOST included (its records are what
+ * the caller set), both dtypes.  The call leaves the handle as ilqr_get_derivatives at the same point does: later iterations are bit for
+ * bit those of a handle that never asked.
+ * ILQR_ERR_INVALID: a bad window, a window with knot T when Su is requested, three NULL outputs; ILQR_ERR_STATE: before ilqr_init_traj /
+ * ilqr_set_trajectory.  Every refusal happens before anything is enqueued. */
+/* host arrays: a call-sized device buffer takes Sigma0 / W up and the window down; synchronises */
+int ilqr_get_covariance(ilqr_batch* h, int t0, int n_knots, const double* Sigma0, const double* W, double* Sigma, double* Su,
+                        double* expected_cost);
+/* device memory of this handle's device: enqueued on the handle's stream, nothing waited for (as ilqr_copy_value_to_device) */
+int ilqr_copy_covariance_to_device(ilqr_batch* h, int t0, int n_knots, const void* Sigma0_device, const void* W_device, void* Sigma_device,
+                                   void* Su_device, void* expected_cost_device);
+
 /* ---- the stored feedback policy applied to caller-given states (additive under ABI 6) -----------------------------------------------
  * What a solve leaves for a controller is the time-varying law u = us[t] + K[t](x - xs[t]).  These calls apply it to states the CALLER
  * holds -- n_samples of them per trajectory, at knot t0 -- and roll it through the handle's device model for n_knots knots; a read-only

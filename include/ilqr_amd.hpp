@@ -379,6 +379,27 @@ class BatchILQR {
   void copy_value_to_device(int t0, int n_knots, void* Vx_device, void* Vxx_device) {
     check(ilqr_copy_value_to_device(h_, t0, n_knots, Vx_device, Vxx_device), "ilqr_copy_value_to_device");
   }
+  // The covariance of the linearised closed loop about the nominal (ilqr_get_covariance) over the knots [t0, t0 + n_knots), n_knots < 0:
+  // up to knot T (up to knot T - 1 when Su is asked for).  Sigma0, W [B][nx*nx] (null = zero); Sigma [B][n_knots][nx*nx], Su
+  // [B][n_knots][nu*nu] (column-major per matrix), expected_cost [B]; any output may be null, not all three.
+  void covariance(const std::vector<double>* Sigma0, const std::vector<double>* W, std::vector<double>* Sigma, std::vector<double>* Su,
+                  std::vector<double>* expected_cost, int t0 = 0, int n_knots = -1) {
+    if (n_knots < 0) n_knots = T_ + (Su ? 0 : 1) - t0;
+    const size_t mat = (size_t)B_ * n_ * n_, knots = (size_t)B_ * (n_knots > 0 ? n_knots : 0);
+    if ((Sigma0 && Sigma0->size() != mat) || (W && W->size() != mat)) throw std::invalid_argument("covariance(): Sigma0 and W are [B][nx*nx]");
+    if (Sigma) Sigma->assign(knots * n_ * n_, 0.0);
+    if (Su) Su->assign(knots * m_ * m_, 0.0);
+    if (expected_cost) expected_cost->assign(B_, 0.0);
+    check(ilqr_get_covariance(h_, t0, n_knots, Sigma0 ? Sigma0->data() : nullptr, W ? W->data() : nullptr, Sigma ? Sigma->data() : nullptr,
+                              Su ? Su->data() : nullptr, expected_cost ? expected_cost->data() : nullptr),
+          "ilqr_get_covariance");
+  }
+  // ... or from and into caller-owned device memory, on the handle's stream, nothing waited for
+  void copy_covariance_to_device(int t0, int n_knots, const void* Sigma0_device, const void* W_device, void* Sigma_device, void* Su_device,
+                                 void* expected_cost_device) {
+    check(ilqr_copy_covariance_to_device(h_, t0, n_knots, Sigma0_device, W_device, Sigma_device, Su_device, expected_cost_device),
+          "ilqr_copy_covariance_to_device");
+  }
   // The stored feedback policy u = us[t] + K[t](x - xs[t]) applied to the caller's states at knot t0 and rolled through the device model for
   // n_knots knots (n_knots < 0: up to knot T; ilqr_evaluate_policy): x [B][S][nx], S = n_samples states per trajectory; cost [B][S], x_end
   // [B][S][nx], u_first [B][S][nu]; any output pointer may be null, not all three.  A read-only query of the handle.
@@ -977,6 +998,38 @@ class iLQR {
       for (int j = 0; j < n; j++)
         for (int a = 0; a < n; a++) Vxx[t](a, j) = vxx[(size_t)t * n * n + a + (size_t)n * j];
     }
+  }
+  // The covariance of the linearised closed loop about the nominal over the knots [t0, t0 + n_knots), n_knots < 0: up to knot T (up to
+  // knot T - 1 when Su is asked for): Sigma[t] of x[t] - xs[t] from x[0] - xs[0] ~ (0, Sigma0) and process noise ~ (0, W) at every knot
+  // (an empty matrix = zero); Su[t] of the feedback controls and the expected cost above the nominal's if asked for (ilqr_get_covariance)
+  void covariance(const MatrixXd& Sigma0, const MatrixXd& W, VecOfMatXd& Sigma, VecOfMatXd* Su = nullptr, double* expected_cost = nullptr,
+                  int t0 = 0, int n_knots = -1) const {
+    if (!engine_) throw std::logic_error("covariance(): no trajectory initialised");
+    const int n = model->x_dims, m = model->u_dims;
+    if (n_knots < 0) n_knots = T + (Su ? 0 : 1) - t0;
+    auto flat = [n](const MatrixXd& M, std::vector<double>& out) {
+      if (M.rows() == 0 && M.cols() == 0) return false;
+      if (M.rows() != n || M.cols() != n) throw std::invalid_argument("covariance(): Sigma0 and W are nx x nx, or empty");
+      out.resize((size_t)n * n);
+      for (int j = 0; j < n; j++)
+        for (int a = 0; a < n; a++) out[a + (size_t)n * j] = M(a, j);
+      return true;
+    };
+    auto mats = [](const std::vector<double>& a, int S, int E) {
+      VecOfMatXd out(S);
+      for (int t = 0; t < S; t++) {
+        out[t] = MatrixXd(E, E);
+        for (int j = 0; j < E; j++)
+          for (int r = 0; r < E; r++) out[t](r, j) = a[(size_t)t * E * E + r + (size_t)E * j];
+      }
+      return out;
+    };
+    std::vector<double> s0, w, sg, su, j;
+    const bool has_s0 = flat(Sigma0, s0), has_w = flat(W, w);
+    engine_->covariance(has_s0 ? &s0 : nullptr, has_w ? &w : nullptr, &sg, Su ? &su : nullptr, expected_cost ? &j : nullptr, t0, n_knots);
+    Sigma = mats(sg, n_knots, n);
+    if (Su) *Su = mats(su, n_knots, m);
+    if (expected_cost) *expected_cost = j[0];
   }
   // the control the stored policy gives at knot t in the state x: us[t] + K[t](x - xs[t]), evaluated on the device (ilqr_evaluate_policy, one knot)
   VectorXd feedback_control(int t, const VectorXd& x) const {
