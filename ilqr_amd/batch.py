@@ -451,6 +451,74 @@ class BatchILQR:
         the handle's stream, nothing waited for."""
         self._check(self.lib.ilqr_copy_covariance_to_device(self.h, int(t0), int(n), Sigma0_ptr, W_ptr, Sigma_ptr, Su_ptr, expected_cost_ptr))
 
+    def _dirs_input(self, a, lead, width, what):
+        """[B] + lead + [S][width], or without the direction axis (one direction) -> (canonical array or None, S, one direction?)"""
+        if a is None:
+            return None, None, False
+        a = _c(a)
+        flat = a.ndim == 2 + len(lead)
+        if flat:
+            a = np.ascontiguousarray(a[..., None, :])
+        if a.ndim != 3 + len(lead) or a.shape[:1 + len(lead)] != (self.B,) + lead or a.shape[-1] != width or a.shape[-2] < 1:
+            raise ValueError("%s must be %s, or the same without the direction axis S; got %s" % (what, ["B"] + list(lead) + ["S", width], a.shape))
+        return a, a.shape[-2], flat
+
+    def _dirs_pair(self, x, u, what):
+        (x, Sx, fx), (u, Su, fu) = x, u
+        if x is None and u is None:
+            raise ValueError("%s are both None: the answer would be zero" % what)
+        if x is not None and u is not None and (Sx != Su or fx != fu):
+            raise ValueError("%s disagree on the directions: %s and %s" % (what, x.shape, u.shape))
+        return (Sx if x is not None else Su), (fx if x is not None else fu)
+
+    def _nku(self, t0, n):
+        return max(min(int(t0) + n, self.T) - int(t0), 0)
+
+    def tangent(self, dx0=None, dv=None, t0=0, n=None):
+        """The tangent (Jacobian-vector product) of the linearised closed loop du[t] = K[t] dx[t] + dv[t], dx[t+1] = fx[t] dx[t] + fu[t] du[t]
+        over the knots [t0, t0 + n) (n=None: up to knot T).  dx0: [B][S][nx], S directions per trajectory, perturbs the measured state;
+        dv: [B][T][S][nu] perturbs the stored controls over the whole horizon; None = zero, not both.  Returns (dxs [B][n][S][nx],
+        dus [B][nku][S][nu]), nku the window's knots that have a control.  A [B][nx] / [B][T][nu] input is one direction and the direction
+        axis is dropped again on output (include/ilqr_amd.h, ilqr_get_tangent: recomputed on the device from the current records and the
+        stored gains; synchronises)."""
+        n = self.T + 1 - int(t0) if n is None else int(n)
+        X, V = self._dirs_input(dx0, (), self.nx, "dx0"), self._dirs_input(dv, (self.T,), self.nu, "dv")
+        S, flat = self._dirs_pair(X, V, "dx0 and dv")
+        nku = self._nku(t0, n)
+        dxs = np.zeros((self.B, max(n, 0), S, self.nx))
+        dus = np.zeros((self.B, nku, S, self.nu))
+        self._check(self.lib.ilqr_get_tangent(self.h, int(t0), n, S, _p(X[0]), _p(V[0]), _p(dxs), _p(dus) if nku else None))
+        return (dxs[:, :, 0], dus[:, :, 0]) if flat else (dxs, dus)
+
+    def adjoint(self, gx=None, gu=None, t0=0, n=None):
+        """The adjoint (vector-Jacobian product) of the same map: gx [B][n][S][nx] = dL/dxs and gu [B][nku][S][nu] = dL/dus of a caller's
+        loss over the knots [t0, t0 + n) (n=None: up to knot T; None = zero, not both).  Returns (g_x0 [B][S][nx] = dL/dx0, g_v [B][T][S][nu] =
+        dL/dv, zero after the window).  A [B][n][nx] / [B][nku][nu] input is one direction and the direction axis is dropped again on output
+        (include/ilqr_amd.h, ilqr_get_adjoint; synchronises)."""
+        n = self.T + 1 - int(t0) if n is None else int(n)
+        nku = self._nku(t0, n)
+        X, U = self._dirs_input(gx, (max(n, 0),), self.nx, "gx"), self._dirs_input(gu, (nku,), self.nu, "gu")
+        S, flat = self._dirs_pair(X, U, "gx and gu")
+        g_x0, g_v = np.zeros((self.B, S, self.nx)), np.zeros((self.B, self.T, S, self.nu))
+        self._check(self.lib.ilqr_get_adjoint(self.h, int(t0), n, S, _p(X[0]), _p(U[0]), _p(g_x0), _p(g_v)))
+        return (g_x0[:, 0], g_v[:, :, 0]) if flat else (g_x0, g_v)
+
+    def transition_matrices(self, t0=0, n=None):
+        """The tangent of dx0 = I: (Phi [B][n][nx][nx], KPhi [B][nku][nu][nx]) with dx[t] = Phi[t] dx[0] and du[t] = KPhi[t] dx[0] = K[t] Phi[t]
+        dx[0], the first-order change of the whole plan with the measured state (the Gauss-Newton sensitivity of a converged plan)."""
+        dxs, dus = self.tangent(dx0=np.broadcast_to(np.eye(self.nx), (self.B, self.nx, self.nx)), t0=t0, n=n)
+        return np.swapaxes(dxs, -1, -2), np.swapaxes(dus, -1, -2)
+
+    def copy_tangent_to_device(self, t0, n, S, dx0_ptr=None, dv_ptr=None, dxs_ptr=None, dus_ptr=None):
+        """The tangent with raw device pointers (e.g. torch.Tensor.data_ptr()) to float64 dx0 [B][S][nx], dv [B][T][S][nu] (None = zero, not
+        both), dxs [B][n][S][nx], dus [B][nku][S][nu] (either may be None, not both).  Enqueued on the handle's stream, nothing waited for."""
+        self._check(self.lib.ilqr_copy_tangent_to_device(self.h, int(t0), int(n), int(S), dx0_ptr, dv_ptr, dxs_ptr, dus_ptr))
+
+    def copy_adjoint_to_device(self, t0, n, S, gx_ptr=None, gu_ptr=None, g_x0_ptr=None, g_v_ptr=None):
+        """The adjoint with raw device pointers to float64 gx [B][n][S][nx], gu [B][nku][S][nu] (None = zero, not both), g_x0 [B][S][nx],
+        g_v [B][T][S][nu] (either may be None, not both).  Enqueued on the handle's stream, nothing waited for."""
+        self._check(self.lib.ilqr_copy_adjoint_to_device(self.h, int(t0), int(n), int(S), gx_ptr, gu_ptr, g_x0_ptr, g_v_ptr))
+
     def derivatives(self):
         n, m, B, T1 = self.nx, self.nu, self.B, self.T + 1
         mem = dict(fx=np.zeros((B, T1, n, n)), fu=np.zeros((B, T1, m, n)), cx=np.zeros((B, T1, n)),

@@ -74,6 +74,10 @@ SYMBOLS = {
     "ilqr_copy_value_to_device": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ilqr_get_covariance": (C.c_int, [_H, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "ilqr_copy_covariance_to_device": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ilqr_get_tangent": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "ilqr_copy_tangent_to_device": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ilqr_get_adjoint": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "ilqr_copy_adjoint_to_device": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ilqr_evaluate_policy": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
     "ilqr_evaluate_policy_on_device": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ilqr_trajectory_params_count": (C.c_int, []),

@@ -25,6 +25,8 @@
 #include "value_wave.hpp"
 #include "covariance_thread.hpp"
 #include "covariance_wave.hpp"
+#include "sensitivity_thread.hpp"
+#include "sensitivity_wave.hpp"
 #include "evaluate.hpp"
 #include "clone.hpp"
 
@@ -1046,6 +1048,106 @@ int ilqr_get_covariance(ilqr_batch* h, int t0, int n_knots, const double* Sigma0
   if (expected_cost) HIPCHK(hipMemcpyAsync(expected_cost, d_j, n_j * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
+}
+
+// ---- the tangent and the adjoint of the stored closed loop (additive under ABI 6; sensitivity_wave.hpp) ------
+// every refusal the four calls share -- before anything is enqueued --, then the records as ilqr_get_derivatives would return them now.
+// in_x, in_u: the two inputs (dx0, dv / gx, gu), not both null; out_x, out_u: the two outputs, not both null; `windowed_u`: the
+// control-sized array that covers the window's nku knots (dus / gu) and so cannot exist when nku == 0.
+static int prepare_sensitivity(ilqr_batch* h, int t0, int n_knots, int n_dirs, const void* in_x, const void* in_u, const void* out_x, const void* out_u,
+                               const void* windowed_u, const char* in_names, const char* out_names, const char* windowed_name, const char* who) {
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  REQUIRE(t0 >= 0 && n_knots >= 1 && t0 <= h->T && n_knots <= h->T + 1 - t0, "%s: window [%d, %d): inside [0, T = %d], at least one knot", who, t0, t0 + n_knots, h->T);
+  REQUIRE(n_dirs >= 1, "%s: n_dirs %d must be >= 1", who, n_dirs);
+  const long long widest = (long long)h->B * (h->T + 1) * n_dirs * std::max(h->nx, h->nu);
+  REQUIRE(widest <= (long long)INT_MAX, "%s: B * (T + 1) * n_dirs * max(nx, nu) = %lld elements do not fit an int", who, widest);
+  REQUIRE(in_x || in_u, "%s: %s are both null: the answer would be zero", who, in_names);
+  REQUIRE(out_x || out_u, "%s: %s are both null", who, out_names);
+  REQUIRE(!windowed_u || t0 < h->T, "%s: window [%d, %d) with %s: knot T = %d has no control", who, t0, t0 + n_knots, windowed_name, h->T);
+  if (!h->initialised) return fail(ILQR_ERR_STATE, "%s before ilqr_init_traj/ilqr_set_trajectory: no policy is stored", who);
+  HIPCHK(hipSetDevice(h->device));
+  return materialise_records(h);
+}
+static int prepare_tangent(ilqr_batch* h, int t0, int n_knots, int n_dirs, const void* dx0, const void* dv, const void* dxs, const void* dus, const char* who) {
+  return prepare_sensitivity(h, t0, n_knots, n_dirs, dx0, dv, dxs, dus, dus, "dx0 and dv", "dxs and dus", "dus", who);
+}
+static int prepare_adjoint(ilqr_batch* h, int t0, int n_knots, int n_dirs, const void* gx, const void* gu, const void* g_x0, const void* g_v, const char* who) {
+  return prepare_sensitivity(h, t0, n_knots, n_dirs, gx, gu, g_x0, g_v, gu, "gx and gu", "g_x0 and g_v", "gu", who);
+}
+static int run_tangent(ilqr_batch* h, const TangentArgs& q, const char* who) {
+  const char* kernel = "";
+  const int rc = launch_tangent(h, q, &kernel);
+  return name_refused_kernel(rc, who, kernel);
+}
+static int run_adjoint(ilqr_batch* h, const AdjointArgs& q, const char* who) {
+  const char* kernel = "";
+  const int rc = launch_adjoint(h, q, &kernel);
+  return name_refused_kernel(rc, who, kernel);
+}
+// the element counts of the four arrays of a call: state-sized over one knot, control-sized over the horizon, state-sized over the
+// window, control-sized over the window's knots with a control (tangent: dx0, dv, dxs, dus; adjoint: g_x0, g_v, gx, gu)
+struct SensSizes {
+  size_t x_one, u_all, x_win, u_win;
+};
+static SensSizes sensitivity_sizes(const ilqr_batch* h, int t0, int n_knots, int n_dirs) {
+  const size_t per_x = (size_t)h->B * n_dirs * h->nx, per_u = (size_t)h->B * n_dirs * h->nu;
+  return {per_x, per_u * h->T, per_x * n_knots, per_u * (std::min(t0 + n_knots, h->T) - t0)};
+}
+// a call-sized device buffer (the staging buffer: the two inputs, then the two outputs): the inputs copied up before the kernel ...
+struct SensStaging {
+  double *in_a, *in_b, *out_a, *out_b;
+  size_t n_out_a, n_out_b;
+};
+static int stage_sensitivity_up(ilqr_batch* h, const double* in_a, size_t n_in_a, const double* in_b, size_t n_in_b, bool want_a, size_t n_out_a, bool want_b,
+                                size_t n_out_b, SensStaging* s) {
+  n_in_a = in_a ? n_in_a : 0, n_in_b = in_b ? n_in_b : 0, n_out_a = want_a ? n_out_a : 0, n_out_b = want_b ? n_out_b : 0;
+  if (int rc = ensure_staging(h, n_in_a + n_in_b + n_out_a + n_out_b)) return rc;
+  *s = {in_a ? h->staging : nullptr, in_b ? h->staging + n_in_a : nullptr, want_a ? h->staging + n_in_a + n_in_b : nullptr,
+        want_b ? h->staging + n_in_a + n_in_b + n_out_a : nullptr, n_out_a, n_out_b};
+  if (in_a) HIPCHK(hipMemcpyAsync(s->in_a, in_a, n_in_a * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (in_b) HIPCHK(hipMemcpyAsync(s->in_b, in_b, n_in_b * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  return 0;
+}
+// ... and the outputs copied out and waited for after it
+static int stage_sensitivity_down(ilqr_batch* h, const SensStaging& s, double* out_a, double* out_b) {
+  if (out_a) HIPCHK(hipMemcpyAsync(out_a, s.out_a, s.n_out_a * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (out_b) HIPCHK(hipMemcpyAsync(out_b, s.out_b, s.n_out_b * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int ilqr_copy_tangent_to_device(ilqr_batch* h, int t0, int n_knots, int n_dirs, const void* dx0_device, const void* dv_device, void* dxs_device,
+                                void* dus_device) {
+  const char* who = "ilqr_copy_tangent_to_device";
+  if (int rc = prepare_tangent(h, t0, n_knots, n_dirs, dx0_device, dv_device, dxs_device, dus_device, who)) return rc;
+  return run_tangent(h, {t0, n_knots, n_dirs, (const double*)dx0_device, (const double*)dv_device, (double*)dxs_device, (double*)dus_device}, who);
+}
+
+int ilqr_get_tangent(ilqr_batch* h, int t0, int n_knots, int n_dirs, const double* dx0, const double* dv, double* dxs, double* dus) {
+  const char* who = "ilqr_get_tangent";
+  if (int rc = prepare_tangent(h, t0, n_knots, n_dirs, dx0, dv, dxs, dus, who)) return rc;
+  const SensSizes n = sensitivity_sizes(h, t0, n_knots, n_dirs);
+  SensStaging d;
+  if (int rc = stage_sensitivity_up(h, dx0, n.x_one, dv, n.u_all, dxs != nullptr, n.x_win, dus != nullptr, n.u_win, &d)) return rc;
+  if (int rc = run_tangent(h, {t0, n_knots, n_dirs, d.in_a, d.in_b, d.out_a, d.out_b}, who)) return rc;
+  return stage_sensitivity_down(h, d, dxs, dus);
+}
+
+int ilqr_copy_adjoint_to_device(ilqr_batch* h, int t0, int n_knots, int n_dirs, const void* gx_device, const void* gu_device, void* g_x0_device,
+                                void* g_v_device) {
+  const char* who = "ilqr_copy_adjoint_to_device";
+  if (int rc = prepare_adjoint(h, t0, n_knots, n_dirs, gx_device, gu_device, g_x0_device, g_v_device, who)) return rc;
+  return run_adjoint(h, {t0, n_knots, n_dirs, (const double*)gx_device, (const double*)gu_device, (double*)g_x0_device, (double*)g_v_device}, who);
+}
+
+int ilqr_get_adjoint(ilqr_batch* h, int t0, int n_knots, int n_dirs, const double* gx, const double* gu, double* g_x0, double* g_v) {
+  const char* who = "ilqr_get_adjoint";
+  if (int rc = prepare_adjoint(h, t0, n_knots, n_dirs, gx, gu, g_x0, g_v, who)) return rc;
+  const SensSizes n = sensitivity_sizes(h, t0, n_knots, n_dirs);
+  SensStaging d;
+  if (int rc = stage_sensitivity_up(h, gx, n.x_win, gu, n.u_win, g_x0 != nullptr, n.x_one, g_v != nullptr, n.u_all, &d)) return rc;
+  if (int rc = run_adjoint(h, {t0, n_knots, n_dirs, d.in_a, d.in_b, d.out_a, d.out_b}, who)) return rc;
+  return stage_sensitivity_down(h, d, g_x0, g_v);
 }
 
 // ---- the stored policy applied to caller-given states (additive under ABI 6; evaluate.hpp) ------

@@ -449,6 +449,53 @@ static int launch_covariance(ilqr_batch* h, const CovArgs& q, const char** name)
   return 0;
 }
 
+// The tangent and the adjoint of the stored closed loop (ilqr_get_tangent / ilqr_get_adjoint and their device forms; sensitivity_wave.hpp,
+// sensitivity_thread.hpp): as launch_covariance, picked by the handle's layout and sizes alone -- no route bit, no stage timer.  The
+// caller has materialised the records, checked the window and that B * n_dirs fits an int.  Generic layout: one wavefront per
+// (trajectory, 16 directions); tiled layout: one thread per (trajectory, direction), the direction by block.
+template <class Args, class Tiled, class Wave>
+static int launch_sensitivity(ilqr_batch* h, const Args& q, const char* kernel_name, Tiled&& tiled, Wave&& wave) {
+  const WaveVariant w = value_wave_variant(h->nx, h->nu, h->dtype);
+  if (!h->aos) {
+    const dim3 grid((unsigned)(h->Bp / 64) * (unsigned)q.nd), block(64);
+    if (int rc = with_model(h, [&](auto& v, auto& m, auto&) {
+          tiled(v, m, grid, block);
+          return 0;
+        }))
+      return rc;
+  } else if (int rc = with_int<1, 2>(w.nt, [&](auto nt) { return with_int<1, 2>(w.mt, [&](auto mt) { return with_bool(w.f32, [&](auto f32) {
+               constexpr int MT = decltype(mt)::value;
+               using S = std::conditional_t<decltype(f32)::value, float, double>;
+               if constexpr (MT == 2 && decltype(f32)::value) {  // float storage: never with two control tiles (ilqr_create)
+                 return fail(ILQR_ERR_UNSUPPORTED, "%s: no fp32 handle has more than %d controls", kernel_name, WM);
+               } else {
+                 wave(nt, mt, S(), dim3((unsigned)h->B * (unsigned)((q.nd + 15) / 16)), dim3(64));
+                 return 0;
+               }
+             }); }); }))
+    return rc;
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+static int launch_tangent(ilqr_batch* h, const TangentArgs& q, const char** name) {
+  *name = tangent_kernel_name(h->aos, value_wave_variant(h->nx, h->nu, h->dtype));
+  return launch_sensitivity(h, q, *name,
+      [&](auto& v, auto& m, dim3 grid, dim3 block) { hipLaunchKernelGGL((k_tangent_t<std::decay_t<decltype(m)>>), grid, block, 0, h->stream, v, q); },
+      [&](auto nt, auto mt, auto s, dim3 grid, dim3 block) {
+        using S = decltype(s);
+        hipLaunchKernelGGL((k_tangent_w<decltype(nt)::value, decltype(mt)::value, S>), grid, block, 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
+      });
+}
+static int launch_adjoint(ilqr_batch* h, const AdjointArgs& q, const char** name) {
+  *name = adjoint_kernel_name(h->aos, value_wave_variant(h->nx, h->nu, h->dtype));
+  return launch_sensitivity(h, q, *name,
+      [&](auto& v, auto& m, dim3 grid, dim3 block) { hipLaunchKernelGGL((k_adjoint_t<std::decay_t<decltype(m)>>), grid, block, 0, h->stream, v, q); },
+      [&](auto nt, auto mt, auto s, dim3 grid, dim3 block) {
+        using S = decltype(s);
+        hipLaunchKernelGGL((k_adjoint_w<decltype(nt)::value, decltype(mt)::value, S>), grid, block, 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
+      });
+}
+
 // The stored policy applied to caller-given states (ilqr_evaluate_policy / _on_device; evaluate.hpp): picked by the handle's layout alone,
 // as launch_value -- no route bit, no stage timer.  One thread per rollout, B * S of them (the caller has checked that they fit an int).
 static int launch_evaluate(ilqr_batch* h, const EvalArgs& e, const char** name) {

@@ -56,6 +56,14 @@ inline const char* covariance_kernel_name(bool aos, const WaveVariant& w) {  // 
   static const char* const kWave[2][2] = {{"k_covariance_w<1, 1>", "k_covariance_w<1, 2>"}, {"k_covariance_w<2, 1>", "k_covariance_w<2, 2>"}};
   return aos ? kWave[w.nt - 1][w.mt - 1] : "k_covariance_t";
 }
+inline const char* tangent_kernel_name(bool aos, const WaveVariant& w) {  // k_tangent_w: the variants value_wave_variant yields
+  static const char* const kWave[2][2] = {{"k_tangent_w<1, 1>", "k_tangent_w<1, 2>"}, {"k_tangent_w<2, 1>", "k_tangent_w<2, 2>"}};
+  return aos ? kWave[w.nt - 1][w.mt - 1] : "k_tangent_t";
+}
+inline const char* adjoint_kernel_name(bool aos, const WaveVariant& w) {  // k_adjoint_w: the same variants
+  static const char* const kWave[2][2] = {{"k_adjoint_w<1, 1>", "k_adjoint_w<1, 2>"}, {"k_adjoint_w<2, 1>", "k_adjoint_w<2, 2>"}};
+  return aos ? kWave[w.nt - 1][w.mt - 1] : "k_adjoint_t";
+}
 inline const char* evaluate_kernel_name(bool aos, bool traj_params) { return !aos ? "k_evaluate_t" : traj_params ? "k_evaluate_g<PT>" : "k_evaluate_g"; }
 
 struct RouteInputs {

@@ -415,6 +415,56 @@ int ilqr_get_covariance(ilqr_batch* h, int t0, int n_knots, const double* Sigma0
 int ilqr_copy_covariance_to_device(ilqr_batch* h, int t0, int n_knots, const void* Sigma0_device, const void* W_device, void* Sigma_device,
                                    void* Su_device, void* expected_cost_device);
 
+/* ---- the tangent and the adjoint of the stored closed loop (additive under ABI 6) ----------------------------------------------------
+ * The piece under the value, covariance and evaluation calls: the closed loop u = us[t] + K[t](x - xs[t]), linearised about the nominal,
+ * as a LINEAR OPERATOR applied to the caller's own vectors in both directions.  The tangent (forward, a Jacobian-vector product) says how
+ * a perturbation dx0 of the measured state and perturbations dv[t] of the stored controls move every later state and control; the
+ * adjoint (backward, a vector-Jacobian product) takes gx[t] = dL/dxs[t], gu[t] = dL/dus[t] of a caller's scalar loss L to dL/dx0 and
+ * dL/dv[t] -- what the backward of an autograd function around ilqr_mpc_step needs.  DEFINITION -- from the derivative records
+ * ilqr_get_derivatives would return at this moment (see there for which trajectory they describe) and the stored gains K; k, us, xs,
+ * the costs and the cost records are not read.  n_dirs >= 1 independent directions (columns) per trajectory;
+ * nku = min(t0 + n_knots, T) - t0 is the number of knots of the window [t0, t0 + n_knots) that have a control.
+ *   TANGENT   dx[0] = dx0[b]                                                 (NULL = zero)
+ *             t = 0 .. T-1:   du[t]   = K[t] dx[t] + dv[b][t]                (dv NULL = zero)
+ *                             dx[t+1] = fx[t] dx[t] + fu[t] du[t]
+ *     in:  dx0 [B][n_dirs][nx]           dv  [B][T][n_dirs][nu]    (the whole horizon)
+ *     out: dxs [B][n_knots][n_dirs][nx]  dus [B][nku][n_dirs][nu]  (the window only)
+ *     The recursion runs from knot 0 to the last knot anything needs.  dx0 and dv both NULL is refused (the answer would be zero), dxs and
+ *     dus both NULL is refused, dus non-NULL with nku == 0 is refused (knot T has no control).
+ *   ADJOINT   a[t] = 0 for t past the window;  gx, gu = 0 outside the window
+ *             t = last .. 0:  w[t] = gu[t] + fu[t]'a[t+1]                                      (t < T)
+ *                             a[t] = gx[t] + fx[t]'a[t+1] + K[t]'w[t]                          (a[T] = gx[T])
+ *             g_x0 = a[0],   g_v[t] = w[t]
+ *     in:  gx [B][n_knots][n_dirs][nx]   gu  [B][nku][n_dirs][nu]  (over the window; NULL = zero)
+ *     out: g_x0 [B][n_dirs][nx]          g_v [B][T][n_dirs][nu]    (us-shaped: the knots after the window are WRITTEN as exact zeros, the
+ *                                                                   caller's buffer is not assumed cleared)
+ *     gx and gu both NULL is refused, gu non-NULL with nku == 0 is refused; either output may be NULL, not both.
+ * The two calls are each other's transposes:  sum_t <gx[t], dx[t]> + sum_t <gu[t], du[t]> = <g_x0, dx0> + sum_t <g_v[t], dv[t]>.
+ * Per direction a vector; [n_dirs][nx] row-major is an nx x n_dirs column-major matrix: with dx0 = I (n_dirs = nx), dxs[t] is the state
+ * transition matrix Phi[t] and dus[t] is K[t] Phi[t], the first-order change of the whole plan with the measured state, both in this
+ * header's column-major convention.  With gx = cx, gu = cu the adjoint is the gradient of the trajectory cost in the controls under the
+ * stored feedback (and a[t] is ilqr_get_value's Vx[t] when k = 0); with K = 0 the plain open-loop cost gradient.
+ * The recursion runs in double on every handle (an fp32 handle's stored float records and gains are widened); every array is canonical
+ * double on every handle.  Every model, ILQR_MODEL_HOST included (its records are what the caller set), both dtypes.  The calls are
+ * read-only: they leave the handle as ilqr_get_derivatives at the same point does, later iterations are bit for bit those of a handle
+ * that never asked.  A window is a slice of the full call, bit for bit (for the adjoint: of the full call with gx, gu zero outside the
+ * window).  Column s of every output depends on column s of the inputs only, BIT FOR BIT: a direction computed alone (n_dirs = 1) and
+ * the same direction as column 20 of 33 give the same bits.
+ * The four arrays of a call do not overlap.
+ * What this is NOT: it is the first-order map of the LINEARISED closed loop about the nominal.  Rows of K that the box-QP zeroed are in
+ * K already, but saturation of the feedback and the model's second derivatives are not modelled; K Phi is the Gauss-Newton sensitivity
+ * of a converged plan, not the exact one.
+ * ILQR_ERR_INVALID: null handle, a bad window, n_dirs < 1, B * (T + 1) * n_dirs * max(nx, nu) beyond INT_MAX, the NULL combinations
+ * above; ILQR_ERR_STATE: before ilqr_init_traj / ilqr_set_trajectory.  Every refusal happens before anything is enqueued. */
+/* host arrays: a call-sized device buffer takes the inputs up and the outputs down; synchronises */
+int ilqr_get_tangent(ilqr_batch* h, int t0, int n_knots, int n_dirs, const double* dx0, const double* dv, double* dxs, double* dus);
+/* device memory of this handle's device: enqueued on the handle's stream, nothing waited for (as ilqr_copy_covariance_to_device) */
+int ilqr_copy_tangent_to_device(ilqr_batch* h, int t0, int n_knots, int n_dirs, const void* dx0_device, const void* dv_device, void* dxs_device,
+                                void* dus_device);
+int ilqr_get_adjoint(ilqr_batch* h, int t0, int n_knots, int n_dirs, const double* gx, const double* gu, double* g_x0, double* g_v);
+int ilqr_copy_adjoint_to_device(ilqr_batch* h, int t0, int n_knots, int n_dirs, const void* gx_device, const void* gu_device, void* g_x0_device,
+                                void* g_v_device);
+
 /* ---- the stored feedback policy applied to caller-given states (additive under ABI 6) -----------------------------------------------
  * What a solve leaves for a controller is the time-varying law u = us[t] + K[t](x - xs[t]).  These calls apply it to states the CALLER
  * holds -- n_samples of them per trajectory, at knot t0 -- and roll it through the handle's device model for n_knots knots; a read-only

@@ -400,6 +400,47 @@ class BatchILQR {
     check(ilqr_copy_covariance_to_device(h_, t0, n_knots, Sigma0_device, W_device, Sigma_device, Su_device, expected_cost_device),
           "ilqr_copy_covariance_to_device");
   }
+  // The tangent of the linearised closed loop (ilqr_get_tangent) over the knots [t0, t0 + n_knots), n_knots < 0: up to knot T: n_dirs
+  // directions per trajectory, dx0 [B][n_dirs][nx] and dv [B][T][n_dirs][nu] (null = zero, not both); dxs [B][n_knots][n_dirs][nx], dus
+  // [B][nku][n_dirs][nu] over the window's nku knots with a control; either output may be null, not both.
+  void tangent(int n_dirs, const std::vector<double>* dx0, const std::vector<double>* dv, std::vector<double>* dxs, std::vector<double>* dus, int t0 = 0,
+               int n_knots = -1) {
+    if (n_knots < 0) n_knots = T_ + 1 - t0;
+    const size_t dirs = (size_t)B_ * (n_dirs > 0 ? n_dirs : 0), knots = n_knots > 0 ? n_knots : 0, nku = knots_with_control(t0, n_knots);
+    require((!dx0 || dx0->size() == dirs * n_) && (!dv || dv->size() == dirs * T_ * m_), "tangent: dx0 [B][n_dirs][nx], dv [B][T][n_dirs][nu]");
+    require(!dus || nku > 0, "tangent: dus over a window that starts at knot T: knot T has no control");
+    if (dxs) dxs->assign(dirs * knots * n_, 0.0);
+    if (dus) dus->assign(dirs * nku * m_, 0.0);
+    check(ilqr_get_tangent(h_, t0, n_knots, n_dirs, dx0 ? dx0->data() : nullptr, dv ? dv->data() : nullptr, dxs ? dxs->data() : nullptr,
+                           dus ? dus->data() : nullptr),
+          "ilqr_get_tangent");
+  }
+  // The adjoint (ilqr_get_adjoint): gx [B][n_knots][n_dirs][nx], gu [B][nku][n_dirs][nu] over the window (null = zero, not both); g_x0
+  // [B][n_dirs][nx], g_v [B][T][n_dirs][nu] (zero after the window); either output may be null, not both.
+  void adjoint(int n_dirs, const std::vector<double>* gx, const std::vector<double>* gu, std::vector<double>* g_x0, std::vector<double>* g_v, int t0 = 0,
+               int n_knots = -1) {
+    if (n_knots < 0) n_knots = T_ + 1 - t0;
+    const size_t dirs = (size_t)B_ * (n_dirs > 0 ? n_dirs : 0), knots = n_knots > 0 ? n_knots : 0, nku = knots_with_control(t0, n_knots);
+    require((!gx || gx->size() == dirs * knots * n_) && (!gu || gu->size() == dirs * nku * m_), "adjoint: gx [B][n_knots][n_dirs][nx], gu [B][nku][n_dirs][nu]");
+    require(!gu || nku > 0, "adjoint: gu over a window that starts at knot T: knot T has no control");
+    if (g_x0) g_x0->assign(dirs * n_, 0.0);
+    if (g_v) g_v->assign(dirs * T_ * m_, 0.0);
+    check(ilqr_get_adjoint(h_, t0, n_knots, n_dirs, gx ? gx->data() : nullptr, gu ? gu->data() : nullptr, g_x0 ? g_x0->data() : nullptr,
+                           g_v ? g_v->data() : nullptr),
+          "ilqr_get_adjoint");
+  }
+  // ... or from and into caller-owned device memory, on the handle's stream, nothing waited for
+  void copy_tangent_to_device(int t0, int n_knots, int n_dirs, const void* dx0_device, const void* dv_device, void* dxs_device, void* dus_device) {
+    check(ilqr_copy_tangent_to_device(h_, t0, n_knots, n_dirs, dx0_device, dv_device, dxs_device, dus_device), "ilqr_copy_tangent_to_device");
+  }
+  void copy_adjoint_to_device(int t0, int n_knots, int n_dirs, const void* gx_device, const void* gu_device, void* g_x0_device, void* g_v_device) {
+    check(ilqr_copy_adjoint_to_device(h_, t0, n_knots, n_dirs, gx_device, gu_device, g_x0_device, g_v_device), "ilqr_copy_adjoint_to_device");
+  }
+  // how many knots of the window [t0, t0 + n_knots) have a control (nku of include/ilqr_amd.h)
+  size_t knots_with_control(int t0, int n_knots) const {
+    const int end = t0 + n_knots < T_ ? t0 + n_knots : T_;
+    return end > t0 ? (size_t)(end - t0) : 0;
+  }
   // The stored feedback policy u = us[t] + K[t](x - xs[t]) applied to the caller's states at knot t0 and rolled through the device model for
   // n_knots knots (n_knots < 0: up to knot T; ilqr_evaluate_policy): x [B][S][nx], S = n_samples states per trajectory; cost [B][S], x_end
   // [B][S][nx], u_first [B][S][nu]; any output pointer may be null, not all three.  A read-only query of the handle.
@@ -1031,6 +1072,45 @@ class iLQR {
     if (Su) *Su = mats(su, n_knots, m);
     if (expected_cost) *expected_cost = j[0];
   }
+  // The tangent of the linearised closed loop about the nominal (ilqr_get_tangent) over the knots [t0, t0 + n_knots), n_knots < 0: up to
+  // knot T.  One nx x n_dirs matrix per knot, a direction per column: dx0 (nx x n_dirs) perturbs the initial state, dv[t] (nu x n_dirs,
+  // T of them) the stored controls; an empty matrix / vector = zero, not both.  dxs[t] (nx x n_dirs) over the window, dus[t] (nu x n_dirs)
+  // over the window's knots with a control if asked for.  With dx0 = I: dxs[t] = Phi[t], dus[t] = K[t] Phi[t].
+  void tangent(const MatrixXd& dx0, const VecOfMatXd& dv, VecOfMatXd& dxs, VecOfMatXd* dus = nullptr, int t0 = 0, int n_knots = -1) const {
+    if (!engine_) throw std::logic_error("tangent(): no trajectory initialised");
+    const int n = model->x_dims, m = model->u_dims;
+    if (n_knots < 0) n_knots = T + 1 - t0;
+    const bool has_x = dx0.rows() != 0 || dx0.cols() != 0, has_v = !dv.empty();
+    if (!has_x && !has_v) throw std::invalid_argument("tangent(): dx0 and dv are both empty");
+    const int S = (int)(has_x ? dx0.cols() : dv[0].cols());
+    if (has_x && dx0.rows() != n) throw std::invalid_argument("tangent(): dx0 is nx x n_dirs");
+    if (has_v && (int)dv.size() != T) throw std::invalid_argument("tangent(): dv holds T matrices");
+    std::vector<double> x0v, dvv, xs, us;
+    if (has_x) x0v = flatten_dirs(&dx0, 1, n, S, "tangent(): dx0 is nx x n_dirs");
+    if (has_v) dvv = flatten_dirs(dv.data(), T, m, S, "tangent(): every dv[t] is nu x n_dirs");
+    engine_->tangent(S, has_x ? &x0v : nullptr, has_v ? &dvv : nullptr, &xs, dus ? &us : nullptr, t0, n_knots);
+    dxs = unflatten_dirs(xs, n_knots, n, S);
+    if (dus) *dus = unflatten_dirs(us, (int)engine_->knots_with_control(t0, n_knots), m, S);
+  }
+  // The adjoint (ilqr_get_adjoint): gx[t] (nx x n_dirs, n_knots of them) and gu[t] (nu x n_dirs, one per knot of the window with a
+  // control) are the caller's cotangents over the window, an empty vector = zero, not both; g_x0 (nx x n_dirs) and, if asked for, g_v[t]
+  // (nu x n_dirs, T of them, zero after the window).  The transpose of tangent().
+  void adjoint(const VecOfMatXd& gx, const VecOfMatXd& gu, MatrixXd& g_x0, VecOfMatXd* g_v = nullptr, int t0 = 0, int n_knots = -1) const {
+    if (!engine_) throw std::logic_error("adjoint(): no trajectory initialised");
+    const int n = model->x_dims, m = model->u_dims;
+    if (n_knots < 0) n_knots = T + 1 - t0;
+    const int nku = (int)engine_->knots_with_control(t0, n_knots);
+    if (gx.empty() && gu.empty()) throw std::invalid_argument("adjoint(): gx and gu are both empty");
+    const int S = (int)(!gx.empty() ? gx[0].cols() : gu[0].cols());
+    if ((!gx.empty() && (int)gx.size() != n_knots) || (!gu.empty() && (int)gu.size() != nku))
+      throw std::invalid_argument("adjoint(): gx holds n_knots matrices, gu one per knot of the window with a control");
+    std::vector<double> gxv, guv, x0, v;
+    if (!gx.empty()) gxv = flatten_dirs(gx.data(), n_knots, n, S, "adjoint(): every gx[t] is nx x n_dirs");
+    if (!gu.empty()) guv = flatten_dirs(gu.data(), nku, m, S, "adjoint(): every gu[t] is nu x n_dirs");
+    engine_->adjoint(S, !gx.empty() ? &gxv : nullptr, !gu.empty() ? &guv : nullptr, &x0, g_v ? &v : nullptr, t0, n_knots);
+    g_x0 = unflatten_dirs(x0, 1, n, S)[0];
+    if (g_v) *g_v = unflatten_dirs(v, T, m, S);
+  }
   // the control the stored policy gives at knot t in the state x: us[t] + K[t](x - xs[t]), evaluated on the device (ilqr_evaluate_policy, one knot)
   VectorXd feedback_control(int t, const VectorXd& x) const {
     if (!engine_) throw std::logic_error("feedback_control(): no trajectory initialised");
@@ -1046,6 +1126,25 @@ class iLQR {
   int status() const { return engine_->status()[0]; }  // enum ilqr_traj_status
 
  private:
+  // `count` matrices of `rows` x S, a direction per column  <->  the ABI's [count][S][rows] (a column-major rows x S matrix per knot)
+  static std::vector<double> flatten_dirs(const MatrixXd* M, int count, int rows, int S, const char* what) {
+    std::vector<double> out((size_t)count * S * rows);
+    for (int t = 0; t < count; t++) {
+      if (M[t].rows() != rows || M[t].cols() != S) throw std::invalid_argument(what);
+      for (int s = 0; s < S; s++)
+        for (int a = 0; a < rows; a++) out[((size_t)t * S + s) * rows + a] = M[t](a, s);
+    }
+    return out;
+  }
+  static VecOfMatXd unflatten_dirs(const std::vector<double>& v, int count, int rows, int S) {
+    VecOfMatXd out(count);
+    for (int t = 0; t < count; t++) {
+      out[t] = MatrixXd(rows, S);
+      for (int s = 0; s < S; s++)
+        for (int a = 0; a < rows; a++) out[t](a, s) = v[((size_t)t * S + s) * rows + a];
+    }
+    return out;
+  }
   double dt = 0;
   int T = 0;
   std::unique_ptr<BatchILQR> engine_;
