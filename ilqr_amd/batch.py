@@ -519,6 +519,41 @@ class BatchILQR:
         g_v [B][T][S][nu] (either may be None, not both).  Enqueued on the handle's stream, nothing waited for."""
         self._check(self.lib.ilqr_copy_adjoint_to_device(self.h, int(t0), int(n), int(S), gx_ptr, gu_ptr, g_x0_ptr, g_v_ptr))
 
+    def lq_solve(self, gx=None, gu=None, dx0=None, mu=0.0, hold_clamped=True, dlam=False):
+        """The LQ subproblem of the current records solved for the caller's linear terms (include/ilqr_amd.h, ilqr_solve_lq): gx
+        [B][T+1][S][nx], gu [B][T][S][nu] the linear cost terms, dx0 [B][S][nx] the initial perturbation, S directions per trajectory (None =
+        zero, not all three); mu >= 0 is added to Quu's diagonal; hold_clamped keeps the controls whose row of the stored K is exactly zero
+        at du = 0.  Returns (dxs [B][T+1][S][nx], dus [B][T][S][nu][, dlam [B][T+1][S][nx]], info [B]); info[b] = t + 1 when Quu of knot t was
+        not positive definite on the free controls (that trajectory's outputs are NaN), else 0.  Inputs without the direction axis are one
+        direction and the axis is dropped again on output.  With gx = cx, gu = cu: the Newton step; with gx = dL/dxs, gu = dL/dus: the
+        backward pass of a differentiable MPC layer.  Synchronises."""
+        X = self._dirs_input(gx, (self.T + 1,), self.nx, "gx")
+        U = self._dirs_input(gu, (self.T,), self.nu, "gu")
+        X0 = self._dirs_input(dx0, (), self.nx, "dx0")
+        given = [a for a in (X, U, X0) if a[0] is not None]
+        if not given:
+            raise ValueError("gx, gu and dx0 are all None: the answer would be zero")
+        S, flat = given[0][1], given[0][2]
+        if any(a[1] != S or a[2] != flat for a in given):
+            raise ValueError("gx, gu and dx0 disagree on the directions: %s" % [a[0].shape for a in given])
+        dxs, dus = np.zeros((self.B, self.T + 1, S, self.nx)), np.zeros((self.B, self.T, S, self.nu))
+        lam = np.zeros((self.B, self.T + 1, S, self.nx)) if dlam else None
+        info = np.zeros(self.B, dtype=np.int32)
+        self._check(self.lib.ilqr_solve_lq(self.h, S, capi.LQ_HOLD_CLAMPED if hold_clamped else 0, float(mu), _p(X0[0]), _p(X[0]), _p(U[0]), _p(dxs),
+                                           _p(dus), _p(lam), _pi(info)))
+        out = (dxs, dus) + ((lam,) if dlam else ())
+        if flat:
+            out = tuple(a[:, :, 0] for a in out)
+        return out + (info,)
+
+    def copy_lq_solve_to_device(self, S, mu=0.0, hold_clamped=True, dx0_ptr=None, gx_ptr=None, gu_ptr=None, dxs_ptr=None, dus_ptr=None, dlam_ptr=None,
+                                info_ptr=None):
+        """ilqr_solve_lq_on_device with raw device pointers (e.g. torch.Tensor.data_ptr()) to float64 dx0 [B][S][nx], gx [B][T+1][S][nx], gu
+        [B][T][S][nu] (None = zero, not all three), dxs, dlam [B][T+1][S][nx], dus [B][T][S][nu] (any may be None, not all three), int32 info
+        [B] (may be None).  Enqueued on the handle's stream, nothing waited for."""
+        self._check(self.lib.ilqr_solve_lq_on_device(self.h, int(S), capi.LQ_HOLD_CLAMPED if hold_clamped else 0, float(mu), dx0_ptr, gx_ptr, gu_ptr,
+                                                     dxs_ptr, dus_ptr, dlam_ptr, info_ptr))
+
     def derivatives(self):
         n, m, B, T1 = self.nx, self.nu, self.B, self.T + 1
         mem = dict(fx=np.zeros((B, T1, n, n)), fu=np.zeros((B, T1, m, n)), cx=np.zeros((B, T1, n)),

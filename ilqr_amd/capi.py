@@ -12,6 +12,7 @@ TAIL_HOLD, TAIL_ZERO = 0, 1  # enum ilqr_tail: what fills the knots a receding-h
 RESET_NONFINITE, RESET_LAMBDA_MAX = 1, 2  # enum ilqr_reset_rule: bits of `rules`
 WAS_MASKED, WAS_NONFINITE, WAS_LAMBDA_MAX = 1, 2, 4  # enum ilqr_reset_why: bits of a reset flag
 WAS_CLONED, CLONE_REFUSED = 1, 2  # enum ilqr_clone_why: a clone flag
+LQ_HOLD_CLAMPED = 1  # enum ilqr_lq_flags: bits of ilqr_solve_lq's `flags`
 EVAL_CLAMP = 1  # enum ilqr_eval_flags: bits of ilqr_evaluate_policy's `flags`
 # enum ilqr_route (include/ilqr_amd.h): which of several equivalent kernels a handle uses; 0 = by batch size
 ROUTE_TILE_PER_CU, ROUTE_TWO_TILES_PER_CU, ROUTE_WIDE_TILES = 1, 2, 3
@@ -78,6 +79,8 @@ SYMBOLS = {
     "ilqr_copy_tangent_to_device": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ilqr_get_adjoint": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
     "ilqr_copy_adjoint_to_device": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ilqr_solve_lq": (C.c_int, [_H, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "ilqr_solve_lq_on_device": (C.c_int, [_H, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ilqr_evaluate_policy": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
     "ilqr_evaluate_policy_on_device": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ilqr_trajectory_params_count": (C.c_int, []),

@@ -27,6 +27,8 @@
 #include "covariance_wave.hpp"
 #include "sensitivity_thread.hpp"
 #include "sensitivity_wave.hpp"
+#include "lq_solve_thread.hpp"
+#include "lq_solve_wave.hpp"
 #include "evaluate.hpp"
 #include "clone.hpp"
 
@@ -86,6 +88,7 @@ void ilqr_destroy(ilqr_batch* h) {
 #endif
   for (void* p : h->allocs) (void)hipFree(p);
   if (h->staging) (void)hipFree(h->staging);
+  if (h->lq_scratch) (void)hipFree(h->lq_scratch);
   if (h->d_perm) (void)hipFree(h->d_perm);
   if (h->perm_scratch) (void)hipFree(h->perm_scratch);
   (void)timers_drain(h);  // (every event back into the pool, each once)
@@ -1148,6 +1151,81 @@ int ilqr_get_adjoint(ilqr_batch* h, int t0, int n_knots, int n_dirs, const doubl
   if (int rc = stage_sensitivity_up(h, gx, n.x_win, gu, n.u_win, g_x0 != nullptr, n.x_one, g_v != nullptr, n.u_all, &d)) return rc;
   if (int rc = run_adjoint(h, {t0, n_knots, n_dirs, d.in_a, d.in_b, d.out_a, d.out_b}, who)) return rc;
   return stage_sensitivity_down(h, d, g_x0, g_v);
+}
+
+// ---- the LQ subproblem of the records, solved for the caller's linear terms (additive under ABI 6; lq_solve_wave.hpp) ------
+// every refusal the two calls share -- before anything is enqueued --, then the records as ilqr_get_derivatives would return them now
+static int prepare_lq_solve(ilqr_batch* h, int n_dirs, int flags, double mu, const void* dx0, const void* gx, const void* gu, const void* dxs, const void* dus,
+                            const void* dlam, const char* who) {
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  REQUIRE(n_dirs >= 1, "%s: n_dirs %d must be >= 1", who, n_dirs);
+  REQUIRE((flags & ~ILQR_LQ_HOLD_CLAMPED) == 0, "%s: unknown flag bits 0x%x", who, (unsigned)(flags & ~ILQR_LQ_HOLD_CLAMPED));
+  REQUIRE(mu >= 0.0 && mu <= 1.7976931348623157e308, "%s: mu %g must be finite and >= 0", who, mu);
+  REQUIRE(dx0 || gx || gu, "%s: dx0, gx and gu are all null: the answer would be zero", who);
+  REQUIRE(dxs || dus || dlam, "%s: dxs, dus and dlam are all null", who);
+  const long long widest = (long long)h->B * (h->T + 1) * n_dirs * std::max(h->nx, h->nu);
+  REQUIRE(widest <= (long long)INT_MAX, "%s: B * (T + 1) * n_dirs * max(nx, nu) = %lld elements do not fit an int", who, widest);
+  if (!h->initialised) return fail(ILQR_ERR_STATE, "%s before ilqr_init_traj/ilqr_set_trajectory: no records are stored", who);
+  HIPCHK(hipSetDevice(h->device));
+  return materialise_records(h);
+}
+// The scratch of one call (include/ilqr_amd.h states the formula), carved up; then the three kernels.  Bs: trajectories the scratch is laid
+// out for (the tiled kernels index [knot][element][Bp]).
+static int run_lq_solve(ilqr_batch* h, int n_dirs, int flags, double mu, const double* dx0, const double* gx, const double* gu, double* dxs, double* dus,
+                        double* dlam, int* info, const char* who) {
+  const size_t Bs = h->aos ? (size_t)h->B : (size_t)h->Bp, T = (size_t)h->T, n = (size_t)h->nx, m = (size_t)h->nu;
+  const size_t n_fail = (Bs + 1) / 2, n_kd = Bs * T * m * n, n_mi = Bs * T * m * m, n_p = dlam ? Bs * (T + 1) * n * n : 0,
+               n_kdir = dus ? 0 : (size_t)h->B * T * n_dirs * m;
+  if (int rc = ensure_lq_scratch(h, n_fail + n_kd + n_mi + n_p + n_kdir)) return rc;
+  double* s = h->lq_scratch;
+  LqArgs q;
+  q.nd = n_dirs, q.hold = (flags & ILQR_LQ_HOLD_CLAMPED) ? 1 : 0, q.mu = mu;
+  q.dx0 = dx0, q.gx = gx, q.gu = gu, q.dxs = dxs, q.dus = dus, q.dlam = dlam, q.info = info;
+  q.fail = (int*)s;
+  q.Kd = s + n_fail;
+  q.Mi = q.Kd + n_kd;
+  q.P = dlam ? q.Mi + n_mi : nullptr;
+  q.kd = dus ? dus : q.Mi + n_mi + n_p;
+  const char* kernel = "";
+  const int rc = launch_lq_solve(h, q, &kernel);
+  return name_refused_kernel(rc, who, kernel);
+}
+
+int ilqr_solve_lq_on_device(ilqr_batch* h, int n_dirs, int flags, double mu, const void* dx0_device, const void* gx_device, const void* gu_device,
+                            void* dxs_device, void* dus_device, void* dlam_device, void* info_device) {
+  const char* who = "ilqr_solve_lq_on_device";
+  if (int rc = prepare_lq_solve(h, n_dirs, flags, mu, dx0_device, gx_device, gu_device, dxs_device, dus_device, dlam_device, who)) return rc;
+  return run_lq_solve(h, n_dirs, flags, mu, (const double*)dx0_device, (const double*)gx_device, (const double*)gu_device, (double*)dxs_device,
+                      (double*)dus_device, (double*)dlam_device, (int*)info_device, who);
+}
+
+int ilqr_solve_lq(ilqr_batch* h, int n_dirs, int flags, double mu, const double* dx0, const double* gx, const double* gu, double* dxs, double* dus,
+                  double* dlam, int* info) {
+  const char* who = "ilqr_solve_lq";
+  if (int rc = prepare_lq_solve(h, n_dirs, flags, mu, dx0, gx, gu, dxs, dus, dlam, who)) return rc;
+  // a call-sized device buffer (the staging buffer: the three inputs, the three outputs, info), the inputs copied up, the outputs copied
+  // out and waited for
+  const size_t per_x = (size_t)h->B * n_dirs * h->nx, per_u = (size_t)h->B * n_dirs * h->nu;
+  const size_t n_x0 = dx0 ? per_x : 0, n_gx = gx ? per_x * (h->T + 1) : 0, n_gu = gu ? per_u * h->T : 0, n_dxs = dxs ? per_x * (h->T + 1) : 0,
+               n_dus = dus ? per_u * h->T : 0, n_dl = dlam ? per_x * (h->T + 1) : 0, n_info = info ? ((size_t)h->B + 1) / 2 : 0;
+  if (int rc = ensure_staging(h, n_x0 + n_gx + n_gu + n_dxs + n_dus + n_dl + n_info)) return rc;
+  double* const d_x0 = dx0 ? h->staging : nullptr;
+  double* const d_gx = gx ? h->staging + n_x0 : nullptr;
+  double* const d_gu = gu ? h->staging + n_x0 + n_gx : nullptr;
+  double* const d_dxs = dxs ? h->staging + n_x0 + n_gx + n_gu : nullptr;
+  double* const d_dus = dus ? h->staging + n_x0 + n_gx + n_gu + n_dxs : nullptr;
+  double* const d_dl = dlam ? h->staging + n_x0 + n_gx + n_gu + n_dxs + n_dus : nullptr;
+  int* const d_info = info ? (int*)(h->staging + n_x0 + n_gx + n_gu + n_dxs + n_dus + n_dl) : nullptr;
+  if (dx0) HIPCHK(hipMemcpyAsync(d_x0, dx0, n_x0 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (gx) HIPCHK(hipMemcpyAsync(d_gx, gx, n_gx * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (gu) HIPCHK(hipMemcpyAsync(d_gu, gu, n_gu * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (int rc = run_lq_solve(h, n_dirs, flags, mu, d_x0, d_gx, d_gu, d_dxs, d_dus, d_dl, d_info, who)) return rc;
+  if (dxs) HIPCHK(hipMemcpyAsync(dxs, d_dxs, n_dxs * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (dus) HIPCHK(hipMemcpyAsync(dus, d_dus, n_dus * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (dlam) HIPCHK(hipMemcpyAsync(dlam, d_dl, n_dl * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (info) HIPCHK(hipMemcpyAsync(info, d_info, (size_t)h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
 }
 
 // ---- the stored policy applied to caller-given states (additive under ABI 6; evaluate.hpp) ------

@@ -70,6 +70,10 @@ struct ilqr_batch {
   // multi-start groups (clone.hpp; ilqr_select_best, ilqr_clone_trajectories, ilqr_clone_best): allocated by the first call that needs them
   int* clone_ints = nullptr;         // [3][Bp]: the map (a host map's copy, or the handle's own best-of-group map), the sources of the call under way, the flags of the last call
   bool clone_flags_valid = false;    // a clone call has run: the flags describe it
+  // ilqr_solve_lq's call-sized scratch (lq_solve_wave.hpp: Kd, Mi, P, kd, the failure marks): allocated by the first call, kept while the
+  // next call's fits (ensure_lq_scratch), freed with the handle
+  double* lq_scratch = nullptr;
+  size_t lq_scratch_elems = 0;
   // v is the view every entry point addresses arrays through; for an fp32 handle its trajectory pointers hold
   // the addresses of FLOAT arrays (never dereferenced as double: kernels get vf, the same addresses typed float*)
   BatchView v;
@@ -311,6 +315,18 @@ static int ensure_staging(ilqr_batch* h, size_t elems) {
   }
   HIPCHK(hipMalloc((void**)&h->staging, elems * sizeof(double)));
   h->staging_elems = elems;
+  return 0;
+}
+static int ensure_lq_scratch(ilqr_batch* h, size_t elems) {
+  if (elems <= h->lq_scratch_elems) return 0;
+  if (h->lq_scratch) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipFree(h->lq_scratch));
+    h->lq_scratch = nullptr;
+    h->lq_scratch_elems = 0;
+  }
+  HIPCHK(hipMalloc((void**)&h->lq_scratch, elems * sizeof(double)));
+  h->lq_scratch_elems = elems;
   return 0;
 }
 // One of the handle's arrays as the conversions take it: S knots of E elements per trajectory, of which the knots [t0, t0 + n) are moved

@@ -496,6 +496,40 @@ static int launch_adjoint(ilqr_batch* h, const AdjointArgs& q, const char** name
       });
 }
 
+// The LQ subproblem of the records solved for the caller's linear terms (ilqr_solve_lq / _on_device; lq_solve_wave.hpp, lq_solve_thread.hpp):
+// as launch_sensitivity, picked by the handle's layout and sizes alone.  The caller has materialised the records, sized the scratch and
+// checked that B * n_dirs fits an int.  Generic layout: the gain sweep, one wavefront per trajectory, then the two direction sweeps, one
+// wavefront per (trajectory, 16 directions); tiled layout: one thread per trajectory, then one per (trajectory, direction).
+static int launch_lq_solve(ilqr_batch* h, const LqArgs& q, const char** name) {
+  const WaveVariant w = value_wave_variant(h->nx, h->nu, h->dtype);
+  *name = lq_solve_kernel_name(h->aos, w);
+  if (!h->aos) {
+    const dim3 block(64), per_traj((unsigned)(h->Bp / 64)), per_dir((unsigned)(h->Bp / 64) * (unsigned)q.nd);
+    if (int rc = with_model(h, [&](auto& v, auto& m, auto&) {
+          using Mdl = std::decay_t<decltype(m)>;
+          hipLaunchKernelGGL((k_lq_gain_t<Mdl>), per_traj, block, 0, h->stream, v, q);
+          hipLaunchKernelGGL((k_lq_dir_t<Mdl>), per_dir, block, 0, h->stream, v, q);
+          return 0;
+        }))
+      return rc;
+  } else if (int rc = with_int<1, 2>(w.nt, [&](auto nt) { return with_int<1, 2>(w.mt, [&](auto mt) { return with_bool(w.f32, [&](auto f32) {
+               constexpr int NT = decltype(nt)::value, MT = decltype(mt)::value;
+               using S = std::conditional_t<decltype(f32)::value, float, double>;
+               if constexpr (MT == 2 && decltype(f32)::value) {  // float storage: never with two control tiles (ilqr_create)
+                 return fail(ILQR_ERR_UNSUPPORTED, "%s: no fp32 handle has more than %d controls", *name, WM);
+               } else {
+                 const dim3 block(64), per_traj((unsigned)h->B), per_tile((unsigned)h->B * (unsigned)((q.nd + 15) / 16));
+                 hipLaunchKernelGGL((k_lq_gain_w<NT, MT, S>), per_traj, block, 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
+                 hipLaunchKernelGGL((k_lq_back_w<NT, MT, S>), per_tile, block, 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
+                 hipLaunchKernelGGL((k_lq_fwd_w<NT, MT, S>), per_tile, block, 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
+                 return 0;
+               }
+             }); }); }))
+    return rc;
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // The stored policy applied to caller-given states (ilqr_evaluate_policy / _on_device; evaluate.hpp): picked by the handle's layout alone,
 // as launch_value -- no route bit, no stage timer.  One thread per rollout, B * S of them (the caller has checked that they fit an int).
 static int launch_evaluate(ilqr_batch* h, const EvalArgs& e, const char** name) {

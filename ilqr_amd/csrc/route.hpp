@@ -64,6 +64,10 @@ inline const char* adjoint_kernel_name(bool aos, const WaveVariant& w) {  // k_a
   static const char* const kWave[2][2] = {{"k_adjoint_w<1, 1>", "k_adjoint_w<1, 2>"}, {"k_adjoint_w<2, 1>", "k_adjoint_w<2, 2>"}};
   return aos ? kWave[w.nt - 1][w.mt - 1] : "k_adjoint_t";
 }
+inline const char* lq_solve_kernel_name(bool aos, const WaveVariant& w) {  // k_lq_gain_w (then k_lq_back_w, k_lq_fwd_w): the same variants
+  static const char* const kWave[2][2] = {{"k_lq_gain_w<1, 1>", "k_lq_gain_w<1, 2>"}, {"k_lq_gain_w<2, 1>", "k_lq_gain_w<2, 2>"}};
+  return aos ? kWave[w.nt - 1][w.mt - 1] : "k_lq_gain_t";
+}
 inline const char* evaluate_kernel_name(bool aos, bool traj_params) { return !aos ? "k_evaluate_t" : traj_params ? "k_evaluate_g<PT>" : "k_evaluate_g"; }
 
 struct RouteInputs {

@@ -465,6 +465,47 @@ int ilqr_get_adjoint(ilqr_batch* h, int t0, int n_knots, int n_dirs, const doubl
 int ilqr_copy_adjoint_to_device(ilqr_batch* h, int t0, int n_knots, int n_dirs, const void* gx_device, const void* gu_device, void* g_x0_device,
                                 void* g_v_device);
 
+/* ---- the LQ subproblem of the records, solved for caller-given linear terms (additive under ABI 6) -----------------------------------
+ * The calls above take the stored gains K as given; this one answers how the OPTIMAL plan moves when the problem moves.  It solves the
+ * equality-constrained LQ subproblem the handle holds (fx, fu, cxx, cxu, cuu of the records) for the caller's linear cost terms gx, gu and
+ * initial perturbation dx0: the Newton / iLQR step (gx = cx, gu = cu), the backward pass of a differentiable MPC layer (gx = dL/dxs,
+ * gu = dL/dus), the first-order re-plan for a shifted goal (gx = -cxx dgoal), the exact LQ response to a measured-state change (dx0 = I).
+ * DEFINITION -- from the derivative records ilqr_get_derivatives would return at this moment, and from the stored K ONLY to decide which
+ * controls are held.  n_dirs >= 1 independent directions (columns) per trajectory, the whole horizon, no windows.
+ *   HELD SET  with ILQR_LQ_HOLD_CLAMPED control e of knot t is held when every element of row e of K[t] is exactly zero (how the box-QP
+ *             leaves a clamped control); without the flag nothing is held.  F = the free controls of the knot.
+ *   GAINS     P[T] = cxx[T];  t = T-1 .. 0:
+ *               Qxx = cxx + fx'P[t+1] fx,   Qux = cxu' + fu'P[t+1] fx,   Quu = cuu + fu'P[t+1] fu + mu I
+ *               Quu_FF = L L'   lower Cholesky over F in index order; a pivot <= 0 or not finite ends this trajectory: info[b] = t + 1
+ *               Kd_F = -Quu_FF^-1 Qux_F, held rows of Kd zero;   P[t] = sym(Qxx + Qux'Kd)
+ *             (a knot with no free control factors nothing and cannot fail)
+ *   BACKWARD  per direction:  v[T] = gx[T];   w = gu[t] + fu'v[t+1];   kd_F = -Quu_FF^-1 w_F, held rows zero;
+ *                             v[t] = gx[t] + fx'v[t+1] + Kd'w
+ *   FORWARD   per direction:  dx[0] = dx0;   du[t] = Kd dx[t] + kd[t];   dx[t+1] = fx dx[t] + fu du[t];   dlam[t] = P[t] dx[t] + v[t]
+ *     in:  dx0 [B][n_dirs][nx]   gx [B][T+1][n_dirs][nx]   gu [B][T][n_dirs][nu]        (NULL = zero, not all three)
+ *     out: dxs, dlam [B][T+1][n_dirs][nx]   dus [B][T][n_dirs][nu]   info int32 [B]       (any may be NULL, not all of dxs, dus, dlam)
+ * For symmetric cxx, cuu, (dxs, dus) minimises  sum_t 1/2 [dx; du]'[cxx cxu; cxu' cuu + mu I][dx; du] + gx'dx + gu'du  subject to the
+ * linearised dynamics, dx[0] = dx0 and held controls = 0; dlam holds the multipliers of the dynamics (dlam[T] = cxx[T] dx[T] + gx[T],
+ * dlam[t] = gx[t] + cxx dx[t] + cxu du[t] + fx'dlam[t+1]).  info[b] = 0: solved.  A failed trajectory gets quiet NaNs in all of its
+ * outputs and changes no other trajectory's bits.  Held dus entries are exact zeros; dxs[:, 0] is dx0 to the bit; column s of every output
+ * depends on column s of the inputs only, BIT FOR BIT.  All arithmetic is double on every handle (an fp32 handle's stored floats are
+ * widened), every array canonical double.  Every model, ILQR_MODEL_HOST included, both dtypes.  Read-only: later iterations are bit for
+ * bit those of a handle that never asked.  The arrays of a call do not overlap.
+ * SCRATCH: the handle keeps one device buffer for these calls, allocated by the first call and kept while the next one's fits, of
+ *     Bs * (T * (nu * nx + nu * nu) + [dlam asked for] (T + 1) * nx * nx) + [dus NULL] B * T * n_dirs * nu + ceil(Bs / 2)   doubles,
+ * Bs = B on the generic layout, B rounded up to 64 on the nx = 4 kernels' layout: Kd, the masked -Quu^-1, P, kd.  At nx = 32, nu = 16,
+ * B = 8192, T = 200 that is 10 GB without dlam and 23 GB with it (nu = 32: 27 / 40 GB), next to the 44 GB of records.
+ * ILQR_ERR_INVALID: null handle, n_dirs < 1, unknown flag bits, mu negative or not finite, dx0, gx and gu all NULL, dxs, dus and dlam all
+ * NULL, B * (T + 1) * n_dirs * max(nx, nu) beyond INT_MAX; ILQR_ERR_STATE: before ilqr_init_traj / ilqr_set_trajectory.  Every refusal
+ * happens before anything is enqueued. */
+enum ilqr_lq_flags { ILQR_LQ_HOLD_CLAMPED = 1 };
+/* host arrays: a call-sized device buffer takes the inputs up and the outputs down; synchronises */
+int ilqr_solve_lq(ilqr_batch* h, int n_dirs, int flags, double mu, const double* dx0, const double* gx, const double* gu, double* dxs, double* dus,
+                  double* dlam, int* info);
+/* device memory of this handle's device: enqueued on the handle's stream, nothing waited for */
+int ilqr_solve_lq_on_device(ilqr_batch* h, int n_dirs, int flags, double mu, const void* dx0_device, const void* gx_device, const void* gu_device,
+                            void* dxs_device, void* dus_device, void* dlam_device, void* info_device);
+
 /* ---- the stored feedback policy applied to caller-given states (additive under ABI 6) -----------------------------------------------
  * What a solve leaves for a controller is the time-varying law u = us[t] + K[t](x - xs[t]).  These calls apply it to states the CALLER
  * holds -- n_samples of them per trajectory, at knot t0 -- and roll it through the handle's device model for n_knots knots; a read-only

@@ -441,6 +441,30 @@ class BatchILQR {
     const int end = t0 + n_knots < T_ ? t0 + n_knots : T_;
     return end > t0 ? (size_t)(end - t0) : 0;
   }
+  // The LQ subproblem of the current records solved for the caller's linear terms (ilqr_solve_lq): n_dirs directions per trajectory, dx0
+  // [B][n_dirs][nx], gx [B][T+1][n_dirs][nx], gu [B][T][n_dirs][nu] (null = zero, not all three); dxs, dlam [B][T+1][n_dirs][nx], dus
+  // [B][T][n_dirs][nu] (any may be null, not all three).  Returns info [B]: 0, or t + 1 when Quu of knot t was not positive definite on
+  // the free controls (that trajectory's outputs are NaN).
+  std::vector<int> lq_solve(int n_dirs, const std::vector<double>* dx0, const std::vector<double>* gx, const std::vector<double>* gu, std::vector<double>* dxs,
+                            std::vector<double>* dus, std::vector<double>* dlam = nullptr, double mu = 0.0, bool hold_clamped = true) {
+    const size_t dirs = (size_t)B_ * (n_dirs > 0 ? n_dirs : 0);
+    require((!dx0 || dx0->size() == dirs * n_) && (!gx || gx->size() == dirs * (T_ + 1) * n_) && (!gu || gu->size() == dirs * T_ * m_),
+            "lq_solve: dx0 [B][n_dirs][nx], gx [B][T+1][n_dirs][nx], gu [B][T][n_dirs][nu]");
+    if (dxs) dxs->assign(dirs * (T_ + 1) * n_, 0.0);
+    if (dus) dus->assign(dirs * T_ * m_, 0.0);
+    if (dlam) dlam->assign(dirs * (T_ + 1) * n_, 0.0);
+    std::vector<int> info(B_, 0);
+    check(ilqr_solve_lq(h_, n_dirs, hold_clamped ? ILQR_LQ_HOLD_CLAMPED : 0, mu, dx0 ? dx0->data() : nullptr, gx ? gx->data() : nullptr,
+                        gu ? gu->data() : nullptr, dxs ? dxs->data() : nullptr, dus ? dus->data() : nullptr, dlam ? dlam->data() : nullptr, info.data()),
+          "ilqr_solve_lq");
+    return info;
+  }
+  // ... or from and into caller-owned device memory, on the handle's stream, nothing waited for (info_device: int32 [B], may be null)
+  void solve_lq_on_device(int n_dirs, int flags, double mu, const void* dx0_device, const void* gx_device, const void* gu_device, void* dxs_device,
+                          void* dus_device, void* dlam_device, void* info_device) {
+    check(ilqr_solve_lq_on_device(h_, n_dirs, flags, mu, dx0_device, gx_device, gu_device, dxs_device, dus_device, dlam_device, info_device),
+          "ilqr_solve_lq_on_device");
+  }
   // The stored feedback policy u = us[t] + K[t](x - xs[t]) applied to the caller's states at knot t0 and rolled through the device model for
   // n_knots knots (n_knots < 0: up to knot T; ilqr_evaluate_policy): x [B][S][nx], S = n_samples states per trajectory; cost [B][S], x_end
   // [B][S][nx], u_first [B][S][nu]; any output pointer may be null, not all three.  A read-only query of the handle.
@@ -1110,6 +1134,30 @@ class iLQR {
     engine_->adjoint(S, !gx.empty() ? &gxv : nullptr, !gu.empty() ? &guv : nullptr, &x0, g_v ? &v : nullptr, t0, n_knots);
     g_x0 = unflatten_dirs(x0, 1, n, S)[0];
     if (g_v) *g_v = unflatten_dirs(v, T, m, S);
+  }
+  // The LQ subproblem of the current records solved for the caller's linear terms (ilqr_solve_lq).  One matrix per knot, a direction per
+  // column: gx[t] (nx x n_dirs, T + 1 of them), gu[t] (nu x n_dirs, T of them), dx0 (nx x n_dirs); an empty vector / matrix = zero, not
+  // all three.  dxs[t], dus[t] and, if asked for, dlam[t] (the multipliers of the dynamics).  Returns ilqr_solve_lq's info: 0, or t + 1
+  // when Quu of knot t was not positive definite on the free controls.  With gx = cx, gu = cu: the Newton step of the current nominal.
+  int lq_solve(const VecOfMatXd& gx, const VecOfMatXd& gu, const MatrixXd& dx0, VecOfMatXd& dxs, VecOfMatXd& dus, VecOfMatXd* dlam = nullptr,
+               double mu = 0.0, bool hold_clamped = true) const {
+    if (!engine_) throw std::logic_error("lq_solve(): no trajectory initialised");
+    const int n = model->x_dims, m = model->u_dims;
+    const bool has_x = dx0.rows() != 0 || dx0.cols() != 0;
+    if (!has_x && gx.empty() && gu.empty()) throw std::invalid_argument("lq_solve(): gx, gu and dx0 are all empty");
+    const int S = (int)(!gx.empty() ? gx[0].cols() : !gu.empty() ? gu[0].cols() : dx0.cols());
+    if ((!gx.empty() && (int)gx.size() != T + 1) || (!gu.empty() && (int)gu.size() != T))
+      throw std::invalid_argument("lq_solve(): gx holds T + 1 matrices, gu T");
+    std::vector<double> x0v, gxv, guv, xs, us, lam;
+    if (has_x) x0v = flatten_dirs(&dx0, 1, n, S, "lq_solve(): dx0 is nx x n_dirs");
+    if (!gx.empty()) gxv = flatten_dirs(gx.data(), T + 1, n, S, "lq_solve(): every gx[t] is nx x n_dirs");
+    if (!gu.empty()) guv = flatten_dirs(gu.data(), T, m, S, "lq_solve(): every gu[t] is nu x n_dirs");
+    const std::vector<int> info =
+        engine_->lq_solve(S, has_x ? &x0v : nullptr, !gx.empty() ? &gxv : nullptr, !gu.empty() ? &guv : nullptr, &xs, &us, dlam ? &lam : nullptr, mu, hold_clamped);
+    dxs = unflatten_dirs(xs, T + 1, n, S);
+    dus = unflatten_dirs(us, T, m, S);
+    if (dlam) *dlam = unflatten_dirs(lam, T + 1, n, S);
+    return info[0];
   }
   // the control the stored policy gives at knot t in the state x: us[t] + K[t](x - xs[t]), evaluated on the device (ilqr_evaluate_policy, one knot)
   VectorXd feedback_control(int t, const VectorXd& x) const {
