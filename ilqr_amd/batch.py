@@ -451,6 +451,52 @@ class BatchILQR:
         the handle's stream, nothing waited for."""
         self._check(self.lib.ilqr_copy_covariance_to_device(self.h, int(t0), int(n), Sigma0_ptr, W_ptr, Sigma_ptr, Su_ptr, expected_cost_ptr))
 
+    def _mat_input(self, M, rows, cols):
+        """[B][rows][cols] or one (rows, cols) matrix for all -> canonical [B][rows*cols], column-major per matrix (None stays None)."""
+        if M is None:
+            return None
+        M = np.broadcast_to(np.asarray(M, dtype=np.float64), (self.B, rows, cols))
+        return np.ascontiguousarray(np.swapaxes(M, -1, -2))
+
+    def estimator(self, H, P0=None, W=None, V=None, t0=0, n_knots=None, Pf=True, L=True, Pp=False, Sigma=False, Su=False, expected_cost=False,
+                  info=False):
+        """The Kalman filter of the stored linearisation for the measurement y = H x + v, v ~ (0, V), process noise W and prior covariance
+        P0, and the covariance of the loop u = us[t] + K[t](xhat[t] - xs[t]) that feeds back on its estimate, over the knots
+        [t0, t0 + n_knots) (n_knots=None: up to knot T, up to knot T - 1 with Su).  H: [B][ny][nx], V: [B][ny][ny], P0, W: [B][nx][nx], or
+        one matrix for all; P0, W None = zero.  Returns a dict with the members asked for: Pp, Pf, Sigma [B][n_knots][nx][nx] (the
+        estimate-error covariance before and after the knot's measurement; the covariance of x - xs), L [B][n_knots][nx][ny] (the Kalman
+        gains), Su [B][n_knots][nu][nu], expected_cost [B], info int32 [B] (0, or the knot of a failed factorisation + 1: that
+        trajectory's outputs are NaN).  include/ilqr_amd.h, ilqr_get_estimator: recomputed on the device from the current records and the
+        stored gains; synchronises."""
+        if H is None or V is None:
+            raise ValueError("estimator: H and V are required")
+        H = np.asarray(H, dtype=np.float64)
+        if H.ndim not in (2, 3) or H.shape[-1] != self.nx:
+            raise ValueError("estimator: H must be [B][ny][nx] or (ny, nx), got %s" % (H.shape,))
+        ny = int(H.shape[-2])
+        n = self.T + (0 if Su else 1) - int(t0) if n_knots is None else int(n_knots)
+        nk = max(n, 0)
+        Hc, Vc = self._mat_input(H, ny, self.nx), self._mat_input(V, ny, ny)
+        P0c, Wc = self._cov_input(P0), self._cov_input(W)
+        nn = lambda want: np.zeros((self.B, nk, self.nx, self.nx)) if want else None  # memory: column-major nx x nx
+        o = dict(Pp=nn(Pp), Pf=nn(Pf), L=np.zeros((self.B, nk, ny, self.nx)) if L else None, Sigma=nn(Sigma),
+                 Su=np.zeros((self.B, nk, self.nu, self.nu)) if Su else None, expected_cost=np.zeros(self.B) if expected_cost else None)
+        flags = np.zeros(self.B, dtype=np.int32) if info else None
+        self._check(self.lib.ilqr_get_estimator(self.h, int(t0), n, ny, _p(Hc), _p(P0c), _p(Wc), _p(Vc), _p(o["Pp"]), _p(o["Pf"]), _p(o["L"]),
+                                                _p(o["Sigma"]), _p(o["Su"]), _p(o["expected_cost"]), _pi(flags)))
+        out = {name: (a if name == "expected_cost" else np.swapaxes(a, -1, -2)) for name, a in o.items() if a is not None}
+        if info:
+            out["info"] = flags
+        return out
+
+    def copy_estimator_to_device(self, t0, n_knots, ny, H_ptr, V_ptr, P0_ptr=None, W_ptr=None, Pp_ptr=None, Pf_ptr=None, L_ptr=None, Sigma_ptr=None,
+                                 Su_ptr=None, expected_cost_ptr=None, info_ptr=None):
+        """The same with raw device pointers (e.g. torch.Tensor.data_ptr()) to float64 H [B][ny*nx], V [B][ny*ny], P0, W [B][nx*nx] (None =
+        zero), Pp, Pf, Sigma [B][n_knots][nx*nx], L [B][n_knots][nx*ny], Su [B][n_knots][nu*nu] (column-major per matrix), expected_cost [B]
+        and int32 info [B]; any output may be None, not all of the first six.  Enqueued on the handle's stream, nothing waited for."""
+        self._check(self.lib.ilqr_copy_estimator_to_device(self.h, int(t0), int(n_knots), int(ny), H_ptr, P0_ptr, W_ptr, V_ptr, Pp_ptr, Pf_ptr, L_ptr,
+                                                           Sigma_ptr, Su_ptr, expected_cost_ptr, info_ptr))
+
     def _dirs_input(self, a, lead, width, what):
         """[B] + lead + [S][width], or without the direction axis (one direction) -> (canonical array or None, S, one direction?)"""
         if a is None:

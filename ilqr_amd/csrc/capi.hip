@@ -29,6 +29,8 @@
 #include "sensitivity_wave.hpp"
 #include "lq_solve_thread.hpp"
 #include "lq_solve_wave.hpp"
+#include "estimator_thread.hpp"
+#include "estimator_wave.hpp"
 #include "evaluate.hpp"
 #include "clone.hpp"
 
@@ -89,6 +91,7 @@ void ilqr_destroy(ilqr_batch* h) {
   for (void* p : h->allocs) (void)hipFree(p);
   if (h->staging) (void)hipFree(h->staging);
   if (h->lq_scratch) (void)hipFree(h->lq_scratch);
+  if (h->est_scratch) (void)hipFree(h->est_scratch);
   if (h->d_perm) (void)hipFree(h->d_perm);
   if (h->perm_scratch) (void)hipFree(h->perm_scratch);
   (void)timers_drain(h);  // (every event back into the pool, each once)
@@ -1224,6 +1227,83 @@ int ilqr_solve_lq(ilqr_batch* h, int n_dirs, int flags, double mu, const double*
   if (dus) HIPCHK(hipMemcpyAsync(dus, d_dus, n_dus * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (dlam) HIPCHK(hipMemcpyAsync(dlam, d_dl, n_dl * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (info) HIPCHK(hipMemcpyAsync(info, d_info, (size_t)h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// ---- the Kalman filter of the stored linearisation and the output-feedback covariance (additive under ABI 6; estimator_wave.hpp) ------
+// every refusal the two calls share -- before anything is enqueued --, then the records as ilqr_get_derivatives would return them now
+static int prepare_estimator(ilqr_batch* h, int t0, int n_knots, int ny, const void* H, const void* V, const void* Pp, const void* Pf, const void* L,
+                             const void* Sigma, const void* Su, const void* expected_cost, const char* who) {
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  REQUIRE(ny >= 1 && ny <= h->nx, "%s: ny %d must be in [1, nx = %d]", who, ny, h->nx);
+  REQUIRE(H && V, "%s: H and V are required", who);
+  REQUIRE(t0 >= 0 && n_knots >= 1 && t0 <= h->T && n_knots <= h->T + 1 - t0, "%s: window [%d, %d): inside [0, T = %d], at least one knot", who, t0, t0 + n_knots, h->T);
+  REQUIRE(!Su || n_knots <= h->T - t0, "%s: window [%d, %d) with Su: knot T = %d has no control", who, t0, t0 + n_knots, h->T);
+  REQUIRE(Pp || Pf || L || Sigma || Su || expected_cost, "%s: Pp, Pf, L, Sigma, Su and expected_cost are all null", who);
+  const long long widest = (long long)h->B * (h->T + 1) * h->nx * h->nx;
+  REQUIRE(widest <= (long long)INT_MAX, "%s: B * (T + 1) * nx * nx = %lld elements do not fit an int", who, widest);
+  if (!h->initialised) return fail(ILQR_ERR_STATE, "%s before ilqr_init_traj/ilqr_set_trajectory: no records are stored", who);
+  HIPCHK(hipSetDevice(h->device));
+  return materialise_records(h);
+}
+// The scratch of one call (include/ilqr_amd.h states the formula), carved up; then the kernels.
+static int run_estimator(ilqr_batch* h, EstArgs q, const char* who) {
+  const size_t n_fail = ((size_t)h->B + 1) / 2;
+  const size_t n_mat = (h->aos && est_closed(q)) ? (size_t)h->B * (est_last_knot(q, h->T) + 1) * h->nx * h->nx : 0;
+  if (int rc = ensure_est_scratch(h, n_fail + 2 * n_mat)) return rc;
+  q.fail = (int*)h->est_scratch;
+  q.Pfs = n_mat ? h->est_scratch + n_fail : nullptr;
+  q.Ns = n_mat ? q.Pfs + n_mat : nullptr;
+  const char* kernel = "";
+  const int rc = launch_estimator(h, q, &kernel);
+  return name_refused_kernel(rc, who, kernel);
+}
+
+int ilqr_copy_estimator_to_device(ilqr_batch* h, int t0, int n_knots, int ny, const void* H_device, const void* P0_device, const void* W_device,
+                                  const void* V_device, void* Pp_device, void* Pf_device, void* L_device, void* Sigma_device, void* Su_device,
+                                  void* expected_cost_device, void* info_device) {
+  const char* who = "ilqr_copy_estimator_to_device";
+  if (int rc = prepare_estimator(h, t0, n_knots, ny, H_device, V_device, Pp_device, Pf_device, L_device, Sigma_device, Su_device, expected_cost_device, who)) return rc;
+  return run_estimator(h, {t0, n_knots, ny, (const double*)H_device, (const double*)P0_device, (const double*)W_device, (const double*)V_device,
+                           (double*)Pp_device, (double*)Pf_device, (double*)L_device, (double*)Sigma_device, (double*)Su_device,
+                           (double*)expected_cost_device, (int*)info_device, nullptr, nullptr, nullptr}, who);
+}
+
+int ilqr_get_estimator(ilqr_batch* h, int t0, int n_knots, int ny, const double* H, const double* P0, const double* W, const double* V, double* Pp,
+                       double* Pf, double* L, double* Sigma, double* Su, double* expected_cost, int* info) {
+  const char* who = "ilqr_get_estimator";
+  if (int rc = prepare_estimator(h, t0, n_knots, ny, H, V, Pp, Pf, L, Sigma, Su, expected_cost, who)) return rc;
+  // a call-sized device buffer (the staging buffer: the four inputs, the six outputs, info), the inputs copied up, the outputs copied out
+  // and waited for
+  const size_t B = (size_t)h->B, nn = B * h->nx * h->nx;
+  const size_t n_in[4] = {B * ny * h->nx, P0 ? nn : 0, W ? nn : 0, B * ny * ny};
+  const size_t n_out[7] = {Pp ? nn * n_knots : 0, Pf ? nn * n_knots : 0, L ? B * n_knots * h->nx * ny : 0, Sigma ? nn * n_knots : 0,
+                           Su ? B * n_knots * h->nu * h->nu : 0, expected_cost ? B : 0, info ? (B + 1) / 2 : 0};
+  size_t total = 0;
+  for (size_t e : n_in) total += e;
+  for (size_t e : n_out) total += e;
+  if (int rc = ensure_staging(h, total)) return rc;
+  const double* const src[4] = {H, P0, W, V};
+  double* d_in[4];
+  double* d_out[7];
+  double* at = h->staging;
+  for (int i = 0; i < 4; i++) {
+    d_in[i] = n_in[i] ? at : nullptr;
+    at += n_in[i];
+    if (n_in[i]) HIPCHK(hipMemcpyAsync(d_in[i], src[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  }
+  for (int i = 0; i < 7; i++) {
+    d_out[i] = n_out[i] ? at : nullptr;
+    at += n_out[i];
+  }
+  if (int rc = run_estimator(h, {t0, n_knots, ny, d_in[0], d_in[1], d_in[2], d_in[3], d_out[0], d_out[1], d_out[2], d_out[3], d_out[4], d_out[5],
+                                 (int*)d_out[6], nullptr, nullptr, nullptr}, who))
+    return rc;
+  double* const dst[6] = {Pp, Pf, L, Sigma, Su, expected_cost};
+  for (int i = 0; i < 6; i++)
+    if (dst[i]) HIPCHK(hipMemcpyAsync(dst[i], d_out[i], n_out[i] * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (info) HIPCHK(hipMemcpyAsync(info, d_out[6], B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }

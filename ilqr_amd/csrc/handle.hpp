@@ -74,6 +74,10 @@ struct ilqr_batch {
   // next call's fits (ensure_lq_scratch), freed with the handle
   double* lq_scratch = nullptr;
   size_t lq_scratch_elems = 0;
+  // ilqr_get_estimator's call-sized scratch (estimator_wave.hpp: the failure marks, Pf and N of every knot on the generic layout): as
+  // lq_scratch, allocated by the first call, kept while the next call's fits (ensure_est_scratch), freed with the handle
+  double* est_scratch = nullptr;
+  size_t est_scratch_elems = 0;
   // v is the view every entry point addresses arrays through; for an fp32 handle its trajectory pointers hold
   // the addresses of FLOAT arrays (never dereferenced as double: kernels get vf, the same addresses typed float*)
   BatchView v;
@@ -327,6 +331,18 @@ static int ensure_lq_scratch(ilqr_batch* h, size_t elems) {
   }
   HIPCHK(hipMalloc((void**)&h->lq_scratch, elems * sizeof(double)));
   h->lq_scratch_elems = elems;
+  return 0;
+}
+static int ensure_est_scratch(ilqr_batch* h, size_t elems) {
+  if (elems <= h->est_scratch_elems) return 0;
+  if (h->est_scratch) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipFree(h->est_scratch));
+    h->est_scratch = nullptr;
+    h->est_scratch_elems = 0;
+  }
+  HIPCHK(hipMalloc((void**)&h->est_scratch, elems * sizeof(double)));
+  h->est_scratch_elems = elems;
   return 0;
 }
 // One of the handle's arrays as the conversions take it: S knots of E elements per trajectory, of which the knots [t0, t0 + n) are moved

@@ -530,6 +530,54 @@ static int launch_lq_solve(ilqr_batch* h, const LqArgs& q, const char** name) {
   return 0;
 }
 
+// The Kalman filter of the stored linearisation and the covariance of the output-feedback loop (ilqr_get_estimator /
+// ilqr_copy_estimator_to_device; estimator_wave.hpp, estimator_thread.hpp): as launch_covariance, picked by the handle's layout and sizes
+// alone.  The caller has materialised the records, checked ny and the window and sized the scratch.  Generic layout: the filter sweep by
+// (state tiles, output tiles), then -- if Sigma, Su or the expected cost is asked for -- the loop sweep by (state tiles, control tiles),
+// one wavefront per trajectory each; tiled layout: one kernel, one thread per trajectory.
+static int launch_estimator(ilqr_batch* h, const EstArgs& q, const char** name) {
+  const WaveVariant w = value_wave_variant(h->nx, h->nu, h->dtype);
+  const int yt = q.ny > 16 ? 2 : 1;
+  *name = estimator_kernel_name(h->aos, w.nt, yt);
+  if (!h->aos) {
+    const dim3 grid(h->Bp / 64), block(64);
+    if (int rc = with_model(h, [&](auto& v, auto& m, auto&) {
+          hipLaunchKernelGGL((k_estimator_t<std::decay_t<decltype(m)>>), grid, block, 0, h->stream, v, q);
+          return 0;
+        }))
+      return rc;
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  if (int rc = with_int<1, 2>(w.nt, [&](auto nt) { return with_int<1, 2>(yt, [&](auto ytc) { return with_bool(w.f32, [&](auto f32) {
+        constexpr int NT = decltype(nt)::value, YT = decltype(ytc)::value;
+        using S = std::conditional_t<decltype(f32)::value, float, double>;
+        if constexpr (YT > NT) {  // (ny <= nx: the caller has checked)
+          return fail(ILQR_ERR_INVALID, "%s: ny %d beyond nx %d", *name, q.ny, h->nx);
+        } else {
+          hipLaunchKernelGGL((k_est_filter_w<NT, YT, S>), dim3(h->B), dim3(64), 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
+          return 0;
+        }
+      }); }); }))
+    return rc;
+  HIPCHK(hipGetLastError());
+  if (!est_closed(q)) return 0;
+  *name = estimator_loop_kernel_name(w);
+  if (int rc = with_int<1, 2>(w.nt, [&](auto nt) { return with_int<1, 2>(w.mt, [&](auto mt) { return with_bool(w.f32, [&](auto f32) {
+        constexpr int MT = decltype(mt)::value;
+        using S = std::conditional_t<decltype(f32)::value, float, double>;
+        if constexpr (MT == 2 && decltype(f32)::value) {  // float storage: never with two control tiles (ilqr_create)
+          return fail(ILQR_ERR_UNSUPPORTED, "%s: no fp32 handle has more than %d controls", *name, WM);
+        } else {
+          hipLaunchKernelGGL((k_est_loop_w<decltype(nt)::value, MT, S>), dim3(h->B), dim3(64), 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
+          return 0;
+        }
+      }); }); }))
+    return rc;
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // The stored policy applied to caller-given states (ilqr_evaluate_policy / _on_device; evaluate.hpp): picked by the handle's layout alone,
 // as launch_value -- no route bit, no stage timer.  One thread per rollout, B * S of them (the caller has checked that they fit an int).
 static int launch_evaluate(ilqr_batch* h, const EvalArgs& e, const char** name) {

@@ -68,6 +68,14 @@ inline const char* lq_solve_kernel_name(bool aos, const WaveVariant& w) {  // k_
   static const char* const kWave[2][2] = {{"k_lq_gain_w<1, 1>", "k_lq_gain_w<1, 2>"}, {"k_lq_gain_w<2, 1>", "k_lq_gain_w<2, 2>"}};
   return aos ? kWave[w.nt - 1][w.mt - 1] : "k_lq_gain_t";
 }
+inline const char* estimator_kernel_name(bool aos, int nt, int yt) {  // k_est_filter_w by (state tiles, output tiles: ny <= 16 yt <= 16 nt)
+  static const char* const kWave[2][2] = {{"k_est_filter_w<1, 1>", "k_est_filter_w<1, 2>"}, {"k_est_filter_w<2, 1>", "k_est_filter_w<2, 2>"}};
+  return aos ? kWave[nt - 1][yt - 1] : "k_estimator_t";
+}
+inline const char* estimator_loop_kernel_name(const WaveVariant& w) {  // k_est_loop_w: the variants value_wave_variant yields
+  static const char* const kWave[2][2] = {{"k_est_loop_w<1, 1>", "k_est_loop_w<1, 2>"}, {"k_est_loop_w<2, 1>", "k_est_loop_w<2, 2>"}};
+  return kWave[w.nt - 1][w.mt - 1];
+}
 inline const char* evaluate_kernel_name(bool aos, bool traj_params) { return !aos ? "k_evaluate_t" : traj_params ? "k_evaluate_g<PT>" : "k_evaluate_g"; }
 
 struct RouteInputs {

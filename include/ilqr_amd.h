@@ -506,6 +506,64 @@ int ilqr_solve_lq(ilqr_batch* h, int n_dirs, int flags, double mu, const double*
 int ilqr_solve_lq_on_device(ilqr_batch* h, int n_dirs, int flags, double mu, const void* dx0_device, const void* gx_device, const void* gu_device,
                             void* dxs_device, void* dus_device, void* dlam_device, void* info_device);
 
+/* ---- the Kalman filter of the stored linearisation and the covariance of the output-feedback loop (additive under ABI 6) --------------
+ * ilqr_get_covariance answers for a controller that sees the true state.  A real loop measures y = H x + v, v ~ (0, V), and feeds back on
+ * an estimate: u = us[t] + K[t](xhat[t] - xs[t]).  These calls give the time-varying Kalman gains L[t] along the stored linearisation, the
+ * estimate-error covariances before (Pp) and after (Pf) the measurement of each knot, and the covariance and expected cost of the loop that
+ * actually runs -- the other half of iLQG.  DEFINITION -- from the derivative records ilqr_get_derivatives would return at this moment
+ * (see there for which trajectory they describe) and the stored gains K; k, us, xs, cx and cu are not read.  ny is the number of measured
+ * outputs, 1 <= ny <= nx; sym(M) = (M + M')/2:
+ *     Pp[0] = P0[b]                                        (as given, not symmetrised; NULL = zero)
+ *     Xh    = 0                                            (covariance of the estimate's deviation from xs; the plan starts at the prior mean)
+ *     t = 0 .. T:
+ *         S      = sym(H Pp[t] H' + V)                     (ny x ny)
+ *         S      = R R'   lower Cholesky in index order; a pivot <= 0 or not finite ends this trajectory: info[b] = t + 1
+ *         L[t]   = Pp[t] H' S^-1                           (nx x ny; by forward and back substitution with R, not an explicit inverse)
+ *         G      = I - L[t] H
+ *         Pf[t]  = sym(G Pp[t] G' + L[t] V L[t]')          (Joseph form)
+ *         N      = sym(L[t] S L[t]')
+ *         Xh     = sym(N)  if t == 0  else  sym(A Xh A' + N)          (A of the previous knot)
+ *         Sigma[t] = Xh + Pf[t]
+ *         J     += 1/2 <cxx[t], Sigma[t]>
+ *         if t < T:
+ *             Z = Xh K[t]',  Su[t] = sym(K[t] Z),  J += 1/2 (<cuu[t], Su[t]> + 2 <cxu[t], Z>)
+ *             A = fx[t] + fu[t] K[t]
+ *             Pp[t+1] = sym(fx[t] Pf[t] fx[t]' + W)        (W NULL = zero)
+ * Pp, Pf and L are the filter and do not depend on K.  Sigma[t] is the covariance of x[t] - xs[t], Su[t] that of the feedback part of
+ * u[t], J the expected cost above the nominal's, to second order, when the feedback acts on the filtered estimate.  The estimation error
+ * of the optimal filter is orthogonal to the estimate, which is why the covariance of the true state splits into the two n x n recursions
+ * Xh and Pf and no 2n x 2n joint covariance is formed.
+ * What this is NOT: it is the filter of the LINEARISATION ABOUT THE NOMINAL, not an EKF relinearised at the estimate.  H, W and V are the
+ * same at every knot.  Saturation of the feedback is not modelled.  The split Sigma = Xh + Pf holds for the gain L defined here and for no
+ * other.
+ * Every array is canonical double on every handle, matrices column-major:
+ *     in:  H [B][ny*nx] (ny rows)   P0, W [B][nx*nx]   V [B][ny*ny]                                  (H and V are required)
+ *     out: Pp, Pf, Sigma [B][n_knots][nx*nx]   L [B][n_knots][nx*ny]   Su [B][n_knots][nu*nu]   expected_cost [B]   info int32 [B]
+ * Any output may be NULL, not all of Pp, Pf, L, Sigma, Su and expected_cost.  Only the window [t0, t0 + n_knots) is stored: it lies inside
+ * [0, T] and holds at least one knot; with Su requested it lies inside [0, T) (knot T has no control).  The recursion runs from knot 0 to
+ * the last knot anything needs: T when expected_cost is requested, else t0 + n_knots - 1.
+ * All arithmetic is double on every handle (an fp32 handle's stored floats are widened).  Every model, ILQR_MODEL_HOST included, both
+ * dtypes.  Read-only: later iterations are bit for bit those of a handle that never asked.  What is computed at a knot does not depend on
+ * which outputs were asked for, only on whether it is computed: a window is a slice of the full call, bit for bit, and Pp, Pf and L have
+ * the same bits whether or not Sigma, Su or expected_cost are requested.  Pp[0] is P0 to the bit; Pf, Sigma, Su and Pp[t >= 1] are
+ * symmetric to the bit.  A failed trajectory gets quiet NaNs in every output it has, over the whole window, plus its info[b]; it changes no
+ * other trajectory's bits (a pivot past the last knot the recursion reaches is not met: info[b] = 0).  The arrays of a call do not overlap.
+ * SCRATCH: the handle keeps one device buffer for these calls, allocated by the first call and kept while the next one's fits, of
+ *     ceil(B / 2) + [generic layout, and Sigma, Su or expected_cost asked for] 2 * B * (last + 1) * nx * nx   doubles,
+ * last the last knot the recursion reaches: the failure marks, and Pf and N of every knot on their way from the filter sweep to the
+ * closed-loop sweep (the nx = 4 kernels' layout runs one sweep and keeps them in registers).  At nx = 32, B = 8192, T = 200 with the
+ * expected cost that is 27 GB.
+ * ILQR_ERR_INVALID: null handle, ny outside [1, nx], NULL H or V, a bad window, a window with knot T when Su is requested, all six outputs
+ * NULL, B * (T + 1) * nx * nx beyond INT_MAX; ILQR_ERR_STATE: before ilqr_init_traj / ilqr_set_trajectory.  Every refusal happens before
+ * anything is enqueued. */
+/* host arrays: a call-sized device buffer takes the inputs up and the window down; synchronises */
+int ilqr_get_estimator(ilqr_batch* h, int t0, int n_knots, int ny, const double* H, const double* P0, const double* W, const double* V,
+                       double* Pp, double* Pf, double* L, double* Sigma, double* Su, double* expected_cost, int* info);
+/* device memory of this handle's device: enqueued on the handle's stream, nothing waited for (as ilqr_copy_covariance_to_device) */
+int ilqr_copy_estimator_to_device(ilqr_batch* h, int t0, int n_knots, int ny, const void* H_device, const void* P0_device, const void* W_device,
+                                  const void* V_device, void* Pp_device, void* Pf_device, void* L_device, void* Sigma_device, void* Su_device,
+                                  void* expected_cost_device, void* info_device);
+
 /* ---- the stored feedback policy applied to caller-given states (additive under ABI 6) -----------------------------------------------
  * What a solve leaves for a controller is the time-varying law u = us[t] + K[t](x - xs[t]).  These calls apply it to states the CALLER
  * holds -- n_samples of them per trajectory, at knot t0 -- and roll it through the handle's device model for n_knots knots; a read-only

@@ -400,6 +400,39 @@ class BatchILQR {
     check(ilqr_copy_covariance_to_device(h_, t0, n_knots, Sigma0_device, W_device, Sigma_device, Su_device, expected_cost_device),
           "ilqr_copy_covariance_to_device");
   }
+  // The Kalman filter of the stored linearisation and the covariance of the loop that feeds back on its estimate (ilqr_get_estimator) over
+  // the knots [t0, t0 + n_knots), n_knots < 0: up to knot T (up to knot T - 1 when Su is asked for).  ny measured outputs; H [B][ny*nx],
+  // V [B][ny*ny] (required), P0, W [B][nx*nx] (null = zero); Pp, Pf, Sigma [B][n_knots][nx*nx], L [B][n_knots][nx*ny], Su
+  // [B][n_knots][nu*nu] (column-major per matrix), expected_cost [B], info [B]; any output may be null, not all of the first six.
+  void estimator(int ny, const std::vector<double>& H, const std::vector<double>* P0, const std::vector<double>* W, const std::vector<double>& V,
+                 std::vector<double>* Pp, std::vector<double>* Pf, std::vector<double>* L, std::vector<double>* Sigma = nullptr,
+                 std::vector<double>* Su = nullptr, std::vector<double>* expected_cost = nullptr, std::vector<int>* info = nullptr, int t0 = 0,
+                 int n_knots = -1) {
+    if (n_knots < 0) n_knots = T_ + (Su ? 0 : 1) - t0;
+    if (ny < 1 || ny > n_) throw std::invalid_argument("estimator(): ny must be in [1, nx]");
+    const size_t mat = (size_t)B_ * n_ * n_, knots = (size_t)B_ * (n_knots > 0 ? n_knots : 0);
+    if (H.size() != (size_t)B_ * ny * n_ || V.size() != (size_t)B_ * ny * ny) throw std::invalid_argument("estimator(): H is [B][ny*nx], V is [B][ny*ny]");
+    if ((P0 && P0->size() != mat) || (W && W->size() != mat)) throw std::invalid_argument("estimator(): P0 and W are [B][nx*nx]");
+    if (Pp) Pp->assign(knots * n_ * n_, 0.0);
+    if (Pf) Pf->assign(knots * n_ * n_, 0.0);
+    if (L) L->assign(knots * n_ * ny, 0.0);
+    if (Sigma) Sigma->assign(knots * n_ * n_, 0.0);
+    if (Su) Su->assign(knots * m_ * m_, 0.0);
+    if (expected_cost) expected_cost->assign(B_, 0.0);
+    if (info) info->assign(B_, 0);
+    check(ilqr_get_estimator(h_, t0, n_knots, ny, H.data(), P0 ? P0->data() : nullptr, W ? W->data() : nullptr, V.data(), Pp ? Pp->data() : nullptr,
+                             Pf ? Pf->data() : nullptr, L ? L->data() : nullptr, Sigma ? Sigma->data() : nullptr, Su ? Su->data() : nullptr,
+                             expected_cost ? expected_cost->data() : nullptr, info ? info->data() : nullptr),
+          "ilqr_get_estimator");
+  }
+  // ... or from and into caller-owned device memory, on the handle's stream, nothing waited for
+  void copy_estimator_to_device(int t0, int n_knots, int ny, const void* H_device, const void* P0_device, const void* W_device, const void* V_device,
+                                void* Pp_device, void* Pf_device, void* L_device, void* Sigma_device, void* Su_device, void* expected_cost_device,
+                                void* info_device) {
+    check(ilqr_copy_estimator_to_device(h_, t0, n_knots, ny, H_device, P0_device, W_device, V_device, Pp_device, Pf_device, L_device, Sigma_device,
+                                        Su_device, expected_cost_device, info_device),
+          "ilqr_copy_estimator_to_device");
+  }
   // The tangent of the linearised closed loop (ilqr_get_tangent) over the knots [t0, t0 + n_knots), n_knots < 0: up to knot T: n_dirs
   // directions per trajectory, dx0 [B][n_dirs][nx] and dv [B][T][n_dirs][nu] (null = zero, not both); dxs [B][n_knots][n_dirs][nx], dus
   // [B][nku][n_dirs][nu] over the window's nku knots with a control; either output may be null, not both.
