@@ -497,6 +497,41 @@ class BatchILQR:
         self._check(self.lib.ilqr_copy_estimator_to_device(self.h, int(t0), int(n_knots), int(ny), H_ptr, P0_ptr, W_ptr, V_ptr, Pp_ptr, Pf_ptr, L_ptr,
                                                            Sigma_ptr, Su_ptr, expected_cost_ptr, info_ptr))
 
+    def risk_sensitive(self, C, theta, mu=0.0, hold_clamped=False, K=True, k=True, Vx=False, Vxx=False, risk_cost=False, info=False):
+        """The risk-sensitive (LEQG) gains and value of the LQ model the records hold, for the noise dx[t+1] += C xi, xi ~ N(0, I):
+        (K, k) minimise (1/theta) log E exp(theta J).  C: [B][nx][nw] or one (nx, nw) matrix for all, 1 <= nw <= nx (W = C C' is
+        covariance()'s process noise); theta > 0 risk-averse, < 0 risk-seeking, 0 the gains solve_lq computes.  mu, hold_clamped: as
+        solve_lq.  Returns a dict with the members asked for: K [B][T][nu][nx], k [B][T][nu] (what set_gains takes), Vx [B][T+1][nx],
+        Vxx [B][T+1][nx][nx], risk_cost [B], info int32 [B] (0; -(knot + 1): breakdown, the risk-sensitive cost at this theta is
+        infinite; knot + 1: Quu is not positive definite on the free controls; either way that trajectory's outputs are NaN).
+        include/ilqr_amd.h, ilqr_get_risk_sensitive: recomputed on the device from the current records; synchronises."""
+        if C is None:
+            raise ValueError("risk_sensitive: C is required")
+        C = np.asarray(C, dtype=np.float64)
+        if C.ndim not in (2, 3) or C.shape[-2] != self.nx:
+            raise ValueError("risk_sensitive: C must be [B][nx][nw] or (nx, nw), got %s" % (C.shape,))
+        nw = int(C.shape[-1])
+        Cc = self._mat_input(C, self.nx, nw)
+        B, T, n, m = self.B, self.T, self.nx, self.nu
+        o = dict(K=np.zeros((B, T, n, m)) if K else None,  # memory: column-major nu x nx
+                 k=np.zeros((B, T, m)) if k else None, Vx=np.zeros((B, T + 1, n)) if Vx else None,
+                 Vxx=np.zeros((B, T + 1, n, n)) if Vxx else None, risk_cost=np.zeros(B) if risk_cost else None)
+        flags = np.zeros(B, dtype=np.int32) if info else None
+        self._check(self.lib.ilqr_get_risk_sensitive(self.h, nw, float(theta), capi.LQ_HOLD_CLAMPED if hold_clamped else 0, float(mu), _p(Cc),
+                                                     _p(o["K"]), _p(o["k"]), _p(o["Vx"]), _p(o["Vxx"]), _p(o["risk_cost"]), _pi(flags)))
+        out = {name: (np.swapaxes(a, -1, -2) if name in ("K", "Vxx") else a) for name, a in o.items() if a is not None}
+        if info:
+            out["info"] = flags
+        return out
+
+    def copy_risk_sensitive_to_device(self, nw, theta, C_ptr, mu=0.0, hold_clamped=False, K_ptr=None, k_ptr=None, Vx_ptr=None, Vxx_ptr=None,
+                                      risk_cost_ptr=None, info_ptr=None):
+        """The same with raw device pointers (e.g. torch.Tensor.data_ptr()) to float64 C [B][nx*nw], K [B][T][nu*nx], k [B][T][nu], Vx
+        [B][T+1][nx], Vxx [B][T+1][nx*nx] (column-major per matrix), risk_cost [B] and int32 info [B]; any output may be None, not all of
+        the first five.  Enqueued on the handle's stream, nothing waited for."""
+        self._check(self.lib.ilqr_copy_risk_sensitive_to_device(self.h, int(nw), float(theta), capi.LQ_HOLD_CLAMPED if hold_clamped else 0,
+                                                                float(mu), C_ptr, K_ptr, k_ptr, Vx_ptr, Vxx_ptr, risk_cost_ptr, info_ptr))
+
     def _dirs_input(self, a, lead, width, what):
         """[B] + lead + [S][width], or without the direction axis (one direction) -> (canonical array or None, S, one direction?)"""
         if a is None:

@@ -83,6 +83,8 @@ SYMBOLS = {
     "ilqr_solve_lq_on_device": (C.c_int, [_H, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ilqr_get_estimator": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "ilqr_copy_estimator_to_device": (C.c_int, [_H, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11),
+    "ilqr_get_risk_sensitive": (C.c_int, [_H, C.c_int, C.c_double, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "ilqr_copy_risk_sensitive_to_device": (C.c_int, [_H, C.c_int, C.c_double, C.c_int, C.c_double] + [C.c_void_p] * 7),
     "ilqr_evaluate_policy": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
     "ilqr_evaluate_policy_on_device": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ilqr_trajectory_params_count": (C.c_int, []),

@@ -31,6 +31,8 @@
 #include "lq_solve_wave.hpp"
 #include "estimator_thread.hpp"
 #include "estimator_wave.hpp"
+#include "risk_thread.hpp"
+#include "risk_wave.hpp"
 #include "evaluate.hpp"
 #include "clone.hpp"
 
@@ -1304,6 +1306,72 @@ int ilqr_get_estimator(ilqr_batch* h, int t0, int n_knots, int ny, const double*
   for (int i = 0; i < 6; i++)
     if (dst[i]) HIPCHK(hipMemcpyAsync(dst[i], d_out[i], n_out[i] * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (info) HIPCHK(hipMemcpyAsync(info, d_out[6], B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// ---- the risk-sensitive (LEQG) gains and value of the records' LQ model (additive under ABI 6; risk_wave.hpp) ------
+// every refusal the two calls share -- before anything is enqueued --, then the records as ilqr_get_derivatives would return them now
+static int prepare_risk(ilqr_batch* h, int nw, double theta, int flags, double mu, const void* C, const void* K, const void* k, const void* Vx,
+                        const void* Vxx, const void* risk_cost, const char* who) {
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  REQUIRE(nw >= 1 && nw <= h->nx, "%s: nw %d must be in [1, nx = %d]", who, nw, h->nx);
+  REQUIRE(C != nullptr, "%s: C is required", who);
+  REQUIRE((flags & ~ILQR_LQ_HOLD_CLAMPED) == 0, "%s: unknown flag bits 0x%x", who, (unsigned)(flags & ~ILQR_LQ_HOLD_CLAMPED));
+  REQUIRE(mu >= 0.0 && mu <= 1.7976931348623157e308, "%s: mu %g must be finite and >= 0", who, mu);
+  REQUIRE(theta >= -1.7976931348623157e308 && theta <= 1.7976931348623157e308, "%s: theta %g must be finite", who, theta);
+  REQUIRE(K || k || Vx || Vxx || risk_cost, "%s: K, k, Vx, Vxx and risk_cost are all null", who);
+  const long long widest = (long long)h->B * (h->T + 1) * h->nx * h->nx;
+  REQUIRE(widest <= (long long)INT_MAX, "%s: B * (T + 1) * nx * nx = %lld elements do not fit an int", who, widest);
+  if (!h->initialised) return fail(ILQR_ERR_STATE, "%s before ilqr_init_traj/ilqr_set_trajectory: no records are stored", who);
+  HIPCHK(hipSetDevice(h->device));
+  return materialise_records(h);
+}
+// The failure marks are the only scratch; then the kernel.
+static int run_risk(ilqr_batch* h, RiskArgs q, const char* who) {
+  if (!h->risk_fail)
+    if (int rc = dev_alloc(h, &h->risk_fail, (size_t)h->Bp)) return rc;
+  q.fail = h->risk_fail;
+  const char* kernel = "";
+  const int rc = launch_risk(h, q, &kernel);
+  return name_refused_kernel(rc, who, kernel);
+}
+
+int ilqr_copy_risk_sensitive_to_device(ilqr_batch* h, int nw, double theta, int flags, double mu, const void* C_device, void* K_device, void* k_device,
+                                       void* Vx_device, void* Vxx_device, void* risk_cost_device, void* info_device) {
+  const char* who = "ilqr_copy_risk_sensitive_to_device";
+  if (int rc = prepare_risk(h, nw, theta, flags, mu, C_device, K_device, k_device, Vx_device, Vxx_device, risk_cost_device, who)) return rc;
+  return run_risk(h, {nw, (flags & ILQR_LQ_HOLD_CLAMPED) ? 1 : 0, theta, mu, (const double*)C_device, (double*)K_device, (double*)k_device,
+                      (double*)Vx_device, (double*)Vxx_device, (double*)risk_cost_device, (int*)info_device, nullptr}, who);
+}
+
+int ilqr_get_risk_sensitive(ilqr_batch* h, int nw, double theta, int flags, double mu, const double* C, double* K, double* k, double* Vx, double* Vxx,
+                            double* risk_cost, int* info) {
+  const char* who = "ilqr_get_risk_sensitive";
+  if (int rc = prepare_risk(h, nw, theta, flags, mu, C, K, k, Vx, Vxx, risk_cost, who)) return rc;
+  // a call-sized device buffer (the staging buffer: C, the five outputs, info), C copied up, the outputs copied out and waited for
+  const size_t B = (size_t)h->B, T = (size_t)h->T, n = (size_t)h->nx, m = (size_t)h->nu;
+  const size_t n_c = B * n * nw;
+  const size_t n_out[6] = {K ? B * T * m * n : 0, k ? B * T * m : 0, Vx ? B * (T + 1) * n : 0, Vxx ? B * (T + 1) * n * n : 0, risk_cost ? B : 0,
+                           info ? (B + 1) / 2 : 0};
+  size_t total = n_c;
+  for (size_t e : n_out) total += e;
+  if (int rc = ensure_staging(h, total)) return rc;
+  double* const d_c = h->staging;
+  double* d_out[6];
+  double* at = h->staging + n_c;
+  for (int i = 0; i < 6; i++) {
+    d_out[i] = n_out[i] ? at : nullptr;
+    at += n_out[i];
+  }
+  HIPCHK(hipMemcpyAsync(d_c, C, n_c * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (int rc = run_risk(h, {nw, (flags & ILQR_LQ_HOLD_CLAMPED) ? 1 : 0, theta, mu, d_c, d_out[0], d_out[1], d_out[2], d_out[3], d_out[4],
+                            (int*)d_out[5], nullptr}, who))
+    return rc;
+  double* const dst[5] = {K, k, Vx, Vxx, risk_cost};
+  for (int i = 0; i < 5; i++)
+    if (dst[i]) HIPCHK(hipMemcpyAsync(dst[i], d_out[i], n_out[i] * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (info) HIPCHK(hipMemcpyAsync(info, d_out[5], B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }

@@ -78,6 +78,8 @@ struct ilqr_batch {
   // lq_scratch, allocated by the first call, kept while the next call's fits (ensure_est_scratch), freed with the handle
   double* est_scratch = nullptr;
   size_t est_scratch_elems = 0;
+  // ilqr_get_risk_sensitive's scratch (risk_wave.hpp: the failure marks, [B]): allocated by the first call (dev_alloc: freed with the handle)
+  int* risk_fail = nullptr;
   // v is the view every entry point addresses arrays through; for an fp32 handle its trajectory pointers hold
   // the addresses of FLOAT arrays (never dereferenced as double: kernels get vf, the same addresses typed float*)
   BatchView v;

@@ -578,6 +578,40 @@ static int launch_estimator(ilqr_batch* h, const EstArgs& q, const char** name) 
   return 0;
 }
 
+// The risk-sensitive gains and value of the records' LQ model (ilqr_get_risk_sensitive / ilqr_copy_risk_sensitive_to_device; risk_wave.hpp,
+// risk_thread.hpp): as launch_estimator, picked by the handle's layout and sizes alone.  The caller has materialised the records and
+// checked nw.  Generic layout: one wavefront per trajectory, by (state tiles, control tiles, noise tiles); tiled layout: one thread per
+// trajectory.
+static int launch_risk(ilqr_batch* h, const RiskArgs& q, const char** name) {
+  const WaveVariant w = value_wave_variant(h->nx, h->nu, h->dtype);
+  const int wt = q.nw > 16 ? 2 : 1;
+  *name = risk_kernel_name(h->aos, w, wt);
+  if (!h->aos) {
+    const dim3 grid(h->Bp / 64), block(64);
+    if (int rc = with_model(h, [&](auto& v, auto& m, auto&) {
+          hipLaunchKernelGGL((k_risk_t<std::decay_t<decltype(m)>>), grid, block, 0, h->stream, v, q);
+          return 0;
+        }))
+      return rc;
+  } else if (int rc = with_int<1, 2>(w.nt, [&](auto nt) { return with_int<1, 2>(w.mt, [&](auto mt) { return with_int<1, 2>(wt, [&](auto wtc) {
+               return with_bool(w.f32, [&](auto f32) {
+                 constexpr int NT = decltype(nt)::value, MT = decltype(mt)::value, WT = decltype(wtc)::value;
+                 using S = std::conditional_t<decltype(f32)::value, float, double>;
+                 if constexpr (WT > NT) {  // (nw <= nx: the caller has checked)
+                   return fail(ILQR_ERR_INVALID, "%s: nw %d beyond nx %d", *name, q.nw, h->nx);
+                 } else if constexpr (MT == 2 && decltype(f32)::value) {  // float storage: never with two control tiles (ilqr_create)
+                   return fail(ILQR_ERR_UNSUPPORTED, "%s: no fp32 handle has more than %d controls", *name, WM);
+                 } else {
+                   hipLaunchKernelGGL((k_risk_w<NT, MT, WT, S>), dim3(h->B), dim3(64), 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
+                   return 0;
+                 }
+               });
+             }); }); }))
+    return rc;
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // The stored policy applied to caller-given states (ilqr_evaluate_policy / _on_device; evaluate.hpp): picked by the handle's layout alone,
 // as launch_value -- no route bit, no stage timer.  One thread per rollout, B * S of them (the caller has checked that they fit an int).
 static int launch_evaluate(ilqr_batch* h, const EvalArgs& e, const char** name) {

@@ -76,6 +76,11 @@ inline const char* estimator_loop_kernel_name(const WaveVariant& w) {  // k_est_
   static const char* const kWave[2][2] = {{"k_est_loop_w<1, 1>", "k_est_loop_w<1, 2>"}, {"k_est_loop_w<2, 1>", "k_est_loop_w<2, 2>"}};
   return kWave[w.nt - 1][w.mt - 1];
 }
+inline const char* risk_kernel_name(bool aos, const WaveVariant& w, int wt) {  // k_risk_w by (state, control, noise tiles: nw <= 16 wt <= 16 nt)
+  static const char* const kWave[2][2][2] = {{{"k_risk_w<1, 1, 1>", "k_risk_w<1, 1, 2>"}, {"k_risk_w<1, 2, 1>", "k_risk_w<1, 2, 2>"}},
+                                             {{"k_risk_w<2, 1, 1>", "k_risk_w<2, 1, 2>"}, {"k_risk_w<2, 2, 1>", "k_risk_w<2, 2, 2>"}}};
+  return aos ? kWave[w.nt - 1][w.mt - 1][wt - 1] : "k_risk_t";
+}
 inline const char* evaluate_kernel_name(bool aos, bool traj_params) { return !aos ? "k_evaluate_t" : traj_params ? "k_evaluate_g<PT>" : "k_evaluate_g"; }
 
 struct RouteInputs {

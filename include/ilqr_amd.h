@@ -564,6 +564,58 @@ int ilqr_copy_estimator_to_device(ilqr_batch* h, int t0, int n_knots, int ny, co
                                   const void* V_device, void* Pp_device, void* Pf_device, void* L_device, void* Sigma_device, void* Su_device,
                                   void* expected_cost_device, void* info_device);
 
+/* ---- the risk-sensitive (LEQG) gains and value of the stored LQ model (additive under ABI 6) -----------------------------------------
+ * Every query above is risk-neutral: noise changes the expected cost they report, never the controller (certainty equivalence: the gains
+ * ilqr_solve_lq computes are the same for any W).  These calls give the controller for which the noise matters: (K, k) minimise
+ * (1/theta) log E exp(theta J) over feedback policies for the LQ model of the records with full state observation (Jacobson 1973,
+ * Whittle 1981; iLEQG: Farshidian and Buchli 2015).  theta > 0 is risk-averse: the saddle point of the game in which a disturbance xi is
+ * penalised by |xi|^2 / (2 theta), the soft-constrained H-infinity problem with gamma^2 = 1/theta; its gains are stiffer where the noise
+ * hurts and its feed-forward is pessimistic.  theta < 0 is risk-seeking and never breaks down for convex records.  theta = 0 gives the gains
+ * ilqr_solve_lq computes internally, with risk_cost the expected cost above the nominal's of the Newton step under the noise.
+ * DEFINITION -- the LQ model of the records about the nominal with dx[t+1] = fx dx + fu du + C[b] xi[t], xi ~ N(0, I_nw), 1 <= nw <= nx;
+ * W = C C' is the process noise of ilqr_get_covariance (a factor is asked for, not W, so that rank-deficient noise needs no factorisation
+ * of a singular W).  From the derivative records ilqr_get_derivatives would return at this moment; the stored K is read only to decide the
+ * held set, as in ilqr_solve_lq; k, us, xs are not read.  sym(M) = (M + M')/2; the value at knot t is 1/2 dx'P[t]dx + v[t]'dx + s[t]:
+ *     P[T] = cxx[T] (as stored), v[T] = cx[T], s[T] = 0
+ *     t = T-1 .. 0, with P = P[t+1], v = v[t+1], s = s[t+1]:
+ *         G  = P C                                (nx x nw)
+ *         M  = I - theta * sym(C'G)               (nw x nw)
+ *         M  = R R'   lower Cholesky in index order; a pivot <= 0 or not finite ends this trajectory: info[b] = -(t + 1)   (breakdown)
+ *         Y  = R^-1 G'  (nw x nx),  y = R^-1 (C'v)            forward substitution, no explicit inverse
+ *         Pt = P + theta * Y'Y,     vt = v + theta * Y'y
+ *         st = s + theta/2 * y'y - (1/theta) * sum_j log R(j,j)          theta != 0
+ *         st = s + 1/2 * trace(C'G)                                      theta == 0 exactly
+ *         Qx = cx + fx'vt,  Qu = cu + fu'vt,  Qxx = cxx + fx'Pt fx,  Qux = cxu' + fu'Pt fx,  Quu = cuu + fu'Pt fu + mu I
+ *         held set as ilqr_solve_lq (ILQR_LQ_HOLD_CLAMPED, the only flag bit: rows of the stored K[t] that are exactly zero); F the rest
+ *         Quu_FF = L L'  lower Cholesky over F in index order; a pivot <= 0 or not finite: info[b] = t + 1
+ *         K[t]_F = -Quu_FF^-1 Qux_F,  k[t]_F = -Quu_FF^-1 Qu_F,  held rows exact zeros   (a knot with no free control factors nothing)
+ *         P[t] = sym(Qxx + Qux'K[t]),  v[t] = Qx + K[t]'Qu,  s[t] = st + 1/2 Qu'k[t]
+ *     risk_cost[b] = s[0]
+ * BREAKDOWN is an answer, not an error: info[b] < 0 says that the risk-sensitive cost at that theta is infinite -- the chosen risk aversion
+ * is more than the plan can bear.  risk_cost loses digits as eps/|theta| for tiny non-zero theta.
+ * What this is NOT: it is the LEQG of the LINEARISATION ABOUT THE NOMINAL.  The noise is the same at every knot.  Saturation is not
+ * modelled.  Output feedback is not modelled: the LEQG separation through ilqr_get_estimator is not claimed.
+ * How it is used: ilqr_set_gains(k, K) installs the result, ilqr_rollout_candidates / ilqr_line_search then take the step, and
+ * ilqr_get_covariance and ilqr_evaluate_policy report how the robust gains do.  Installing gains from device memory is out of scope here.
+ * Every array is canonical double on every handle, matrices column-major:
+ *     in:  C [B][nx*nw] (nx rows; required)
+ *     out: K [B][T][nu*nx] (as ilqr_get_gains)   k [B][T][nu]   Vx [B][T+1][nx] = v   Vxx [B][T+1][nx*nx] = P   risk_cost [B]   info int32 [B]
+ * The whole horizon, no windows.  Any output may be NULL, not all of K, k, Vx, Vxx and risk_cost.
+ * All arithmetic is double on every handle (an fp32 handle's stored floats are widened).  Every model, ILQR_MODEL_HOST included, both
+ * dtypes.  Read-only: later iterations are bit for bit those of a handle that never asked.  A failed trajectory gets quiet NaNs in every
+ * output it has, over the whole horizon; the sign of info[b] says which factorisation failed; no other trajectory's bits change.  Vxx[t] is
+ * symmetric to the bit for t < T; Vxx[T] and Vx[T] are the records' bits; held rows are exact zeros.  Outputs do not depend on which other
+ * outputs were requested.  The arrays of a call do not overlap.  The only scratch is B failure marks, kept by the handle.
+ * ILQR_ERR_INVALID: null handle, nw outside [1, nx], NULL C, unknown flag bits, mu negative or not finite, theta not finite, all five of
+ * K, k, Vx, Vxx and risk_cost NULL, B * (T + 1) * nx * nx beyond INT_MAX; ILQR_ERR_STATE: before ilqr_init_traj / ilqr_set_trajectory.
+ * Every refusal happens before anything is enqueued. */
+/* host arrays: a call-sized device buffer takes C up and the outputs down; synchronises */
+int ilqr_get_risk_sensitive(ilqr_batch* h, int nw, double theta, int flags, double mu, const double* C, double* K, double* k, double* Vx,
+                            double* Vxx, double* risk_cost, int* info);
+/* device memory of this handle's device: enqueued on the handle's stream, nothing waited for */
+int ilqr_copy_risk_sensitive_to_device(ilqr_batch* h, int nw, double theta, int flags, double mu, const void* C_device, void* K_device,
+                                       void* k_device, void* Vx_device, void* Vxx_device, void* risk_cost_device, void* info_device);
+
 /* ---- the stored feedback policy applied to caller-given states (additive under ABI 6) -----------------------------------------------
  * What a solve leaves for a controller is the time-varying law u = us[t] + K[t](x - xs[t]).  These calls apply it to states the CALLER
  * holds -- n_samples of them per trajectory, at knot t0 -- and roll it through the handle's device model for n_knots knots; a read-only

@@ -433,6 +433,33 @@ class BatchILQR {
                                         Su_device, expected_cost_device, info_device),
           "ilqr_copy_estimator_to_device");
   }
+  // The risk-sensitive (LEQG) gains and value of the LQ model the records hold (ilqr_get_risk_sensitive) for the noise dx[t+1] += C xi,
+  // xi ~ N(0, I_nw): C [B][nx*nw] (required); K [B][T][nu*nx], k [B][T][nu] (what set_gains takes), Vx [B][T+1][nx], Vxx [B][T+1][nx*nx]
+  // (column-major per matrix), risk_cost [B], info [B] (< 0: breakdown at that knot; > 0: Quu not positive definite); any output may be
+  // null, not all of the first five.  flags: ILQR_LQ_HOLD_CLAMPED or 0.
+  void risk_sensitive(int nw, double theta, const std::vector<double>& C, std::vector<double>* K, std::vector<double>* k,
+                      std::vector<double>* Vx = nullptr, std::vector<double>* Vxx = nullptr, std::vector<double>* risk_cost = nullptr,
+                      std::vector<int>* info = nullptr, int flags = 0, double mu = 0.0) {
+    if (nw < 1 || nw > n_) throw std::invalid_argument("risk_sensitive(): nw must be in [1, nx]");
+    if (C.size() != (size_t)B_ * n_ * nw) throw std::invalid_argument("risk_sensitive(): C is [B][nx*nw]");
+    const size_t BT = (size_t)B_ * T_, BT1 = (size_t)B_ * (T_ + 1);
+    if (K) K->assign(BT * m_ * n_, 0.0);
+    if (k) k->assign(BT * m_, 0.0);
+    if (Vx) Vx->assign(BT1 * n_, 0.0);
+    if (Vxx) Vxx->assign(BT1 * n_ * n_, 0.0);
+    if (risk_cost) risk_cost->assign(B_, 0.0);
+    if (info) info->assign(B_, 0);
+    check(ilqr_get_risk_sensitive(h_, nw, theta, flags, mu, C.data(), K ? K->data() : nullptr, k ? k->data() : nullptr, Vx ? Vx->data() : nullptr,
+                                  Vxx ? Vxx->data() : nullptr, risk_cost ? risk_cost->data() : nullptr, info ? info->data() : nullptr),
+          "ilqr_get_risk_sensitive");
+  }
+  // ... or from and into caller-owned device memory, on the handle's stream, nothing waited for
+  void copy_risk_sensitive_to_device(int nw, double theta, int flags, double mu, const void* C_device, void* K_device, void* k_device, void* Vx_device,
+                                     void* Vxx_device, void* risk_cost_device, void* info_device) {
+    check(ilqr_copy_risk_sensitive_to_device(h_, nw, theta, flags, mu, C_device, K_device, k_device, Vx_device, Vxx_device, risk_cost_device,
+                                             info_device),
+          "ilqr_copy_risk_sensitive_to_device");
+  }
   // The tangent of the linearised closed loop (ilqr_get_tangent) over the knots [t0, t0 + n_knots), n_knots < 0: up to knot T: n_dirs
   // directions per trajectory, dx0 [B][n_dirs][nx] and dv [B][T][n_dirs][nu] (null = zero, not both); dxs [B][n_knots][n_dirs][nx], dus
   // [B][nku][n_dirs][nu] over the window's nku knots with a control; either output may be null, not both.
