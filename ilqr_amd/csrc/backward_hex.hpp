@@ -50,6 +50,15 @@ constexpr bool kHexCandT = ILQR_HEX_CAND_T != 0;
 #define ILQR_HEX_QUAD_ROLLOUT 1   // the kernel's rollouts as one quad x eleven alphas per SIMD (rollout.hpp: QUAD); 0: 16 trajectories x 4 alphas on three SIMDs (A/B)
 #endif
 constexpr bool kHexQuadRollout = ILQR_HEX_QUAD_ROLLOUT != 0;
+#ifndef ILQR_HEX_SLOT_PHASES
+#define ILQR_HEX_SLOT_PHASES 4   // knots per group of ring slots: the chain's step loop is unrolled by it and a knot's slot is group + phase, the phase an immediate; 1: a slot index per knot (A/B)
+#endif
+constexpr int kHexSlotPhases = ILQR_HEX_SLOT_PHASES;
+static_assert(kHexSlotPhases == 1 || kHexSlotPhases == 2 || kHexSlotPhases == 4, "backward_hex's step loop is written out for groups of 1, 2 or 4 knots");
+#ifndef ILQR_HEX_MFMA_SPREAD
+#define ILQR_HEX_MFMA_SPREAD 0   // the step's matrix instructions: nine at the top of the step; 1: the three the box-QP needs first, the other six pinned further down (A/B: measured, not shipped -- DESIGN 3.10)
+#endif
+constexpr bool kHexMfmaSpread = ILQR_HEX_MFMA_SPREAD != 0;
 
 // One pair's ring: a slot holds one knot of the sub-tile's 4 trajectories, pair-interleaved like the HBM records:
 // [pair][trajectory lp][2].
@@ -82,17 +91,30 @@ struct HexRing {
 
 constexpr int kHexKnotsPerRound = 64 / HT;       // a producer round: 16 knots x 4 trajectories
 // The LDS a pair's records may take is what 24 full slots take (4 pairs x 24 x 1 600 B = 154 KB in double: one block per CU);
-// a compact slot is about half a full one, so the same bytes -- less the knot-T area -- hold 45 of them.
+// a compact slot is about half a full one, so the same bytes -- less the knot-T area -- hold 45 of them: 44, whole groups of
+// kHexSlotPhases slots (HexGate).
 constexpr int kHexFullSlots = 24;
 template <int NX, int NU, class real, bool COMPACT>
 struct HexRingSize {
   using Full = HexRing<NX, NU, real, kHexFullSlots, false>;
   static constexpr int TERM = COMPACT ? ((NX + NX * NX) / 2) * Full::ROW : 0;  // `real`s of the knot-T area: 10 pair rows x 4 trajectories
-  static constexpr int SLOTS = COMPACT ? (kHexFullSlots * Full::ELEMS - TERM) / HexRing<NX, NU, real, 1, COMPACT>::ELEMS : kHexFullSlots;
-  // a round may be written once its first knot is at most LEAD knots ahead of the consumer: the whole ring but a round and a knot
-  // to spare (24 full slots: 7; 45 compact ones: 28)
+  static constexpr int FIT = COMPACT ? (kHexFullSlots * Full::ELEMS - TERM) / HexRing<NX, NU, real, 1, COMPACT>::ELEMS : kHexFullSlots;
+  static constexpr int SLOTS = FIT / kHexSlotPhases * kHexSlotPhases;
+  // A pass begins on running index pass x N, N a multiple of the round: with whole groups in the ring and in a round, a knot's
+  // phase (its running index mod kHexSlotPhases) is the phase of its slot, and a round begins at phase 0.
+  static_assert(SLOTS % kHexSlotPhases == 0 && kHexKnotsPerRound % kHexSlotPhases == 0, "the ring and a producer round are whole groups of slots");
+  // a round may be written once its first knot is at most LEAD knots ahead of the index the chain has PUBLISHED: the whole ring but
+  // a round and a knot to spare (24 full slots: 7; 44 compact ones: 27).  The chain publishes at phase 0 only (HexGate), so what the
+  // producer reads is up to STALE knots behind the knot the chain is at.
   static constexpr int LEAD = SLOTS - kHexKnotsPerRound - 1;
-  static_assert(SLOTS > LEAD + kHexKnotsPerRound - 1 && LEAD >= 1, "a round must not reach a slot the chain has not left");
+  static constexpr int STALE = kHexSlotPhases - 1;
+  // Slot reuse: every knot below the published index p has been read; a round that may start has its first knot at most p + LEAD, its
+  // last at most p + LEAD + 15, and that one shares its slot with knot p + LEAD + 15 - SLOTS, which must lie below p.  The chain
+  // itself is at p .. p + STALE: staleness only moves it further from the slots being written, never closer.
+  static_assert(SLOTS > LEAD + kHexKnotsPerRound - 1, "a round must not reach a slot the chain has not left");
+  // Liveness and lead: a chain STALE knots past its last publication still releases rounds that begin at least one knot ahead of it
+  // (and where it blocks, at the first knot of a round, it has just published that very knot).
+  static_assert(LEAD - STALE >= 1, "the producer is released ahead of the chain, the published index being up to STALE knots old");
   static_assert(SLOTS * HexRing<NX, NU, real, 1, COMPACT>::ELEMS + TERM <= kHexFullSlots * Full::ELEMS, "the pair's records fit the bytes of 24 full slots");
 };
 
@@ -117,30 +139,48 @@ struct HexPair : HexTerm<real, HexRingSize<NX, NU, real, COMPACT>::TERM> {  // L
   unsigned long long pass_lanes;      // exec mask of the chain wavefront in the current pass (bit 4 t = trajectory t)
 };
 
-// Consumer side (cf. RingGate / WideGate).  consumer_at is published at EVERY knot (one LDS store, nothing to wait for): with
-// 16 knots per producer round the producer must be released in the middle of a round, not at its end.  No release fence: the
-// LDS executes a wavefront's operations in order, so the reads of every knot below G were executed before this store is.
+// Consumer side (cf. RingGate / WideGate).  The knots of a pass are taken in GROUPS of kHexSlotPhases: a pass begins on a running
+// index that is a multiple of the round (16) and the ring is whole groups, so knot G sits in slot group + phase with phase =
+// G mod kHexSlotPhases known where the step loop is unrolled -- the caller reads it at the group's offset plus an immediate, and
+// the gate's bookkeeping (the running index, the wrap, the question "is this knot there?") happens once per group, at phase 0:
+// rounds begin at phase 0, so no other knot can be the first one missing.  consumer_at is published there too (one LDS store,
+// nothing to wait for): with 16 knots per producer round the producer must be released in the middle of a round, not at its end,
+// and a value up to kHexSlotPhases - 1 knots old only releases it that much later (HexRingSize: LEAD, STALE); where the chain
+// blocks it has just published the knot it blocks on.  No release fence: the LDS executes a wavefront's operations in order, so
+// the reads of every knot below G were executed before this store is.
+// (kHexSlotPhases = 1: a group is a knot -- every knot publishes, asks and moves on by one slot.)
 template <class P>
 struct HexGate {
   static constexpr bool kRing = true;
+  static constexpr int NPH = kHexSlotPhases;
+  static constexpr int GROUP = NPH * P::RS::ELEMS, RING = P::RS::SLOTS * P::RS::ELEMS;   // `real`s
   P& sh;
   const int T, nrounds, N;
   int pass = -1, have = 0;
-  int g_next = 0, slot_next = 0, slot_cur = 0;
+  int g_grp = 0, off_grp = 0;   // the current group: running index of its phase-0 knot, offset of its first slot in the ring (`real`s)
   __device__ __forceinline__ HexGate(P& s, int T_) : sh(s), T(T_), nrounds((T_ + 1 + kHexKnotsPerRound - 1) / kHexKnotsPerRound), N(nrounds * kHexKnotsPerRound) {}
-  __device__ __forceinline__ void begin_pass() {
+  // (both return how far the group's offset moved: the caller keeps the lanes' addresses of the group and moves them along)
+  __device__ __forceinline__ int begin_pass() {
     pass++;
     have = pass * N;
-    g_next = pass * N;
-    slot_next = g_next % P::RS::SLOTS;
+    g_grp = pass * N;
+    const int was = off_grp;
+    off_grp = (g_grp % P::RS::SLOTS) * P::RS::ELEMS;
     __hip_atomic_store(&sh.pass_lanes, __ballot(1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     __hip_atomic_store(&sh.passes_started, pass + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    return off_grp - was;
   }
-  __device__ __forceinline__ int slot(int) const { return slot_cur; }
-  __device__ __forceinline__ void wait(int) {
-    const int G = g_next++;
-    slot_cur = slot_next;
-    slot_next = (slot_next + 1 == P::RS::SLOTS) ? 0 : slot_next + 1;
+  __device__ __forceinline__ int next_group() {
+    g_grp += NPH;
+    const int d = (off_grp + GROUP == RING) ? GROUP - RING : GROUP;
+    off_grp += d;
+    return d;
+  }
+  // before the knot of phase PH of the current group is read
+  template <int PH>
+  __device__ __forceinline__ void wait() {
+    if constexpr (PH != 0) return;
+    const int G = g_grp;
     __hip_atomic_store(&sh.consumer_at, G, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (G < have) return;
     const int round = pass * nrounds + (G - pass * N) / kHexKnotsPerRound;
@@ -167,7 +207,10 @@ struct HexGate {
 __device__ __forceinline__ int hex_first(unsigned long long bal, int t4) {
   return __builtin_ctzll(((bal >> t4) & 0x000F000F000F000Full) | 0x8000000000000000ull);
 }
-__device__ __forceinline__ void qp1_search_hex(QP1StateT<double>& q, int j, int t4, double step_j0, const double* __restrict__ lds_steps) {
+// under_read(): the caller's, run between the step table's read and the first use of what it returns -- the one LDS round trip the
+// straight-line pass waits out (every lane of the wavefront is still active there); backward_hex issues matrix instructions in it.
+template <class Under>
+__device__ __forceinline__ void qp1_search_hex(QP1StateT<double>& q, int j, int t4, double step_j0, const double* __restrict__ lds_steps, Under under_read) {
   // First pass, k = j, straight-line for every lane (an early exit's lanes compute along: the caller's selects ignore their
   // x1 / v1): the reference's loop ends inside it for all but a few per cent of the QPs.  A trial that lands on x itself ("stuck":
   // failure, qp1_backtrack_seq) has value == old value and fails the test, and so does every shorter step after it: a passing k
@@ -179,10 +222,12 @@ __device__ __forceinline__ void qp1_search_hex(QP1StateT<double>& q, int j, int 
   const bool success = pp < 52;            // a set bit
   const int jw = success ? (((pp >> 4) << 2) | (pp & 3)) : 0;
 #ifdef ILQR_EXP_NO_STEP_LDS  // timing experiment (wrong results for jw >= 2): what the step table's LDS round trip costs the chain
-  q.step = jw == 0 ? 1.0 : 0.6;
+  const double step_w = jw == 0 ? 1.0 : 0.6;
 #else
-  q.step = lds_steps[jw];
+  const double step_w = lds_steps[jw];
 #endif
+  under_read();
+  q.step = step_w;
   q.x1 = clamp_of(q.x + q.step * q.search, q.lo, q.hi);   // the winner's trial point and value, by the winner's expressions
   q.v1 = qp1_value(q, q.x1);
   bool more = p_and(!success, !q.early);
@@ -259,52 +304,77 @@ __device__ __forceinline__ void backward_hex(const BatchViewT<typename M::real>&
   const creal step_j0 = lds_steps[j16];
   auto mm = [](creal a, creal bb) __attribute__((always_inline)) { return __builtin_amdgcn_mfma_f64_4x4x4f64(a, bb, 0.0, 0, 0, 0); };
 
-  auto load = [&](int t, HexStep<real>& d) __attribute__((always_inline)) {
-    gate.wait(t);
-    lds_cd* r = (lds_cd*)(ring + gate.slot(t) * RS::ELEMS + t_ * 2);
-    auto pair = [&](int e) { return *(lds_cd2*)(r + RS::pos(e >> 1) * RS::ROW); };   // (constant e)
-    auto one = [&](int e) { return r[hex_pos_rt<RS>(e >> 1) * RS::ROW + (e & 1)]; };  // (e depends on the lane)
+  // The lane's addresses in the gate's current GROUP of slots: its own two `real`s of a pair row, and one address per record entry
+  // whose place depends on the lane.  They move with the group (a wave-uniform distance, once per kHexSlotPhases knots); a knot's slot
+  // is the group's plus phase x ELEMS, an immediate of the load.
+  using C = CompactRec<4, 1>;
+  enum { A_ROW, A_FX, A_FU, A_CXX_RC, A_CXX_CR, A_CX, A_CXU_R, A_CXU_C, A_FULL };
+  constexpr int NADDR = RS::COMPACT ? A_FU + 1 : A_FULL;
+  lds_cd* at[NADDR];
+  {
+    lds_cd* r = (lds_cd*)(ring + t_ * 2);   // (the gate's first group is the ring's first)
+    auto one = [&](int e) { return r + hex_pos_rt<RS>(e >> 1) * RS::ROW + (e & 1); };  // (e depends on the lane)
+    at[A_ROW] = r;
+    at[A_FX] = one((RS::COMPACT ? C::FX : R::FX) + r_ + 4 * c_);
+    at[A_FU] = one((RS::COMPACT ? C::FU : R::FU) + r_);
+    if constexpr (!RS::COMPACT) {
+      at[A_CXX_RC] = one(R::CXX + r_ + 4 * c_);
+      at[A_CXX_CR] = one(R::CXX + c_ + 4 * r_);
+      at[A_CX] = one(R::CX + r_);
+      at[A_CXU_R] = one(R::CXU + r_);
+      at[A_CXU_C] = one(R::CXU + c_);
+    }
+  }
+  auto move = [&](int d) __attribute__((always_inline)) {
+#pragma unroll
+    for (int a = 0; a < NADDR; a++) at[a] += d;
+  };
+  constexpr int NPH = kHexSlotPhases;
+  auto load = [&](auto phase, HexStep<real>& d) __attribute__((always_inline)) {
+    constexpr int PH = decltype(phase)::value, o = PH * RS::ELEMS;
+    gate.template wait<PH>();
+    auto pair = [&](int e) { return *(lds_cd2*)(at[A_ROW] + o + RS::pos(e >> 1) * RS::ROW); };   // (constant e)
     if constexpr (RS::COMPACT) {
       // five loads instead of nine: the knot's cx, cxx, cxu entries are all the one value Z (+0.0, or NaN with an overflowing
       // cost).  The step below still ADDS them (-0.0 + 0.0 is +0.0: a dropped addition would change signs of zero).
-      using C = CompactRec<4, 1>;
-      d.F = one(C::FX + r_ + 4 * c_);
-      d.fu_r = one(C::FU + r_);
-      d.cxx_rc = d.cxx_cr = d.cx_r = d.cxu_r = d.cxu_c = r[RS::Z];
+      d.F = at[A_FX][o];
+      d.fu_r = at[A_FU][o];
+      d.cxx_rc = d.cxx_cr = d.cx_r = d.cxu_r = d.cxu_c = at[A_ROW][o + RS::Z];
       d.tail = pair(C::CU);
       d.uw = pair(C::US);
-      return;
+    } else {
+      d.F = at[A_FX][o];
+      d.cxx_rc = at[A_CXX_RC][o];
+      d.cxx_cr = at[A_CXX_CR][o];
+      d.fu_r = at[A_FU][o];
+      d.cx_r = at[A_CX][o];
+      d.cxu_r = at[A_CXU_R][o];
+      d.cxu_c = at[A_CXU_C][o];
+      d.tail = pair(R::CU);
+      d.uw = pair(RS::US);
     }
-    d.F = one(R::FX + r_ + 4 * c_);
-    d.cxx_rc = one(R::CXX + r_ + 4 * c_);
-    d.cxx_cr = one(R::CXX + c_ + 4 * r_);
-    d.fu_r = one(R::FU + r_);
-    d.cx_r = one(R::CX + r_);
-    d.cxu_r = one(R::CXU + r_);
-    d.cxu_c = one(R::CXU + c_);
-    d.tail = pair(R::CU);
-    d.uw = pair(RS::US);
+    if constexpr (PH == NPH - 1) move(gate.next_group());
   };
 
   int diverge = 0;
   bool done = false;
   double dV0 = 0, dV1 = 0, gacc = 0;
   auto one_pass = [&]() __attribute__((always_inline)) {
-    gate.begin_pass();
+    move(gate.begin_pass());
     creal V, RVx, kprev;   // Vxx'[r][c] (D layout), Vx'[r] (replicated over c)
     const creal lam_r = (creal)lambda;
     {
-      gate.wait(T);  // (compact ring: knot T keeps its place in the count -- its slot stays empty -- and its round carries the term area)
+      // knot T is phase 0 of the pass's first group; knot i is phase (T - i) mod kHexSlotPhases
+      gate.template wait<0>();  // (compact ring: knot T keeps its place in the count -- its slot stays empty -- and its round carries the term area)
       if constexpr (RS::COMPACT) {
-        using C = CompactRec<4, 1>;
         lds_cd* r = (lds_cd*)(term + t_ * 2);
         RVx = (creal)r[((C::TERM_CX + r_) >> 1) * RS::ROW + ((C::TERM_CX + r_) & 1)];                          // :353
         V = (creal)r[((C::TERM_CXX + r_ + 4 * c_) >> 1) * RS::ROW + ((C::TERM_CXX + r_ + 4 * c_) & 1)];        // :354
       } else {
-      lds_cd* r = (lds_cd*)(ring + gate.slot(T) * RS::ELEMS + t_ * 2);
-      RVx = (creal)r[hex_pos_rt<RS>((R::CX + r_) >> 1) * RS::ROW + ((R::CX + r_) & 1)];                        // :353
-      V = (creal)r[hex_pos_rt<RS>((R::CXX + r_ + 4 * c_) >> 1) * RS::ROW + ((R::CXX + r_ + 4 * c_) & 1)];    // :354
+        RVx = (creal)at[A_CX][0];      // :353
+        V = (creal)at[A_CXX_RC][0];    // :354
       }
+      if constexpr (NPH == 1) move(gate.next_group());
     }
     kprev = (creal)kt[(unsigned)((T - 1) * TW)];
     // (gfx950 counts stores in vmcnt too: with this load still "in flight" at the loop header the compiler made every step wait for
@@ -317,29 +387,39 @@ __device__ __forceinline__ void backward_hex(const BatchViewT<typename M::real>&
     real* __restrict__ Kt_i = Kt + (unsigned)(((T - 1) * 4 + c_) * TW);  // K[c] of step i
     real* __restrict__ kt_i = kt + (unsigned)((T - 1) * TW);
 
-    // one Riccati step from the record `raw` of knot i; `nxt` is loaded with knot i - 1 on the way
-    auto step = [&](int i, const HexStep<real>& raw, HexStep<real>& nxt) -> bool {
+    // one Riccati step from the record `raw` of knot i; `nxt` is loaded with knot i - 1, the knot of phase `phase`, on the way
+    auto step = [&](auto phase, int i, const HexStep<real>& raw, HexStep<real>& nxt) -> bool {
       const creal F = (creal)raw.F, Rfu = (creal)raw.fu_r;
       const creal cu = (creal)raw.tail.x, cuu = (creal)raw.tail.y, us = (creal)raw.uw.x, usw = (creal)raw.uw.y;
-      // the matrix unit: every sum runs k = 0..3 from a zero accumulator, as backward_quad's do
-      const creal W = mm(V, F);               // (Vxx' fx)[r][c]
+      // the matrix unit: every sum runs k = 0..3 from a zero accumulator, as backward_quad's do.  A matrix instruction holds the
+      // vector pipe for 21 cycles, a vector instruction behind it waits them out, a scalar one or a wait for LDS does not
+      // (scripts/ubench/coissue.hip, kinds 4-14).  Shipped: all nine here.  kHexMfmaSpread (off: phase 1 - 2 %, the iteration inside
+      // the noise): only what the box-QP starts from is multiplied here -- wv, with aQu under its latency, then aQuu --,
+      // three more in the step table's round trip inside the search, the last three behind it.
+      creal W, aQx, Tm, Tt, aQux_c, aQux_r;
+      auto products_1 = [&]() __attribute__((always_inline)) {
+        W = mm(V, F);                         // (Vxx' fx)[r][c]
+        aQx = mm(F, RVx);                     // (fx' Vx')[r]
+        Tm = mm(F, W);                        // (fx' W)[r][c]
+      };
+      auto products_2 = [&]() __attribute__((always_inline)) {
+        Tt = mm(W, F);                        // (fx' W)[c][r]
+        aQux_c = mm(Rfu, W);                  // (fu' W)[c]
+        aQux_r = mm(W, Rfu);                  // (fu' W)[r]
+      };
       const creal wv = mm(V, Rfu);            // (Vxx' fu)[r]
       const creal aQu = mm(Rfu, RVx);         // fu' Vx'
-      const creal aQx = mm(F, RVx);           // (fx' Vx')[r]
-      const creal Tm = mm(F, W);              // (fx' W)[r][c]
-      const creal Tt = mm(W, F);              // (fx' W)[c][r]
       const creal aQuu = mm(Rfu, wv);         // fu' Vxx' fu
-      const creal aQux_c = mm(Rfu, W);        // (fu' W)[c]
-      const creal aQux_r = mm(W, Rfu);        // (fu' W)[r]
-      const creal Qxx_rc = (creal)raw.cxx_rc + Tm, Qxx_cr = (creal)raw.cxx_cr + Tt;   // :361
-      const creal Qx_r = (creal)raw.cx_r + aQx;                                       // :359
+      if constexpr (!kHexMfmaSpread) {
+        products_1();
+        products_2();
+      }
       const creal Qu = cu + aQu;                                                      // :360
-      const creal Qux_c = (creal)raw.cxu_c + aQux_c, Qux_r = (creal)raw.cxu_r + aQux_r;  // :362/:366
       const creal Quu = cuu + aQuu, QuuF = (cuu + lam_r) + aQuu;                      // :363, :367
       const creal lo = (creal)model.u_min[0] - us, hi = (creal)model.u_max[0] - us;
       // the next step's record: issued here, it lands under the box-QP
       __builtin_amdgcn_sched_barrier(0);
-      if (i >= 1) load(i - 1, nxt);
+      if (i >= 1) load(phase, nxt);
       __builtin_amdgcn_sched_barrier(0);
       // :369  box-QP, replicated over the 16 lanes of the trajectory; 16 step sizes per pass of the Armijo search
       creal x;
@@ -347,13 +427,23 @@ __device__ __forceinline__ void backward_hex(const BatchViewT<typename M::real>&
       creal minv;
       QP1StateT<creal> q1;
       qp1_begin<false>(QuuF, Qu, kprev, lo, hi, q1, false);
-      qp1_search_hex(q1, j16, t4, step_j0, lds_steps);
+      qp1_search_hex(q1, j16, t4, step_j0, lds_steps, [&]() __attribute__((always_inline)) {
+        if constexpr (kHexMfmaSpread) {
+          __builtin_amdgcn_sched_barrier(0);
+          products_1();
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      });
+      if constexpr (kHexMfmaSpread) products_2();
       bool goes_on;
       bool ok = qp1_finish_ok(q1, x, free0, minv, goes_on);
       if (goes_on)
         ok = qp1_continue(
-                 q1, [&](QP1StateT<creal>& qs) __attribute__((always_inline)) { qp1_search_hex(qs, j16, t4, step_j0, lds_steps); }, x, free0) >= 1;
+                 q1, [&](QP1StateT<creal>& qs) __attribute__((always_inline)) { qp1_search_hex(qs, j16, t4, step_j0, lds_steps, [] {}); }, x, free0) >= 1;
       if (!ok) diverge = i;
+      const creal Qxx_rc = (creal)raw.cxx_rc + Tm, Qxx_cr = (creal)raw.cxx_cr + Tt;   // :361
+      const creal Qx_r = (creal)raw.cx_r + aQx;                                       // :359
+      const creal Qux_c = (creal)raw.cxu_c + aQux_c, Qux_r = (creal)raw.cxu_r + aQux_r;  // :362/:366
       // :373-385  K = -(R^-1 R^-T) Qux on a free control, 0 on a clamped one
       const creal k_scale = free0 ? -minv : creal(0);
       const creal K_r = k_scale * Qux_r, K_c = k_scale * Qux_c;
@@ -419,14 +509,22 @@ __device__ __forceinline__ void backward_hex(const BatchViewT<typename M::real>&
       return ok;
     };
 
+    // knots T - 1, T - 2, ... are phases 1, 2, 3, 0, 1, ...: the loop is one turn of the phases, and a pass may end after any step
     HexStep<real> A, Bd;
     int i = T - 1;
-    load(i, A);
+    auto ph = [](auto n) { return std::integral_constant<int, decltype(n)::value % NPH>(); };
+    load(ph(std::integral_constant<int, 1>()), A);
     while (true) {
-      if (!step(i, A, Bd)) break;
+      if (!step(ph(std::integral_constant<int, 2>()), i, A, Bd)) break;
       if (--i < 0) break;
-      if (!step(i, Bd, A)) break;
+      if (!step(ph(std::integral_constant<int, 3>()), i, Bd, A)) break;
       if (--i < 0) break;
+      if constexpr (NPH == 4) {
+        if (!step(ph(std::integral_constant<int, 4>()), i, A, Bd)) break;
+        if (--i < 0) break;
+        if (!step(ph(std::integral_constant<int, 5>()), i, Bd, A)) break;
+        if (--i < 0) break;
+      }
     }
   };
 
