@@ -6,7 +6,8 @@
 // dynamics() / cost() / final_cost() exactly as src/derivatives.cpp does, the matrix-core backward pass.
 //   user_params: A [6][6], B [6][2], Q [6][6], R [2][2], Qf [6][6], row-major (124 doubles), optionally followed by wb: the weight of
 //   a soft penalty wb sum_j (u_j / u_max_j)^2 on the controls -- a cost that reads the model's own limits, as a Model subclass may
-//   (include/model.h:17: u_min / u_max are public members set by the subclass)
+//   (include/model.h:17: u_min / u_max are public members set by the subclass), and after wb optionally by N [6][2]: a state-control term
+//   x'N u of the running cost (cxu = N)
 template <class real_>
 struct UserModelT {
   using real = real_;
@@ -14,6 +15,8 @@ struct UserModelT {
   real u_min[NU], u_max[NU];
   real A[NX][NX], B[NX][NU], Q[NX][NX], R[NU][NU], Qf[NX][NX];
   real wb;
+  real N[NX][NU];
+  bool has_N;
 
   void set_params(const double* p, int n) {
     const int need = 3 * NX * NX + NX * NU + NU * NU;
@@ -28,6 +31,9 @@ struct UserModelT {
     for (int i = 0; i < NU; i++)
       for (int j = 0; j < NU; j++) R[i][j] = (n >= need) ? (real)p[2 * NX * NX + NX * NU + i * NU + j] : real(i == j);
     wb = (n > need) ? (real)p[need] : real(0);
+    has_N = n >= need + 1 + NX * NU;
+    for (int i = 0; i < NX; i++)
+      for (int j = 0; j < NU; j++) N[i][j] = has_N ? (real)p[need + 1 + i * NU + j] : real(0);
   }
   __device__ void dynamics(const real* x, const real* u, real* dx) const {
     for (int i = 0; i < NX; i++) {
@@ -51,12 +57,18 @@ struct UserModelT {
     real c = real(0.5) * (quad<NX>(Q, x) + quad<NU>(R, u));
     if (wb != real(0))
       for (int j = 0; j < NU; j++) c += wb * (u[j] / u_max[j]) * (u[j] / u_max[j]);
+    if (has_N)
+      for (int i = 0; i < NX; i++) {
+        real r = 0;
+        for (int j = 0; j < NU; j++) r += N[i][j] * u[j];
+        c += x[i] * r;
+      }
     return c;
   }
   __device__ real final_cost(const real* x) const { return real(0.5) * quad<NX>(Qf, x); }
   // optional: exact derivatives (ILQR_FLAG_ANALYTIC_DERIVATIVES).  One thread writes the whole record: fx | fu | cx | cxx | cxu | cu | cuu,
   // matrices column-major, with the conventions of src/derivatives.cpp at the last knot (fx = fu = 0, cx / cxx from final_cost, cu = 0,
-  // cuu from cost(x_T, 0), cxu = 0).
+  // cuu from cost(x_T, 0), cxu = 0); before it cxu = N, cx gains N u and cu gains N'x.
   __device__ void analytic_record(const real* x, const real* u, real dt, bool last, real* rec) const {
     real* fx = rec;
     real* fu = fx + NX * NX;
@@ -74,11 +86,13 @@ struct UserModelT {
     for (int c = 0; c < NU; c++)
       for (int r = 0; r < NX; r++) {
         fu[r + NX * c] = last ? real(0) : dt * B[r][c];
-        cxu[r + NX * c] = real(0);
+        cxu[r + NX * c] = (last || !has_N) ? real(0) : N[r][c];
       }
     for (int i = 0; i < NX; i++) {
       real acc = 0;
       for (int j = 0; j < NX; j++) acc += real(0.5) * (W[i][j] + W[j][i]) * x[j];
+      if (has_N && !last)
+        for (int j = 0; j < NU; j++) acc += N[i][j] * u[j];
       cx[i] = acc;
     }
     for (int c = 0; c < NU; c++)
@@ -88,6 +102,8 @@ struct UserModelT {
       if (!last) {
         for (int j = 0; j < NU; j++) acc += real(0.5) * (R[i][j] + R[j][i]) * u[j];
         if (wb != real(0)) acc += real(2) * wb * u[i] / (u_max[i] * u_max[i]);
+        if (has_N)
+          for (int j = 0; j < NX; j++) acc += N[j][i] * x[j];
       }
       cu[i] = acc;
     }

@@ -93,8 +93,14 @@ USER_CHAIN_LIB = os.path.join(PKG, "lib", "libilqr_amd_user_chain.so")
 # a user twin with more than 16 controls (n = 24, m = 20): the generic kernels with the two-control-tile backward pass
 USER_WIDE_HEADER = os.path.join(os.path.dirname(PKG), "examples", "user_model_linear_wide.hpp")
 USER_WIDE_LIB = os.path.join(PKG, "lib", "libilqr_amd_user_linear_wide.so")
+# test twins, not examples: four states with a state-control term x'N u in the running cost (cxu != 0 on the lane-quad kernels and the
+# persistent routes), with one control and with two -- tests/test_gpu_coupled_twin.py
+USER_COUPLED4_HEADER = os.path.join(os.path.dirname(PKG), "tests", "native", "user_model_coupled4.hpp")
+USER_COUPLED4_LIB = os.path.join(PKG, "lib", "libilqr_amd_user_coupled4.so")
+USER_COUPLED4_NU2_HEADER = os.path.join(os.path.dirname(PKG), "tests", "native", "user_model_coupled4_nu2.hpp")
+USER_COUPLED4_NU2_LIB = os.path.join(PKG, "lib", "libilqr_amd_user_coupled4_nu2.so")
 USER_BUILDS = ((USER_EXAMPLE_HEADER, USER_EXAMPLE_LIB), (USER_EXAMPLE6_HEADER, USER_EXAMPLE6_LIB), (USER_CHAIN_HEADER, USER_CHAIN_LIB),
-               (USER_WIDE_HEADER, USER_WIDE_LIB))
+               (USER_WIDE_HEADER, USER_WIDE_LIB), (USER_COUPLED4_HEADER, USER_COUPLED4_LIB), (USER_COUPLED4_NU2_HEADER, USER_COUPLED4_NU2_LIB))
 
 
 def build_all(verbose=False):

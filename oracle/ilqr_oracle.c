@@ -138,6 +138,7 @@ void orc_model_init_lq(orc_model* m, int nx, int nu, const orc_real* A, const or
   m->cost_fd = lq_cost_fd;
   m->final_cost_fd = lq_final_cost_fd;
 }
+void orc_model_set_lq_cross(orc_model* m, const orc_real* N) { m->N = N; }
 
 /* the pendulum chain (orc_models.inc): N links, params[8] = g/l, damping, coupling, w_theta, w_omega, w_u, final scale, target angle */
 void orc_model_init_chain(orc_model* m, int N, const orc_f64* params, orc_f64 umin, orc_f64 umax) {

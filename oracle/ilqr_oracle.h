@@ -98,6 +98,7 @@ typedef struct orc_model {
   orc_real goal[ORC_MAXN];
   /* LQ model (synthetic config 5): xdot = A x + B u ; cost 0.5(x'Qx+u'Ru) ; final 0.5 x'Qf x */
   const orc_real *A, *Bm, *Q, *R, *Qf;
+  const orc_real* N; /* or NULL: a state-control term x'N u in the running cost (row-major N[nx][nu]) */
 } orc_model;
 
 void orc_model_init_acrobot(orc_model* m);                               /* include/acrobot.h */
@@ -105,6 +106,8 @@ void orc_model_init_double_integrator(orc_model* m, const orc_real* goal); /* in
 void orc_model_init_lq(orc_model* m, int nx, int nu, const orc_real* A, const orc_real* Bm,
                        const orc_real* Q, const orc_real* R, const orc_real* Qf, orc_f64 umin,
                        orc_f64 umax);
+/* the LQ model's running cost gains x'N u (N row-major [nx][nu], NULL takes it away): cxu = N, the twin of tests/native/user_model_coupled4.hpp */
+void orc_model_set_lq_cross(orc_model* m, const orc_real* N);
 /* a chain of N coupled pendulums (nx = 2 N <= 32, nu = N / 2): the oracle-side twin of examples/user_model_pendulum_chain.hpp */
 void orc_model_init_chain(orc_model* m, int N, const orc_f64* params, orc_f64 umin, orc_f64 umax);
 void orc_integrate_dynamics(const orc_model* m, const orc_real* x, const orc_real* u, orc_f64 dt,

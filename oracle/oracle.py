@@ -88,7 +88,7 @@ def _structs():
             ("dynamics", C.c_void_p), ("cost", C.c_void_p), ("final_cost", C.c_void_p),
             ("dynamics_fd", C.c_void_p), ("cost_fd", C.c_void_p), ("final_cost_fd", C.c_void_p),
             ("goal", rc * MAXN),
-            ("A", rp), ("Bm", rp), ("Q", rp), ("R", rp), ("Qf", rp),
+            ("A", rp), ("Bm", rp), ("Q", rp), ("R", rp), ("Qf", rp), ("N", rp),
         ]
 
     class _Traj(C.Structure):
@@ -214,9 +214,9 @@ def _pi(a):
 class Model:
     """A Model plugin instance (include/model.h) on the oracle side, in the flavour current at construction."""
 
-    def __init__(self, kind, goal=None, lq=None, u_lim=None, chain=None, u_min=None, u_max=None):
+    def __init__(self, kind, goal=None, lq=None, u_lim=None, chain=None, u_min=None, u_max=None, cross=None):
         """u_lim: the box [-u_lim, u_lim] for every control; u_min / u_max (scalars or one value per control, given together)
-        set each control's own box and take precedence over u_lim."""
+        set each control's own box and take precedence over u_lim.  cross (kind "lq" only): N [nx][nu], the running cost gains x'N u."""
         assert (u_min is None) == (u_max is None), "u_min and u_max go together"
         self.flavour = _cur
         _Model, _ = _structs()
@@ -235,6 +235,11 @@ class Model:
             lim = 1.0 if u_lim is None else float(u_lim)
             L.orc_model_init_lq(C.byref(self.m), nx, nu, _p(A), _p(Bm), _p(Q), _p(R), _p(Qf),
                                 C.c_double(-lim), C.c_double(lim))
+            if cross is not None:
+                N = _c(cross)
+                assert N.shape == (nx, nu), N.shape
+                self._keep.append(N)
+                L.orc_model_set_lq_cross(C.byref(self.m), _p(N))
             u_lim = None
         elif kind == "chain":  # chain = (N, params[8]): the pendulum chain of orc_models.inc / examples/user_model_pendulum_chain.hpp
             N, prm = int(chain[0]), np.ascontiguousarray(chain[1], dtype=np.float64)
@@ -244,7 +249,8 @@ class Model:
             u_lim = None
         else:
             raise ValueError(kind)
-        self.chain_arg = chain
+        assert cross is None or kind in ("lq", MODEL_LQ), "cross belongs to the lq model"
+        self.chain_arg, self.cross_arg = chain, cross
         self.kind, self.goal_arg, self.lq_arg, self.lim_arg = kind, goal, lq, u_lim
         if u_lim is not None:
             self.set_limits(-abs(u_lim), abs(u_lim))
@@ -256,7 +262,8 @@ class Model:
         limits as they stand now -- also those given to set_limits after construction, whatever the kind."""
         with flavour(name):
             m = Model(self.kind, goal=self.goal_arg, lq=[np.asarray(a, dtype=np.float64) for a in self.lq_arg] if self.lq_arg is not None else None,
-                      chain=self.chain_arg, u_min=self.u_min, u_max=self.u_max)
+                      chain=self.chain_arg, u_min=self.u_min, u_max=self.u_max,
+                      cross=None if self.cross_arg is None else np.asarray(self.cross_arg, dtype=np.float64))
         return m
 
     def set_limits(self, lo, hi):

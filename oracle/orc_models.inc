@@ -105,7 +105,7 @@ static MT MN(dint_final_cost)(const orc_model* m, const MT* x) {
 }
 
 /* Synthetic LQ model (BASELINE.json configs[4]; no counterpart in the reference, SURVEY.md 0.1):
- * xdot = A x + B u (row-major A[nx][nx], B[nx][nu]); cost 0.5 (x'Qx + u'Ru); final 0.5 x'Qf x.
+ * xdot = A x + B u (row-major A[nx][nx], B[nx][nu]); cost 0.5 (x'Qx + u'Ru) [+ x'N u when N is set]; final 0.5 x'Qf x.
  * Sums run left to right over the column index. */
 static void MN(lq_dynamics)(const orc_model* m, const MT* x, const MT* u, MT* dx) {
   const int n = m->nx, mu = m->nu;
@@ -126,7 +126,15 @@ static MT MN(lq_quad)(int n, const orc_real* M, const MT* v) {
   return s;
 }
 static MT MN(lq_cost)(const orc_model* m, const MT* x, const MT* u) {
-  return (MT)0.5 * (MN(lq_quad)(m->nx, m->Q, x) + MN(lq_quad)(m->nu, m->R, u));
+  MT c = (MT)0.5 * (MN(lq_quad)(m->nx, m->Q, x) + MN(lq_quad)(m->nu, m->R, u));
+  if (m->N) { /* + x'N u */
+    for (int i = 0; i < m->nx; i++) {
+      MT r = 0;
+      for (int j = 0; j < m->nu; j++) r += m->N[i * m->nu + j] * u[j];
+      c += x[i] * r;
+    }
+  }
+  return c;
 }
 static MT MN(lq_final_cost)(const orc_model* m, const MT* x) {
   return (MT)0.5 * MN(lq_quad)(m->nx, m->Qf, x);
