@@ -270,6 +270,35 @@ class BatchILQR:
         """Every trajectory back to the handle-wide parameters of the constructor."""
         self._check(self.lib.ilqr_clear_trajectory_params(self.h))
 
+    def param_gradient(self, dxs=None, dus=None, dlam=None, eps_p=0.0, want_lam=False):
+        """dL/dp, the gradient of the caller's loss in the rows of set_trajectory_params (include/ilqr_amd.h, ilqr_get_param_gradient), from
+        what lq_solve(gx=dL/dxs, gu=dL/dus, dlam=True) returned: dxs, dlam [B][T+1][S][nx], dus [B][T][S][nu] (None = zero, not all three;
+        dlam[:, 0] is not read).  Returns gp [B][S][NTP], with want_lam (gp, lam [B][T+1][nx]), lam the nominal costate of the records.
+        Inputs without the direction axis are one direction and the axis is dropped again on output.  eps_p: the relative parameter step
+        (0 = 1e-3).  The gradient through the records' LQ model: exact for dynamics linear in (x, u), Gauss-Newton otherwise.  Synchronises."""
+        X = self._dirs_input(dxs, (self.T + 1,), self.nx, "dxs")
+        U = self._dirs_input(dus, (self.T,), self.nu, "dus")
+        Lm = self._dirs_input(dlam, (self.T + 1,), self.nx, "dlam")
+        given = [a for a in (X, U, Lm) if a[0] is not None]
+        if not given:
+            raise ValueError("dxs, dus and dlam are all None: the answer would be zero")
+        S, flat = given[0][1], given[0][2]
+        if any(a[1] != S or a[2] != flat for a in given):
+            raise ValueError("dxs, dus and dlam disagree on the directions: %s" % [a[0].shape for a in given])
+        gp = np.zeros((self.B, S, max(self.lib.ilqr_trajectory_params_count(), 1)))
+        lam = np.zeros((self.B, self.T + 1, self.nx)) if want_lam else None
+        self._check(self.lib.ilqr_get_param_gradient(self.h, S, 0, float(eps_p), _p(X[0]), _p(U[0]), _p(Lm[0]), _p(gp), _p(lam)))
+        if flat:
+            gp = gp[:, 0]
+        return (gp, lam) if want_lam else gp
+
+    def param_gradient_on_device(self, S, dxs=None, dus=None, dlam=None, gp=None, lam=None, eps_p=0.0):
+        """ilqr_param_gradient_on_device: float64 dxs, dlam [B][T+1][S][nx], dus [B][T][S][nu] (None = zero, not all three), gp [B][S][NTP],
+        lam [B][T+1][nx] (either may be None, not both) in device memory, each a torch tensor (contiguous float64 on the handle's device)
+        or a raw pointer.  Enqueued on the handle's stream, nothing waited for."""
+        ptr = lambda a: a.data_ptr() if hasattr(a, "data_ptr") else a
+        self._check(self.lib.ilqr_param_gradient_on_device(self.h, int(S), 0, float(eps_p), ptr(dxs), ptr(dus), ptr(dlam), ptr(gp), ptr(lam)))
+
     # ---- stages ----
     def compute_derivatives(self):
         self._check(self.lib.ilqr_compute_derivatives(self.h))

@@ -34,6 +34,7 @@
 #include "risk_thread.hpp"
 #include "risk_wave.hpp"
 #include "evaluate.hpp"
+#include "param_gradient.hpp"
 #include "clone.hpp"
 
 using namespace ilqr;
@@ -94,6 +95,7 @@ void ilqr_destroy(ilqr_batch* h) {
   if (h->staging) (void)hipFree(h->staging);
   if (h->lq_scratch) (void)hipFree(h->lq_scratch);
   if (h->est_scratch) (void)hipFree(h->est_scratch);
+  if (h->pg_scratch) (void)hipFree(h->pg_scratch);
   if (h->d_perm) (void)hipFree(h->d_perm);
   if (h->perm_scratch) (void)hipFree(h->perm_scratch);
   (void)timers_drain(h);  // (every event back into the pool, each once)
@@ -1478,6 +1480,76 @@ int ilqr_clear_trajectory_params(ilqr_batch* h) {
   if (!h) return fail(ILQR_ERR_INVALID, "null handle");
   if (int rc = check_trajectory_params(h, "ilqr_clear_trajectory_params")) return rc;
   h->plan.traj_params = false;  // (the rows stay allocated for the next set)
+  return 0;
+}
+
+// ---- the gradient of a caller's loss with respect to the per-trajectory parameters (additive under ABI 6; param_gradient.hpp) ------
+// every refusal the two calls share -- before anything is enqueued; the argument checks need no handle and come first --, then the nominal
+// and the records as ilqr_get_trajectory / ilqr_get_derivatives would return them now
+static int prepare_param_gradient(ilqr_batch* h, int n_dirs, int flags, double eps_p, const void* dxs, const void* dus, const void* dlam, const void* gp,
+                                  const void* lam, const char* who) {
+  REQUIRE(n_dirs >= 1, "%s: n_dirs %d must be >= 1", who, n_dirs);
+  REQUIRE(flags == 0, "%s: unknown flag bits 0x%x", who, (unsigned)flags);
+  REQUIRE(eps_p >= 0.0 && eps_p <= 1.7976931348623157e308, "%s: eps_p %g must be finite and >= 0", who, eps_p);
+  REQUIRE(dxs || dus || dlam, "%s: dxs, dus and dlam are all null: the answer would be zero", who);
+  REQUIRE(gp || lam, "%s: gp and lam are both null", who);
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  if (int rc = check_trajectory_params(h, who)) return rc;
+  const long long widest = (long long)h->B * (h->T + 1) * n_dirs * std::max(std::max(h->nx, h->nu), kUserNTP);
+  REQUIRE(widest <= (long long)INT_MAX, "%s: B * (T + 1) * n_dirs * max(nx, nu, NTP) = %lld elements do not fit an int", who, widest);
+  if (!h->initialised) return fail(ILQR_ERR_STATE, "%s before ilqr_init_traj/ilqr_set_trajectory: no trajectory is stored", who);
+  if (!h->plan.traj_params)
+    return fail(ILQR_ERR_STATE, "%s: no per-trajectory parameters are set (ilqr_create's user_params have no mapping onto the NTP fields)", who);
+  HIPCHK(hipSetDevice(h->device));
+  if (int rc = flush_commit(h)) return rc;
+  return materialise_records(h);
+}
+// The scratch of one call (include/ilqr_amd.h states the formula), carved up; then the kernels
+static int run_param_gradient(ilqr_batch* h, int n_dirs, double eps_p, const double* dxs, const double* dus, const double* dlam, double* gp, double* lam,
+                              const char* who) {
+  const size_t nchunk = ((size_t)h->T + 1 + kPgChunk - 1) / kPgChunk;
+  const size_t n_lam = lam ? 0 : (size_t)h->B * (h->T + 1) * h->nx, n_part = gp ? (size_t)h->B * nchunk * n_dirs * kUserNTP : 0;
+  if (int rc = ensure_pg_scratch(h, n_lam + n_part)) return rc;
+  PgArgs a;
+  a.nd = n_dirs, a.nchunk = (int)nchunk, a.eps_p = eps_p == 0.0 ? 1e-3 : eps_p;
+  a.dxs = dxs, a.dus = dus, a.dlam = dlam, a.gp = gp;
+  a.lam = lam ? lam : h->pg_scratch;
+  a.part = h->pg_scratch + n_lam;
+  const char* kernel = "";
+  const int rc = launch_param_gradient(h, a, &kernel);
+  return name_refused_kernel(rc, who, kernel);
+}
+
+int ilqr_param_gradient_on_device(ilqr_batch* h, int n_dirs, int flags, double eps_p, const void* dxs_device, const void* dus_device,
+                                  const void* dlam_device, void* gp_device, void* lam_device) {
+  const char* who = "ilqr_param_gradient_on_device";
+  if (int rc = prepare_param_gradient(h, n_dirs, flags, eps_p, dxs_device, dus_device, dlam_device, gp_device, lam_device, who)) return rc;
+  return run_param_gradient(h, n_dirs, eps_p, (const double*)dxs_device, (const double*)dus_device, (const double*)dlam_device, (double*)gp_device,
+                            (double*)lam_device, who);
+}
+
+int ilqr_get_param_gradient(ilqr_batch* h, int n_dirs, int flags, double eps_p, const double* dxs, const double* dus, const double* dlam, double* gp,
+                            double* lam) {
+  const char* who = "ilqr_get_param_gradient";
+  if (int rc = prepare_param_gradient(h, n_dirs, flags, eps_p, dxs, dus, dlam, gp, lam, who)) return rc;
+  // a call-sized device buffer (the staging buffer: the three inputs, the two outputs), the inputs copied up, the outputs copied out and
+  // waited for
+  const size_t per_x = (size_t)h->B * n_dirs * h->nx, per_u = (size_t)h->B * n_dirs * h->nu;
+  const size_t n_dx = dxs ? per_x * (h->T + 1) : 0, n_du = dus ? per_u * h->T : 0, n_dl = dlam ? per_x * (h->T + 1) : 0,
+               n_gp = gp ? (size_t)h->B * n_dirs * kUserNTP : 0, n_lam = lam ? (size_t)h->B * (h->T + 1) * h->nx : 0;
+  if (int rc = ensure_staging(h, n_dx + n_du + n_dl + n_gp + n_lam)) return rc;
+  double* const d_dx = dxs ? h->staging : nullptr;
+  double* const d_du = dus ? h->staging + n_dx : nullptr;
+  double* const d_dl = dlam ? h->staging + n_dx + n_du : nullptr;
+  double* const d_gp = gp ? h->staging + n_dx + n_du + n_dl : nullptr;
+  double* const d_lam = lam ? h->staging + n_dx + n_du + n_dl + n_gp : nullptr;
+  if (dxs) HIPCHK(hipMemcpyAsync(d_dx, dxs, n_dx * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (dus) HIPCHK(hipMemcpyAsync(d_du, dus, n_du * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (dlam) HIPCHK(hipMemcpyAsync(d_dl, dlam, n_dl * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (int rc = run_param_gradient(h, n_dirs, eps_p, d_dx, d_du, d_dl, d_gp, d_lam, who)) return rc;
+  if (gp) HIPCHK(hipMemcpyAsync(gp, d_gp, n_gp * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (lam) HIPCHK(hipMemcpyAsync(lam, d_lam, n_lam * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }
 

@@ -80,6 +80,10 @@ struct ilqr_batch {
   size_t est_scratch_elems = 0;
   // ilqr_get_risk_sensitive's scratch (risk_wave.hpp: the failure marks, [B]): allocated by the first call (dev_alloc: freed with the handle)
   int* risk_fail = nullptr;
+  // ilqr_get_param_gradient's call-sized scratch (param_gradient.hpp: the costate when the caller takes none, the chunks' partials): as
+  // lq_scratch, allocated by the first call, kept while the next call's fits (ensure_pg_scratch), freed with the handle
+  double* pg_scratch = nullptr;
+  size_t pg_scratch_elems = 0;
   // v is the view every entry point addresses arrays through; for an fp32 handle its trajectory pointers hold
   // the addresses of FLOAT arrays (never dereferenced as double: kernels get vf, the same addresses typed float*)
   BatchView v;
@@ -345,6 +349,18 @@ static int ensure_est_scratch(ilqr_batch* h, size_t elems) {
   }
   HIPCHK(hipMalloc((void**)&h->est_scratch, elems * sizeof(double)));
   h->est_scratch_elems = elems;
+  return 0;
+}
+static int ensure_pg_scratch(ilqr_batch* h, size_t elems) {
+  if (elems <= h->pg_scratch_elems) return 0;
+  if (h->pg_scratch) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipFree(h->pg_scratch));
+    h->pg_scratch = nullptr;
+    h->pg_scratch_elems = 0;
+  }
+  HIPCHK(hipMalloc((void**)&h->pg_scratch, elems * sizeof(double)));
+  h->pg_scratch_elems = elems;
   return 0;
 }
 // One of the handle's arrays as the conversions take it: S knots of E elements per trajectory, of which the knots [t0, t0 + n) are moved

@@ -632,6 +632,32 @@ static int launch_evaluate(ilqr_batch* h, const EvalArgs& e, const char** name) 
   }); });
 }
 
+// The gradient with respect to the per-trajectory parameters (ilqr_get_param_gradient / _on_device; param_gradient.hpp): the costate
+// sweep, then -- when gp is asked for -- the contraction and the reduction of its partials.  The kernels exist only in a build whose twin
+// has NTP; the caller has refused every other handle (check_trajectory_params), carved the scratch and checked that the sizes fit an int.
+static int launch_param_gradient(ilqr_batch* h, const PgArgs& a, const char** name) {
+  *name = param_gradient_kernel_name(h->dtype);
+#ifdef ILQR_HAVE_USER_MODEL
+  if constexpr (kUserGeneric && kUserNTP > 0) {
+    using M = std::decay_t<decltype(h->user_g)>;
+    const unsigned ngroup = (unsigned)((a.nd + pg_shape(kUserNTP).dirs - 1) / pg_shape(kUserNTP).dirs);
+    if (int rc = with_view(h, [&](auto& v) {
+          using S = std::remove_pointer_t<decltype(v.D)>;
+          hipLaunchKernelGGL((k_pg_costate<S, M::NX, M::NU>), dim3(h->B), dim3(64), 0, h->stream, v, a.lam);
+          if (!a.gp) return 0;
+          hipLaunchKernelGGL((k_pg_contract<M, S>), dim3((unsigned)h->B * (unsigned)a.nchunk * ngroup), dim3(64), 0, h->stream, v,
+                             per_trajectory(h, h->user_g), a);
+          hipLaunchKernelGGL((k_pg_reduce<kUserNTP>), dim3((unsigned)(((size_t)h->B * a.nd * kUserNTP + 255) / 256)), dim3(256), 0, h->stream, h->B, a);
+          return 0;
+        }))
+      return rc;
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+#endif
+  return fail(ILQR_ERR_UNSUPPORTED, "%s: this build's user model declares no per-trajectory parameters", *name);
+}
+
 static AlphaSet line_search_alphas() {
   AlphaSet a;
   for (int i = 0; i < NALPHA; i++) a.a[i] = kAlphaHost[i];

@@ -82,6 +82,13 @@ inline const char* risk_kernel_name(bool aos, const WaveVariant& w, int wt) {  /
   return aos ? kWave[w.nt - 1][w.mt - 1][wt - 1] : "k_risk_t";
 }
 inline const char* evaluate_kernel_name(bool aos, bool traj_params) { return !aos ? "k_evaluate_t" : traj_params ? "k_evaluate_g<PT>" : "k_evaluate_g"; }
+// k_pg_contract (param_gradient.hpp): how a wavefront's eight lane octets are shared out for a twin of ntp per-trajectory parameters, as
+// plain data -- dirs directions side by side (ntp <= 4), or passes rounds of eight parameters for one direction (ntp > 8)
+struct ParamGradientShape {
+  int dirs, passes;
+};
+constexpr ParamGradientShape pg_shape(int ntp) { return {ntp >= 1 && ntp <= 4 ? 8 / ntp : 1, ntp > 8 ? (ntp + 7) / 8 : 1}; }
+inline const char* param_gradient_kernel_name(int dtype) { return dtype == ILQR_DTYPE_F32 ? "k_pg_contract<float>" : "k_pg_contract"; }
 
 struct RouteInputs {
   int model, nx, nu, flags, route, ntiles, num_cus;  // (num_cus after ilqr_desc.assume_cus)

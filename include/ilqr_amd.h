@@ -666,6 +666,54 @@ int ilqr_get_trajectory_params(ilqr_batch* h, double* p, int n); /* the rows as 
 /* back to the handle-wide parameters of ilqr_create for every trajectory */
 int ilqr_clear_trajectory_params(ilqr_batch* h);
 
+/* ---- the gradient of a caller's loss with respect to the per-trajectory parameters (additive under ABI 6) ----------------------------
+ * ilqr_solve_lq turns gx = dL/dxs, gu = dL/dus into dxs, dus and the multipliers dlam; these calls turn those three into dL/dp, the
+ * gradient of the loss in the rows of ilqr_set_trajectory_params the solve ran under (masses, dampings, cost weights, targets: system
+ * identification and cost learning through MPC), in one sweep over the horizon with 6 * NTP model evaluations per knot and direction
+ * instead of 2 * NTP whole re-solves.  With the KKT residual r(z, lambda; p) of the nominal problem and ilqr_solve_lq's convention
+ * (K [dz; dlambda] = -[g; 0]) the implicit-function theorem gives dL/dp = d/dp G(p),
+ *     G(p) = sum_{t<T} [ grad_{x,u}(c_t + lam[t+1].F_t)(x_t, u_t; p).(dx_t, du_t) + dlam[t+1].F_t(x_t, u_t; p) ] + grad c_T(x_T; p).dx_T
+ * with F the Euler map x + dt * dynamics(x, u), lam the nominal costate, and (x, u, lam, dx, du, dlam) held fixed while p moves: a
+ * contraction of model derivatives along caller-given vectors, which is how it is defined here.
+ * DEFINITION -- xs, us as ilqr_get_trajectory would return them at this moment (an accepted candidate still waiting to be copied is copied
+ * first), the derivative records as ilqr_get_derivatives would return them, p the rows as they were set (an fp32 handle: their
+ * float-rounded values).  n_dirs directions per trajectory:
+ *     in:  dxs, dlam [B][T+1][n_dirs][nx]   dus [B][T][n_dirs][nu]       (the layouts ilqr_solve_lq writes; dlam[:, 0] is not read)
+ *     out: gp [B][n_dirs][NTP]   lam [B][T+1][nx]
+ * An input that is NULL is zero, not all three; either output may be NULL, not both.
+ *     lam[T] = cx[T],   lam[t] = cx[t] + fx[t]' lam[t+1]                 (t = T-1 .. 0; each sum over r ascending)
+ * For trajectory b, direction s, parameter j:  h = eps_p * max(1, |p[b][j]|) (eps_p = 0 means 1e-3);  M+, M- the handle's model with the
+ * row p[b] + h e_j, p[b] - h e_j applied through set_trajectory_params on the kernel's own copy;  eps = 1e-3, the records' own step.
+ *     t < T:  z = (xs[t], us[t]),  d = (dxs[t][s], dus[t][s]),  n = |d|_2
+ *             Psi(M, sigma) = M.cost(z + sigma (eps / n) d) + lam[t+1] . F_M(z + sigma (eps / n) d)
+ *             A_t = (Psi(M+,+) - Psi(M+,-) - Psi(M-,+) + Psi(M-,-)) * n / (4 eps h),  zero when n = 0
+ *             B_t = dlam[t+1][s] . (F_{M+}(z) - F_{M-}(z)) / (2 h)
+ *     t = T:  A_T the same stencil of final_cost along dxs[T][s]; no B_T
+ *     gp[b][s][j] = sum_t (A_t + B_t)
+ * All arithmetic is double, in UserModelT<double>, on every handle (an fp32 handle's stored floats are widened).  The sum over t runs in a
+ * fixed order (ascending inside chunks of 16 knots, then the chunks ascending) and no atomics are used: repeated calls give the same bits.
+ * Column s of gp depends on column s of the inputs only, bit for bit.  A non-finite evaluation poisons only its own gp[b][s][:].
+ * Read-only: later iterations are bit for bit those of a handle that never asked.  The arrays of a call do not overlap.
+ * What this is NOT: with (dxs, dus, dlam) from ilqr_solve_lq the result is the gradient through the equality-constrained LQ subproblem the
+ * records hold (fx, fu, cxx, cxu, cuu).  That model is Gauss-Newton -- cxx carries no lam.F_zz term --, so the result is exact when the
+ * dynamics are linear in (x, u) and approximate otherwise (pendulum chain, T = 20, a random linear loss, against central differences
+ * over whole re-solves: within 1.6e-5 relative at g/l = 0, inside the re-solves' own step-size noise; off by 0.1 to 19 % at g/l = 9.81).
+ * SCRATCH: the handle keeps one device buffer for these calls, allocated by the first call and kept while the next one's fits, of
+ *     [lam NULL] B * (T + 1) * nx + [gp given] B * ceil((T + 1) / 16) * n_dirs * NTP   doubles.
+ * ILQR_ERR_INVALID (checked first, in this order; the first five need no handle): n_dirs < 1, unknown flag bits, eps_p negative or not
+ * finite, all three inputs NULL, both outputs NULL, a null handle; then B * (T + 1) * n_dirs * max(nx, nu, NTP) beyond INT_MAX.
+ * ILQR_ERR_UNSUPPORTED: every handle on which ilqr_set_trajectory_params is refused -- a build without a user model or whose twin has no
+ * NTP, ILQR_MODEL_HOST and the built-in models, the tiled nx = 4 and small-twin kernels.  ILQR_ERR_STATE: before ilqr_init_traj /
+ * ilqr_set_trajectory, or while no per-trajectory rows are set (the handle-wide user_params have no defined mapping onto the NTP fields).
+ * Every refusal happens before anything is enqueued and ilqr_last_error() names it. */
+enum ilqr_param_gradient_flags { ILQR_PARAM_GRADIENT_NO_FLAGS = 0 }; /* none yet: unknown bits are refused */
+/* host arrays: a call-sized device buffer takes the inputs up and the outputs down; synchronises */
+int ilqr_get_param_gradient(ilqr_batch* h, int n_dirs, int flags, double eps_p, const double* dxs, const double* dus, const double* dlam,
+                            double* gp, double* lam);
+/* device memory of this handle's device: enqueued on the handle's stream, nothing waited for */
+int ilqr_param_gradient_on_device(ilqr_batch* h, int n_dirs, int flags, double eps_p, const void* dxs_device, const void* dus_device,
+                                  const void* dlam_device, void* gp_device, void* lam_device);
+
 /* ---- single stages (teacher-forced parity tests, host-model fallback) --------------------- */
 /* STEP 1, src/ilqr_core.cpp:115-120 = src/derivatives.cpp:15-144 over t = 0..T, all trajectories */
 int ilqr_compute_derivatives(ilqr_batch* h);

@@ -665,6 +665,28 @@ class BatchILQR {
     return p;
   }
   void clear_trajectory_params() { check(ilqr_clear_trajectory_params(h_), "ilqr_clear_trajectory_params"); }
+  // dL/dp, the gradient of the caller's loss in those rows (ilqr_get_param_gradient), from what lq_solve returned for gx = dL/dxs, gu =
+  // dL/dus: dxs, dlam [B][T+1][n_dirs][nx], dus [B][T][n_dirs][nu] (null = zero, not all three).  Returns gp [B][n_dirs][NTP]; lam, if asked
+  // for, is the nominal costate [B][T+1][nx].  eps_p: the relative parameter step (0 = 1e-3).
+  std::vector<double> param_gradient(int n_dirs, const std::vector<double>* dxs, const std::vector<double>* dus, const std::vector<double>* dlam,
+                                     std::vector<double>* lam = nullptr, double eps_p = 0.0) {
+    const size_t dirs = (size_t)B_ * (n_dirs > 0 ? n_dirs : 0);
+    require((!dxs || dxs->size() == dirs * (T_ + 1) * n_) && (!dus || dus->size() == dirs * T_ * m_) && (!dlam || dlam->size() == dirs * (T_ + 1) * n_),
+            "param_gradient: dxs, dlam [B][T+1][n_dirs][nx], dus [B][T][n_dirs][nu]");
+    const int ntp = ilqr_trajectory_params_count();
+    std::vector<double> gp(dirs * (ntp > 0 ? ntp : 1), 0.0);
+    if (lam) lam->assign((size_t)B_ * (T_ + 1) * n_, 0.0);
+    check(ilqr_get_param_gradient(h_, n_dirs, 0, eps_p, dxs ? dxs->data() : nullptr, dus ? dus->data() : nullptr, dlam ? dlam->data() : nullptr,
+                                  gp.data(), lam ? lam->data() : nullptr),
+          "ilqr_get_param_gradient");
+    return gp;
+  }
+  // ... or from and into caller-owned device memory, on the handle's stream, nothing waited for
+  void param_gradient_on_device(int n_dirs, int flags, double eps_p, const void* dxs_device, const void* dus_device, const void* dlam_device,
+                                void* gp_device, void* lam_device) {
+    check(ilqr_param_gradient_on_device(h_, n_dirs, flags, eps_p, dxs_device, dus_device, dlam_device, gp_device, lam_device),
+          "ilqr_param_gradient_on_device");
+  }
   std::vector<int> status() {
     std::vector<int> s(B_);
     check(ilqr_get_status(h_, s.data(), nullptr, nullptr), "ilqr_get_status");
