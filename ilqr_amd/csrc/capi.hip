@@ -40,6 +40,7 @@
 using namespace ilqr;
 
 #include "route.hpp"
+#include "staging.hpp"
 #include "handle.hpp"
 #include "launch.hpp"
 
@@ -982,17 +983,8 @@ static int prepare_value(ilqr_batch* h, int t0, int n_knots, const void* Vx, con
   HIPCHK(hipSetDevice(h->device));
   return materialise_records(h);
 }
-// a launch that was itself refused says which kernel (run_value, run_evaluate)
-static int name_refused_kernel(int rc, const char* who, const char* kernel) {
-  if (rc != ILQR_ERR_HIP) return rc;
-  char keep[sizeof(g_err)];
-  memcpy(keep, g_err, sizeof(keep));
-  return fail(rc, "%s: %s: %.400s", who, kernel, keep);
-}
 static int run_value(ilqr_batch* h, int t0, int n_knots, double* Vx, double* Vxx, const char* who) {
-  const char* kernel = "";
-  const int rc = launch_value(h, t0, n_knots, Vx, Vxx, &kernel);
-  return name_refused_kernel(rc, who, kernel);
+  return run_launch(who, [&](const char** kernel) { return launch_value(h, t0, n_knots, Vx, Vxx, kernel); });
 }
 
 int ilqr_copy_value_to_device(ilqr_batch* h, int t0, int n_knots, void* Vx_device, void* Vxx_device) {
@@ -1002,16 +994,11 @@ int ilqr_copy_value_to_device(ilqr_batch* h, int t0, int n_knots, void* Vx_devic
 
 int ilqr_get_value(ilqr_batch* h, int t0, int n_knots, double* Vx, double* Vxx) {
   if (int rc = prepare_value(h, t0, n_knots, Vx, Vxx, "ilqr_get_value")) return rc;
-  // a window-sized device buffer (the staging buffer: Vx, then Vxx), copied out and waited for
-  const size_t n_vx = Vx ? (size_t)h->B * n_knots * h->nx : 0, n_vxx = Vxx ? (size_t)h->B * n_knots * h->nx * h->nx : 0;
-  if (int rc = ensure_staging(h, n_vx + n_vxx)) return rc;
-  double* const d_vx = Vx ? h->staging : nullptr;
-  double* const d_vxx = Vxx ? h->staging + n_vx : nullptr;
-  if (int rc = run_value(h, t0, n_knots, d_vx, d_vxx, "ilqr_get_value")) return rc;
-  if (Vx) HIPCHK(hipMemcpyAsync(Vx, d_vx, n_vx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (Vxx) HIPCHK(hipMemcpyAsync(Vxx, d_vxx, n_vxx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return 0;
+  // a window-sized device buffer (the staging buffer, laid out by staging.hpp), copied out and waited for
+  StagePlan p = stage_value(stage_dims(h), n_knots, Vx, Vxx);
+  if (int rc = stage_up(h, p)) return rc;
+  if (int rc = run_value(h, t0, n_knots, p.dev(0), p.dev(1), "ilqr_get_value")) return rc;
+  return stage_down(h, p);
 }
 
 // ---- the closed-loop covariance of the stored policy (additive under ABI 6; covariance_wave.hpp) ------
@@ -1026,9 +1013,7 @@ static int prepare_covariance(ilqr_batch* h, int t0, int n_knots, const void* Si
   return materialise_records(h);
 }
 static int run_covariance(ilqr_batch* h, const CovArgs& q, const char* who) {
-  const char* kernel = "";
-  const int rc = launch_covariance(h, q, &kernel);
-  return name_refused_kernel(rc, who, kernel);
+  return run_launch(who, [&](const char** kernel) { return launch_covariance(h, q, kernel); });
 }
 
 int ilqr_copy_covariance_to_device(ilqr_batch* h, int t0, int n_knots, const void* Sigma0_device, const void* W_device, void* Sigma_device,
@@ -1041,23 +1026,11 @@ int ilqr_copy_covariance_to_device(ilqr_batch* h, int t0, int n_knots, const voi
 int ilqr_get_covariance(ilqr_batch* h, int t0, int n_knots, const double* Sigma0, const double* W, double* Sigma, double* Su, double* expected_cost) {
   const char* who = "ilqr_get_covariance";
   if (int rc = prepare_covariance(h, t0, n_knots, Sigma, Su, expected_cost, who)) return rc;
-  // a call-sized device buffer (the staging buffer: Sigma0, W, then the outputs asked for), copied out and waited for
-  const size_t nn = (size_t)h->B * h->nx * h->nx;
-  const size_t n_s0 = Sigma0 ? nn : 0, n_w = W ? nn : 0, n_s = Sigma ? nn * n_knots : 0, n_u = Su ? (size_t)h->B * n_knots * h->nu * h->nu : 0, n_j = expected_cost ? h->B : 0;
-  if (int rc = ensure_staging(h, n_s0 + n_w + n_s + n_u + n_j)) return rc;
-  double* const d_s0 = Sigma0 ? h->staging : nullptr;
-  double* const d_w = W ? h->staging + n_s0 : nullptr;
-  double* const d_s = Sigma ? h->staging + n_s0 + n_w : nullptr;
-  double* const d_u = Su ? h->staging + n_s0 + n_w + n_s : nullptr;
-  double* const d_j = expected_cost ? h->staging + n_s0 + n_w + n_s + n_u : nullptr;
-  if (Sigma0) HIPCHK(hipMemcpyAsync(d_s0, Sigma0, n_s0 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (W) HIPCHK(hipMemcpyAsync(d_w, W, n_w * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (int rc = run_covariance(h, {t0, n_knots, d_s0, d_w, d_s, d_u, d_j}, who)) return rc;
-  if (Sigma) HIPCHK(hipMemcpyAsync(Sigma, d_s, n_s * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (Su) HIPCHK(hipMemcpyAsync(Su, d_u, n_u * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (expected_cost) HIPCHK(hipMemcpyAsync(expected_cost, d_j, n_j * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return 0;
+  // a call-sized device buffer (the staging buffer, laid out by staging.hpp), the inputs copied up, the outputs copied out and waited for
+  StagePlan p = stage_covariance(stage_dims(h), n_knots, Sigma0, W, Sigma, Su, expected_cost);
+  if (int rc = stage_up(h, p)) return rc;
+  if (int rc = run_covariance(h, {t0, n_knots, p.dev(0), p.dev(1), p.dev(2), p.dev(3), p.dev(4)}, who)) return rc;
+  return stage_down(h, p);
 }
 
 // ---- the tangent and the adjoint of the stored closed loop (additive under ABI 6; sensitivity_wave.hpp) ------
@@ -1085,45 +1058,10 @@ static int prepare_adjoint(ilqr_batch* h, int t0, int n_knots, int n_dirs, const
   return prepare_sensitivity(h, t0, n_knots, n_dirs, gx, gu, g_x0, g_v, gu, "gx and gu", "g_x0 and g_v", "gu", who);
 }
 static int run_tangent(ilqr_batch* h, const TangentArgs& q, const char* who) {
-  const char* kernel = "";
-  const int rc = launch_tangent(h, q, &kernel);
-  return name_refused_kernel(rc, who, kernel);
+  return run_launch(who, [&](const char** kernel) { return launch_tangent(h, q, kernel); });
 }
 static int run_adjoint(ilqr_batch* h, const AdjointArgs& q, const char* who) {
-  const char* kernel = "";
-  const int rc = launch_adjoint(h, q, &kernel);
-  return name_refused_kernel(rc, who, kernel);
-}
-// the element counts of the four arrays of a call: state-sized over one knot, control-sized over the horizon, state-sized over the
-// window, control-sized over the window's knots with a control (tangent: dx0, dv, dxs, dus; adjoint: g_x0, g_v, gx, gu)
-struct SensSizes {
-  size_t x_one, u_all, x_win, u_win;
-};
-static SensSizes sensitivity_sizes(const ilqr_batch* h, int t0, int n_knots, int n_dirs) {
-  const size_t per_x = (size_t)h->B * n_dirs * h->nx, per_u = (size_t)h->B * n_dirs * h->nu;
-  return {per_x, per_u * h->T, per_x * n_knots, per_u * (std::min(t0 + n_knots, h->T) - t0)};
-}
-// a call-sized device buffer (the staging buffer: the two inputs, then the two outputs): the inputs copied up before the kernel ...
-struct SensStaging {
-  double *in_a, *in_b, *out_a, *out_b;
-  size_t n_out_a, n_out_b;
-};
-static int stage_sensitivity_up(ilqr_batch* h, const double* in_a, size_t n_in_a, const double* in_b, size_t n_in_b, bool want_a, size_t n_out_a, bool want_b,
-                                size_t n_out_b, SensStaging* s) {
-  n_in_a = in_a ? n_in_a : 0, n_in_b = in_b ? n_in_b : 0, n_out_a = want_a ? n_out_a : 0, n_out_b = want_b ? n_out_b : 0;
-  if (int rc = ensure_staging(h, n_in_a + n_in_b + n_out_a + n_out_b)) return rc;
-  *s = {in_a ? h->staging : nullptr, in_b ? h->staging + n_in_a : nullptr, want_a ? h->staging + n_in_a + n_in_b : nullptr,
-        want_b ? h->staging + n_in_a + n_in_b + n_out_a : nullptr, n_out_a, n_out_b};
-  if (in_a) HIPCHK(hipMemcpyAsync(s->in_a, in_a, n_in_a * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (in_b) HIPCHK(hipMemcpyAsync(s->in_b, in_b, n_in_b * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  return 0;
-}
-// ... and the outputs copied out and waited for after it
-static int stage_sensitivity_down(ilqr_batch* h, const SensStaging& s, double* out_a, double* out_b) {
-  if (out_a) HIPCHK(hipMemcpyAsync(out_a, s.out_a, s.n_out_a * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (out_b) HIPCHK(hipMemcpyAsync(out_b, s.out_b, s.n_out_b * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return 0;
+  return run_launch(who, [&](const char** kernel) { return launch_adjoint(h, q, kernel); });
 }
 
 int ilqr_copy_tangent_to_device(ilqr_batch* h, int t0, int n_knots, int n_dirs, const void* dx0_device, const void* dv_device, void* dxs_device,
@@ -1136,11 +1074,10 @@ int ilqr_copy_tangent_to_device(ilqr_batch* h, int t0, int n_knots, int n_dirs, 
 int ilqr_get_tangent(ilqr_batch* h, int t0, int n_knots, int n_dirs, const double* dx0, const double* dv, double* dxs, double* dus) {
   const char* who = "ilqr_get_tangent";
   if (int rc = prepare_tangent(h, t0, n_knots, n_dirs, dx0, dv, dxs, dus, who)) return rc;
-  const SensSizes n = sensitivity_sizes(h, t0, n_knots, n_dirs);
-  SensStaging d;
-  if (int rc = stage_sensitivity_up(h, dx0, n.x_one, dv, n.u_all, dxs != nullptr, n.x_win, dus != nullptr, n.u_win, &d)) return rc;
-  if (int rc = run_tangent(h, {t0, n_knots, n_dirs, d.in_a, d.in_b, d.out_a, d.out_b}, who)) return rc;
-  return stage_sensitivity_down(h, d, dxs, dus);
+  StagePlan p = stage_tangent(stage_dims(h), t0, n_knots, n_dirs, dx0, dv, dxs, dus);
+  if (int rc = stage_up(h, p)) return rc;
+  if (int rc = run_tangent(h, {t0, n_knots, n_dirs, p.dev(0), p.dev(1), p.dev(2), p.dev(3)}, who)) return rc;
+  return stage_down(h, p);
 }
 
 int ilqr_copy_adjoint_to_device(ilqr_batch* h, int t0, int n_knots, int n_dirs, const void* gx_device, const void* gu_device, void* g_x0_device,
@@ -1153,11 +1090,10 @@ int ilqr_copy_adjoint_to_device(ilqr_batch* h, int t0, int n_knots, int n_dirs, 
 int ilqr_get_adjoint(ilqr_batch* h, int t0, int n_knots, int n_dirs, const double* gx, const double* gu, double* g_x0, double* g_v) {
   const char* who = "ilqr_get_adjoint";
   if (int rc = prepare_adjoint(h, t0, n_knots, n_dirs, gx, gu, g_x0, g_v, who)) return rc;
-  const SensSizes n = sensitivity_sizes(h, t0, n_knots, n_dirs);
-  SensStaging d;
-  if (int rc = stage_sensitivity_up(h, gx, n.x_win, gu, n.u_win, g_x0 != nullptr, n.x_one, g_v != nullptr, n.u_all, &d)) return rc;
-  if (int rc = run_adjoint(h, {t0, n_knots, n_dirs, d.in_a, d.in_b, d.out_a, d.out_b}, who)) return rc;
-  return stage_sensitivity_down(h, d, g_x0, g_v);
+  StagePlan p = stage_adjoint(stage_dims(h), t0, n_knots, n_dirs, gx, gu, g_x0, g_v);
+  if (int rc = stage_up(h, p)) return rc;
+  if (int rc = run_adjoint(h, {t0, n_knots, n_dirs, p.dev(0), p.dev(1), p.dev(2), p.dev(3)}, who)) return rc;
+  return stage_down(h, p);
 }
 
 // ---- the LQ subproblem of the records, solved for the caller's linear terms (additive under ABI 6; lq_solve_wave.hpp) ------
@@ -1193,9 +1129,7 @@ static int run_lq_solve(ilqr_batch* h, int n_dirs, int flags, double mu, const d
   q.Mi = q.Kd + n_kd;
   q.P = dlam ? q.Mi + n_mi : nullptr;
   q.kd = dus ? dus : q.Mi + n_mi + n_p;
-  const char* kernel = "";
-  const int rc = launch_lq_solve(h, q, &kernel);
-  return name_refused_kernel(rc, who, kernel);
+  return run_launch(who, [&](const char** kernel) { return launch_lq_solve(h, q, kernel); });
 }
 
 int ilqr_solve_lq_on_device(ilqr_batch* h, int n_dirs, int flags, double mu, const void* dx0_device, const void* gx_device, const void* gu_device,
@@ -1210,29 +1144,11 @@ int ilqr_solve_lq(ilqr_batch* h, int n_dirs, int flags, double mu, const double*
                   double* dlam, int* info) {
   const char* who = "ilqr_solve_lq";
   if (int rc = prepare_lq_solve(h, n_dirs, flags, mu, dx0, gx, gu, dxs, dus, dlam, who)) return rc;
-  // a call-sized device buffer (the staging buffer: the three inputs, the three outputs, info), the inputs copied up, the outputs copied
-  // out and waited for
-  const size_t per_x = (size_t)h->B * n_dirs * h->nx, per_u = (size_t)h->B * n_dirs * h->nu;
-  const size_t n_x0 = dx0 ? per_x : 0, n_gx = gx ? per_x * (h->T + 1) : 0, n_gu = gu ? per_u * h->T : 0, n_dxs = dxs ? per_x * (h->T + 1) : 0,
-               n_dus = dus ? per_u * h->T : 0, n_dl = dlam ? per_x * (h->T + 1) : 0, n_info = info ? ((size_t)h->B + 1) / 2 : 0;
-  if (int rc = ensure_staging(h, n_x0 + n_gx + n_gu + n_dxs + n_dus + n_dl + n_info)) return rc;
-  double* const d_x0 = dx0 ? h->staging : nullptr;
-  double* const d_gx = gx ? h->staging + n_x0 : nullptr;
-  double* const d_gu = gu ? h->staging + n_x0 + n_gx : nullptr;
-  double* const d_dxs = dxs ? h->staging + n_x0 + n_gx + n_gu : nullptr;
-  double* const d_dus = dus ? h->staging + n_x0 + n_gx + n_gu + n_dxs : nullptr;
-  double* const d_dl = dlam ? h->staging + n_x0 + n_gx + n_gu + n_dxs + n_dus : nullptr;
-  int* const d_info = info ? (int*)(h->staging + n_x0 + n_gx + n_gu + n_dxs + n_dus + n_dl) : nullptr;
-  if (dx0) HIPCHK(hipMemcpyAsync(d_x0, dx0, n_x0 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (gx) HIPCHK(hipMemcpyAsync(d_gx, gx, n_gx * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (gu) HIPCHK(hipMemcpyAsync(d_gu, gu, n_gu * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (int rc = run_lq_solve(h, n_dirs, flags, mu, d_x0, d_gx, d_gu, d_dxs, d_dus, d_dl, d_info, who)) return rc;
-  if (dxs) HIPCHK(hipMemcpyAsync(dxs, d_dxs, n_dxs * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (dus) HIPCHK(hipMemcpyAsync(dus, d_dus, n_dus * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (dlam) HIPCHK(hipMemcpyAsync(dlam, d_dl, n_dl * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (info) HIPCHK(hipMemcpyAsync(info, d_info, (size_t)h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return 0;
+  // a call-sized device buffer (the staging buffer, laid out by staging.hpp), the inputs copied up, the outputs copied out and waited for
+  StagePlan p = stage_lq_solve(stage_dims(h), n_dirs, dx0, gx, gu, dxs, dus, dlam, info);
+  if (int rc = stage_up(h, p)) return rc;
+  if (int rc = run_lq_solve(h, n_dirs, flags, mu, p.dev(0), p.dev(1), p.dev(2), p.dev(3), p.dev(4), p.dev(5), (int*)p.dev(6), who)) return rc;
+  return stage_down(h, p);
 }
 
 // ---- the Kalman filter of the stored linearisation and the output-feedback covariance (additive under ABI 6; estimator_wave.hpp) ------
@@ -1259,9 +1175,7 @@ static int run_estimator(ilqr_batch* h, EstArgs q, const char* who) {
   q.fail = (int*)h->est_scratch;
   q.Pfs = n_mat ? h->est_scratch + n_fail : nullptr;
   q.Ns = n_mat ? q.Pfs + n_mat : nullptr;
-  const char* kernel = "";
-  const int rc = launch_estimator(h, q, &kernel);
-  return name_refused_kernel(rc, who, kernel);
+  return run_launch(who, [&](const char** kernel) { return launch_estimator(h, q, kernel); });
 }
 
 int ilqr_copy_estimator_to_device(ilqr_batch* h, int t0, int n_knots, int ny, const void* H_device, const void* P0_device, const void* W_device,
@@ -1278,38 +1192,13 @@ int ilqr_get_estimator(ilqr_batch* h, int t0, int n_knots, int ny, const double*
                        double* Pf, double* L, double* Sigma, double* Su, double* expected_cost, int* info) {
   const char* who = "ilqr_get_estimator";
   if (int rc = prepare_estimator(h, t0, n_knots, ny, H, V, Pp, Pf, L, Sigma, Su, expected_cost, who)) return rc;
-  // a call-sized device buffer (the staging buffer: the four inputs, the six outputs, info), the inputs copied up, the outputs copied out
-  // and waited for
-  const size_t B = (size_t)h->B, nn = B * h->nx * h->nx;
-  const size_t n_in[4] = {B * ny * h->nx, P0 ? nn : 0, W ? nn : 0, B * ny * ny};
-  const size_t n_out[7] = {Pp ? nn * n_knots : 0, Pf ? nn * n_knots : 0, L ? B * n_knots * h->nx * ny : 0, Sigma ? nn * n_knots : 0,
-                           Su ? B * n_knots * h->nu * h->nu : 0, expected_cost ? B : 0, info ? (B + 1) / 2 : 0};
-  size_t total = 0;
-  for (size_t e : n_in) total += e;
-  for (size_t e : n_out) total += e;
-  if (int rc = ensure_staging(h, total)) return rc;
-  const double* const src[4] = {H, P0, W, V};
-  double* d_in[4];
-  double* d_out[7];
-  double* at = h->staging;
-  for (int i = 0; i < 4; i++) {
-    d_in[i] = n_in[i] ? at : nullptr;
-    at += n_in[i];
-    if (n_in[i]) HIPCHK(hipMemcpyAsync(d_in[i], src[i], n_in[i] * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  }
-  for (int i = 0; i < 7; i++) {
-    d_out[i] = n_out[i] ? at : nullptr;
-    at += n_out[i];
-  }
-  if (int rc = run_estimator(h, {t0, n_knots, ny, d_in[0], d_in[1], d_in[2], d_in[3], d_out[0], d_out[1], d_out[2], d_out[3], d_out[4], d_out[5],
-                                 (int*)d_out[6], nullptr, nullptr, nullptr}, who))
+  // a call-sized device buffer (the staging buffer, laid out by staging.hpp), the inputs copied up, the outputs copied out and waited for
+  StagePlan p = stage_estimator(stage_dims(h), n_knots, ny, H, P0, W, V, Pp, Pf, L, Sigma, Su, expected_cost, info);
+  if (int rc = stage_up(h, p)) return rc;
+  if (int rc = run_estimator(h, {t0, n_knots, ny, p.dev(0), p.dev(1), p.dev(2), p.dev(3), p.dev(4), p.dev(5), p.dev(6), p.dev(7), p.dev(8), p.dev(9),
+                                 (int*)p.dev(10), nullptr, nullptr, nullptr}, who))
     return rc;
-  double* const dst[6] = {Pp, Pf, L, Sigma, Su, expected_cost};
-  for (int i = 0; i < 6; i++)
-    if (dst[i]) HIPCHK(hipMemcpyAsync(dst[i], d_out[i], n_out[i] * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (info) HIPCHK(hipMemcpyAsync(info, d_out[6], B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return 0;
+  return stage_down(h, p);
 }
 
 // ---- the risk-sensitive (LEQG) gains and value of the records' LQ model (additive under ABI 6; risk_wave.hpp) ------
@@ -1334,9 +1223,7 @@ static int run_risk(ilqr_batch* h, RiskArgs q, const char* who) {
   if (!h->risk_fail)
     if (int rc = dev_alloc(h, &h->risk_fail, (size_t)h->Bp)) return rc;
   q.fail = h->risk_fail;
-  const char* kernel = "";
-  const int rc = launch_risk(h, q, &kernel);
-  return name_refused_kernel(rc, who, kernel);
+  return run_launch(who, [&](const char** kernel) { return launch_risk(h, q, kernel); });
 }
 
 int ilqr_copy_risk_sensitive_to_device(ilqr_batch* h, int nw, double theta, int flags, double mu, const void* C_device, void* K_device, void* k_device,
@@ -1351,31 +1238,13 @@ int ilqr_get_risk_sensitive(ilqr_batch* h, int nw, double theta, int flags, doub
                             double* risk_cost, int* info) {
   const char* who = "ilqr_get_risk_sensitive";
   if (int rc = prepare_risk(h, nw, theta, flags, mu, C, K, k, Vx, Vxx, risk_cost, who)) return rc;
-  // a call-sized device buffer (the staging buffer: C, the five outputs, info), C copied up, the outputs copied out and waited for
-  const size_t B = (size_t)h->B, T = (size_t)h->T, n = (size_t)h->nx, m = (size_t)h->nu;
-  const size_t n_c = B * n * nw;
-  const size_t n_out[6] = {K ? B * T * m * n : 0, k ? B * T * m : 0, Vx ? B * (T + 1) * n : 0, Vxx ? B * (T + 1) * n * n : 0, risk_cost ? B : 0,
-                           info ? (B + 1) / 2 : 0};
-  size_t total = n_c;
-  for (size_t e : n_out) total += e;
-  if (int rc = ensure_staging(h, total)) return rc;
-  double* const d_c = h->staging;
-  double* d_out[6];
-  double* at = h->staging + n_c;
-  for (int i = 0; i < 6; i++) {
-    d_out[i] = n_out[i] ? at : nullptr;
-    at += n_out[i];
-  }
-  HIPCHK(hipMemcpyAsync(d_c, C, n_c * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (int rc = run_risk(h, {nw, (flags & ILQR_LQ_HOLD_CLAMPED) ? 1 : 0, theta, mu, d_c, d_out[0], d_out[1], d_out[2], d_out[3], d_out[4],
-                            (int*)d_out[5], nullptr}, who))
+  // a call-sized device buffer (the staging buffer, laid out by staging.hpp), C copied up, the outputs copied out and waited for
+  StagePlan p = stage_risk(stage_dims(h), nw, C, K, k, Vx, Vxx, risk_cost, info);
+  if (int rc = stage_up(h, p)) return rc;
+  if (int rc = run_risk(h, {nw, (flags & ILQR_LQ_HOLD_CLAMPED) ? 1 : 0, theta, mu, p.dev(0), p.dev(1), p.dev(2), p.dev(3), p.dev(4), p.dev(5),
+                            (int*)p.dev(6), nullptr}, who))
     return rc;
-  double* const dst[5] = {K, k, Vx, Vxx, risk_cost};
-  for (int i = 0; i < 5; i++)
-    if (dst[i]) HIPCHK(hipMemcpyAsync(dst[i], d_out[i], n_out[i] * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (info) HIPCHK(hipMemcpyAsync(info, d_out[5], B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return 0;
+  return stage_down(h, p);
 }
 
 // ---- the stored policy applied to caller-given states (additive under ABI 6; evaluate.hpp) ------
@@ -1395,9 +1264,7 @@ static int prepare_evaluate(ilqr_batch* h, int t0, int n_knots, int n_samples, i
   return flush_commit(h);
 }
 static int run_evaluate(ilqr_batch* h, const EvalArgs& e, const char* who) {
-  const char* kernel = "";
-  const int rc = launch_evaluate(h, e, &kernel);
-  return name_refused_kernel(rc, who, kernel);
+  return run_launch(who, [&](const char** kernel) { return launch_evaluate(h, e, kernel); });
 }
 static int eval_clamp(const ilqr_batch* h, int flags) { return ((flags & ILQR_EVAL_CLAMP) || (h->sp.fixes & 1)) ? 1 : 0; }
 
@@ -1412,21 +1279,11 @@ int ilqr_evaluate_policy(ilqr_batch* h, int t0, int n_knots, int n_samples, int 
                          double* u_first) {
   const char* who = "ilqr_evaluate_policy";
   if (int rc = prepare_evaluate(h, t0, n_knots, n_samples, flags, x, cost, x_end, u_first, who)) return rc;
-  // a call-sized device buffer (the staging buffer: x, then the outputs asked for), copied out and waited for
-  const size_t R = (size_t)h->B * n_samples;
-  const size_t n_x = R * h->nx, n_c = cost ? R : 0, n_e = x_end ? R * h->nx : 0, n_u = u_first ? R * h->nu : 0;
-  if (int rc = ensure_staging(h, n_x + n_c + n_e + n_u)) return rc;
-  double* const d_x = h->staging;
-  double* const d_c = cost ? d_x + n_x : nullptr;
-  double* const d_e = x_end ? d_x + n_x + n_c : nullptr;
-  double* const d_u = u_first ? d_x + n_x + n_c + n_e : nullptr;
-  HIPCHK(hipMemcpyAsync(d_x, x, n_x * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (int rc = run_evaluate(h, {t0, n_knots, n_samples, eval_clamp(h, flags), d_x, d_c, d_e, d_u}, who)) return rc;
-  if (cost) HIPCHK(hipMemcpyAsync(cost, d_c, n_c * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (x_end) HIPCHK(hipMemcpyAsync(x_end, d_e, n_e * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (u_first) HIPCHK(hipMemcpyAsync(u_first, d_u, n_u * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return 0;
+  // a call-sized device buffer (the staging buffer, laid out by staging.hpp), x copied up, the outputs copied out and waited for
+  StagePlan p = stage_evaluate(stage_dims(h), n_samples, x, cost, x_end, u_first);
+  if (int rc = stage_up(h, p)) return rc;
+  if (int rc = run_evaluate(h, {t0, n_knots, n_samples, eval_clamp(h, flags), p.dev(0), p.dev(1), p.dev(2), p.dev(3)}, who)) return rc;
+  return stage_down(h, p);
 }
 
 // ---- per-trajectory model parameters (additive under ABI 6) ------------------------------------
@@ -1515,9 +1372,7 @@ static int run_param_gradient(ilqr_batch* h, int n_dirs, double eps_p, const dou
   a.dxs = dxs, a.dus = dus, a.dlam = dlam, a.gp = gp;
   a.lam = lam ? lam : h->pg_scratch;
   a.part = h->pg_scratch + n_lam;
-  const char* kernel = "";
-  const int rc = launch_param_gradient(h, a, &kernel);
-  return name_refused_kernel(rc, who, kernel);
+  return run_launch(who, [&](const char** kernel) { return launch_param_gradient(h, a, kernel); });
 }
 
 int ilqr_param_gradient_on_device(ilqr_batch* h, int n_dirs, int flags, double eps_p, const void* dxs_device, const void* dus_device,
@@ -1532,25 +1387,11 @@ int ilqr_get_param_gradient(ilqr_batch* h, int n_dirs, int flags, double eps_p, 
                             double* lam) {
   const char* who = "ilqr_get_param_gradient";
   if (int rc = prepare_param_gradient(h, n_dirs, flags, eps_p, dxs, dus, dlam, gp, lam, who)) return rc;
-  // a call-sized device buffer (the staging buffer: the three inputs, the two outputs), the inputs copied up, the outputs copied out and
-  // waited for
-  const size_t per_x = (size_t)h->B * n_dirs * h->nx, per_u = (size_t)h->B * n_dirs * h->nu;
-  const size_t n_dx = dxs ? per_x * (h->T + 1) : 0, n_du = dus ? per_u * h->T : 0, n_dl = dlam ? per_x * (h->T + 1) : 0,
-               n_gp = gp ? (size_t)h->B * n_dirs * kUserNTP : 0, n_lam = lam ? (size_t)h->B * (h->T + 1) * h->nx : 0;
-  if (int rc = ensure_staging(h, n_dx + n_du + n_dl + n_gp + n_lam)) return rc;
-  double* const d_dx = dxs ? h->staging : nullptr;
-  double* const d_du = dus ? h->staging + n_dx : nullptr;
-  double* const d_dl = dlam ? h->staging + n_dx + n_du : nullptr;
-  double* const d_gp = gp ? h->staging + n_dx + n_du + n_dl : nullptr;
-  double* const d_lam = lam ? h->staging + n_dx + n_du + n_dl + n_gp : nullptr;
-  if (dxs) HIPCHK(hipMemcpyAsync(d_dx, dxs, n_dx * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (dus) HIPCHK(hipMemcpyAsync(d_du, dus, n_du * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (dlam) HIPCHK(hipMemcpyAsync(d_dl, dlam, n_dl * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (int rc = run_param_gradient(h, n_dirs, eps_p, d_dx, d_du, d_dl, d_gp, d_lam, who)) return rc;
-  if (gp) HIPCHK(hipMemcpyAsync(gp, d_gp, n_gp * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (lam) HIPCHK(hipMemcpyAsync(lam, d_lam, n_lam * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return 0;
+  // a call-sized device buffer (the staging buffer, laid out by staging.hpp), the inputs copied up, the outputs copied out and waited for
+  StagePlan p = stage_param_gradient(stage_dims(h), n_dirs, dxs, dus, dlam, gp, lam);
+  if (int rc = stage_up(h, p)) return rc;
+  if (int rc = run_param_gradient(h, n_dirs, eps_p, p.dev(0), p.dev(1), p.dev(2), p.dev(3), p.dev(4), who)) return rc;
+  return stage_down(h, p);
 }
 
 // ---- stages --------------------------------------------------------------------------------

@@ -94,7 +94,7 @@ struct ilqr_batch {
   int* commit_idx = nullptr;
   long long* phase_ticks = nullptr;  // [ntiles][5] per-tile clocks of k_solve_tile: sweep+backward, rollouts+accept, iterations, shader cycles, wall ticks
   double wall_clock_khz = 100000.0;
-  double* staging = nullptr;  // device scratch for canonical <-> tiled conversion
+  double* staging = nullptr;  // device scratch for canonical <-> tiled conversion and for the host getters' arrays (staging.hpp)
   double* x0_stage = nullptr;  // [B][nx] canonical: a host x0 of ilqr_mpc_step on its way to the device layout (never reallocated, never waited for)
   // LQ model with exact derivatives: the sweep writes one copy of the constant matrices (const_rec) and
   // per knot only cx, cu; records_partial says that D holds no matrices for t < T right now
@@ -363,6 +363,22 @@ static int ensure_pg_scratch(ilqr_batch* h, size_t elems) {
   h->pg_scratch_elems = elems;
   return 0;
 }
+// A host getter's arrays (staging.hpp): room for the plan in the staging buffer, every segment's device pointer, the inputs on their way up ...
+static int stage_up(ilqr_batch* h, StagePlan& p) {
+  if (int rc = ensure_staging(h, p.total)) return rc;
+  p.resolve(h->staging);
+  for (int i = 0; i < p.n; i++)
+    if (const StageSeg& s = p.seg[i]; s.up && s.host) HIPCHK(hipMemcpyAsync(s.dev, s.host, s.bytes(), hipMemcpyHostToDevice, h->stream));
+  return 0;
+}
+// ... and, after the kernels, the outputs copied out and waited for
+static int stage_down(ilqr_batch* h, const StagePlan& p) {
+  for (int i = 0; i < p.n; i++)
+    if (const StageSeg& s = p.seg[i]; !s.up && s.host) HIPCHK(hipMemcpyAsync(s.host, s.dev, s.bytes(), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+static StageDims stage_dims(const ilqr_batch* h) { return {(size_t)h->B, (size_t)h->T, (size_t)h->nx, (size_t)h->nu, (size_t)kUserNTP}; }
 // One of the handle's arrays as the conversions take it: S knots of E elements per trajectory, of which the knots [t0, t0 + n) are moved
 // (n = 0: all S).  rec: not a plain array but the E elements from offset `off` of every knot's derivative record.
 struct DevArray {

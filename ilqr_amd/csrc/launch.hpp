@@ -2,7 +2,8 @@
 // at launch -- the handle's device model and arithmetic, its route plan (which of several equivalent kernels it runs: route.hpp,
 // DESIGN.md 3.2), its sizes -- reaches that expression as a type, through the with_* dispatchers here and in handle.hpp.  Where only
 // some combinations of a kernel's switches are built, the `if constexpr` beside the launch is the list of them: a generic lambda
-// instantiates whatever it is handed, so a combination that is not excluded there is compiled.  Included once, by capi.hip.
+// instantiates whatever it is handed, so a combination that is not excluded there is compiled.  The wavefront-per-trajectory kernels of the
+// stored-model queries share one such list and one dispatcher, with_wave_tiles.  Included once, by capi.hip.
 #pragma once
 #include "handle.hpp"
 
@@ -392,6 +393,30 @@ static int launch_solve_tiles(ilqr_batch* h, int n_iters) {
   return timer_end(h, ILQR_STAGE_SOLVE, ev);
 }
 
+// launch(&kernel) of a stored-model query (the launch_* below) for the entry point `who`: a launch that was itself refused says which kernel
+template <class L>
+static int run_launch(const char* who, L&& launch) {
+  const char* kernel = "";
+  const int rc = launch(&kernel);
+  if (rc != ILQR_ERR_HIP) return rc;
+  char keep[sizeof(g_err)];
+  memcpy(keep, g_err, sizeof(keep));
+  return fail(rc, "%s: %s: %.400s", who, kernel, keep);
+}
+// f(nt, mt, S()) for the instantiation of a stored-model query's wavefront-per-trajectory kernel that a generic handle of these sizes runs
+// (value_wave_variant: nt state tiles, mt control tiles, storage type S).  The `if constexpr` is the build list of every such kernel.
+template <class F>
+static int with_wave_tiles(ilqr_batch* h, const char* kernel_name, F&& f) {
+  const WaveVariant w = value_wave_variant(h->nx, h->nu, h->dtype);
+  return with_int<1, 2>(w.nt, [&](auto nt) { return with_int<1, 2>(w.mt, [&](auto mt) { return with_bool(w.f32, [&](auto f32) {
+    if constexpr (decltype(mt)::value == 2 && decltype(f32)::value) {  // float storage: never with two control tiles (ilqr_create)
+      return fail(ILQR_ERR_UNSUPPORTED, "%s: no fp32 handle has more than %d controls", kernel_name, WM);
+    } else {
+      return f(nt, mt, std::conditional_t<decltype(f32)::value, float, double>());
+    }
+  }); }); });
+}
+
 // The value model of the stored policy (ilqr_get_value / ilqr_copy_value_to_device; value_wave.hpp, value_thread.hpp): picked by the
 // handle's layout and sizes alone -- no route bit, no stage timer.  The caller has materialised the records.  Vx [B][nk][nx], Vxx
 // [B][nk][nx * nx]: canonical double in device memory, either may be null.
@@ -406,16 +431,11 @@ static int launch_value(ilqr_batch* h, int t0, int nk, double* Vx, double* Vxx, 
           return 0;
         }))
       return rc;
-  } else if (int rc = with_int<1, 2>(w.nt, [&](auto nt) { return with_int<1, 2>(w.mt, [&](auto mt) { return with_bool(w.f32, [&](auto f32) {
-               constexpr int MT = decltype(mt)::value;
-               using S = std::conditional_t<decltype(f32)::value, float, double>;
-               if constexpr (MT == 2 && decltype(f32)::value) {  // float storage: never with two control tiles (ilqr_create)
-                 return fail(ILQR_ERR_UNSUPPORTED, "%s: no fp32 handle has more than %d controls", *name, WM);
-               } else {
-                 hipLaunchKernelGGL((k_value_w<decltype(nt)::value, MT, S>), dim3(h->B), dim3(64), 0, h->stream, view_of<S>(h), h->nx, h->nu, t0, nk, Vx, Vxx);
-                 return 0;
-               }
-             }); }); }))
+  } else if (int rc = with_wave_tiles(h, *name, [&](auto nt, auto mt, auto s) {
+               using S = decltype(s);
+               hipLaunchKernelGGL((k_value_w<decltype(nt)::value, decltype(mt)::value, S>), dim3(h->B), dim3(64), 0, h->stream, view_of<S>(h), h->nx, h->nu, t0, nk, Vx, Vxx);
+               return 0;
+             }))
     return rc;
   HIPCHK(hipGetLastError());
   return 0;
@@ -434,16 +454,11 @@ static int launch_covariance(ilqr_batch* h, const CovArgs& q, const char** name)
           return 0;
         }))
       return rc;
-  } else if (int rc = with_int<1, 2>(w.nt, [&](auto nt) { return with_int<1, 2>(w.mt, [&](auto mt) { return with_bool(w.f32, [&](auto f32) {
-               constexpr int MT = decltype(mt)::value;
-               using S = std::conditional_t<decltype(f32)::value, float, double>;
-               if constexpr (MT == 2 && decltype(f32)::value) {  // float storage: never with two control tiles (ilqr_create)
-                 return fail(ILQR_ERR_UNSUPPORTED, "%s: no fp32 handle has more than %d controls", *name, WM);
-               } else {
-                 hipLaunchKernelGGL((k_covariance_w<decltype(nt)::value, MT, S>), dim3(h->B), dim3(64), 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
-                 return 0;
-               }
-             }); }); }))
+  } else if (int rc = with_wave_tiles(h, *name, [&](auto nt, auto mt, auto s) {
+               using S = decltype(s);
+               hipLaunchKernelGGL((k_covariance_w<decltype(nt)::value, decltype(mt)::value, S>), dim3(h->B), dim3(64), 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
+               return 0;
+             }))
     return rc;
   HIPCHK(hipGetLastError());
   return 0;
@@ -455,7 +470,6 @@ static int launch_covariance(ilqr_batch* h, const CovArgs& q, const char** name)
 // (trajectory, 16 directions); tiled layout: one thread per (trajectory, direction), the direction by block.
 template <class Args, class Tiled, class Wave>
 static int launch_sensitivity(ilqr_batch* h, const Args& q, const char* kernel_name, Tiled&& tiled, Wave&& wave) {
-  const WaveVariant w = value_wave_variant(h->nx, h->nu, h->dtype);
   if (!h->aos) {
     const dim3 grid((unsigned)(h->Bp / 64) * (unsigned)q.nd), block(64);
     if (int rc = with_model(h, [&](auto& v, auto& m, auto&) {
@@ -463,16 +477,10 @@ static int launch_sensitivity(ilqr_batch* h, const Args& q, const char* kernel_n
           return 0;
         }))
       return rc;
-  } else if (int rc = with_int<1, 2>(w.nt, [&](auto nt) { return with_int<1, 2>(w.mt, [&](auto mt) { return with_bool(w.f32, [&](auto f32) {
-               constexpr int MT = decltype(mt)::value;
-               using S = std::conditional_t<decltype(f32)::value, float, double>;
-               if constexpr (MT == 2 && decltype(f32)::value) {  // float storage: never with two control tiles (ilqr_create)
-                 return fail(ILQR_ERR_UNSUPPORTED, "%s: no fp32 handle has more than %d controls", kernel_name, WM);
-               } else {
-                 wave(nt, mt, S(), dim3((unsigned)h->B * (unsigned)((q.nd + 15) / 16)), dim3(64));
-                 return 0;
-               }
-             }); }); }))
+  } else if (int rc = with_wave_tiles(h, kernel_name, [&](auto nt, auto mt, auto s) {
+               wave(nt, mt, s, dim3((unsigned)h->B * (unsigned)((q.nd + 15) / 16)), dim3(64));
+               return 0;
+             }))
     return rc;
   HIPCHK(hipGetLastError());
   return 0;
@@ -512,19 +520,15 @@ static int launch_lq_solve(ilqr_batch* h, const LqArgs& q, const char** name) {
           return 0;
         }))
       return rc;
-  } else if (int rc = with_int<1, 2>(w.nt, [&](auto nt) { return with_int<1, 2>(w.mt, [&](auto mt) { return with_bool(w.f32, [&](auto f32) {
+  } else if (int rc = with_wave_tiles(h, *name, [&](auto nt, auto mt, auto s) {
                constexpr int NT = decltype(nt)::value, MT = decltype(mt)::value;
-               using S = std::conditional_t<decltype(f32)::value, float, double>;
-               if constexpr (MT == 2 && decltype(f32)::value) {  // float storage: never with two control tiles (ilqr_create)
-                 return fail(ILQR_ERR_UNSUPPORTED, "%s: no fp32 handle has more than %d controls", *name, WM);
-               } else {
-                 const dim3 block(64), per_traj((unsigned)h->B), per_tile((unsigned)h->B * (unsigned)((q.nd + 15) / 16));
-                 hipLaunchKernelGGL((k_lq_gain_w<NT, MT, S>), per_traj, block, 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
-                 hipLaunchKernelGGL((k_lq_back_w<NT, MT, S>), per_tile, block, 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
-                 hipLaunchKernelGGL((k_lq_fwd_w<NT, MT, S>), per_tile, block, 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
-                 return 0;
-               }
-             }); }); }))
+               using S = decltype(s);
+               const dim3 block(64), per_traj((unsigned)h->B), per_tile((unsigned)h->B * (unsigned)((q.nd + 15) / 16));
+               hipLaunchKernelGGL((k_lq_gain_w<NT, MT, S>), per_traj, block, 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
+               hipLaunchKernelGGL((k_lq_back_w<NT, MT, S>), per_tile, block, 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
+               hipLaunchKernelGGL((k_lq_fwd_w<NT, MT, S>), per_tile, block, 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
+               return 0;
+             }))
     return rc;
   HIPCHK(hipGetLastError());
   return 0;
@@ -563,16 +567,11 @@ static int launch_estimator(ilqr_batch* h, const EstArgs& q, const char** name) 
   HIPCHK(hipGetLastError());
   if (!est_closed(q)) return 0;
   *name = estimator_loop_kernel_name(w);
-  if (int rc = with_int<1, 2>(w.nt, [&](auto nt) { return with_int<1, 2>(w.mt, [&](auto mt) { return with_bool(w.f32, [&](auto f32) {
-        constexpr int MT = decltype(mt)::value;
-        using S = std::conditional_t<decltype(f32)::value, float, double>;
-        if constexpr (MT == 2 && decltype(f32)::value) {  // float storage: never with two control tiles (ilqr_create)
-          return fail(ILQR_ERR_UNSUPPORTED, "%s: no fp32 handle has more than %d controls", *name, WM);
-        } else {
-          hipLaunchKernelGGL((k_est_loop_w<decltype(nt)::value, MT, S>), dim3(h->B), dim3(64), 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
-          return 0;
-        }
-      }); }); }))
+  if (int rc = with_wave_tiles(h, *name, [&](auto nt, auto mt, auto s) {
+        using S = decltype(s);
+        hipLaunchKernelGGL((k_est_loop_w<decltype(nt)::value, decltype(mt)::value, S>), dim3(h->B), dim3(64), 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
+        return 0;
+      }))
     return rc;
   HIPCHK(hipGetLastError());
   return 0;
@@ -593,20 +592,15 @@ static int launch_risk(ilqr_batch* h, const RiskArgs& q, const char** name) {
           return 0;
         }))
       return rc;
-  } else if (int rc = with_int<1, 2>(w.nt, [&](auto nt) { return with_int<1, 2>(w.mt, [&](auto mt) { return with_int<1, 2>(wt, [&](auto wtc) {
-               return with_bool(w.f32, [&](auto f32) {
-                 constexpr int NT = decltype(nt)::value, MT = decltype(mt)::value, WT = decltype(wtc)::value;
-                 using S = std::conditional_t<decltype(f32)::value, float, double>;
-                 if constexpr (WT > NT) {  // (nw <= nx: the caller has checked)
-                   return fail(ILQR_ERR_INVALID, "%s: nw %d beyond nx %d", *name, q.nw, h->nx);
-                 } else if constexpr (MT == 2 && decltype(f32)::value) {  // float storage: never with two control tiles (ilqr_create)
-                   return fail(ILQR_ERR_UNSUPPORTED, "%s: no fp32 handle has more than %d controls", *name, WM);
-                 } else {
-                   hipLaunchKernelGGL((k_risk_w<NT, MT, WT, S>), dim3(h->B), dim3(64), 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
-                   return 0;
-                 }
-               });
-             }); }); }))
+  } else if (wt > w.nt) {  // (nw <= nx: the caller has checked)
+    return fail(ILQR_ERR_INVALID, "%s: nw %d beyond nx %d", *name, q.nw, h->nx);
+  } else if (int rc = with_wave_tiles(h, *name, [&](auto nt, auto mt, auto s) { return with_int<1, 2>(wt, [&](auto wtc) {
+               constexpr int NT = decltype(nt)::value, MT = decltype(mt)::value, WT = decltype(wtc)::value;
+               using S = decltype(s);
+               if constexpr (WT <= NT)  // (more noise tiles than state tiles: refused above, never built)
+                 hipLaunchKernelGGL((k_risk_w<NT, MT, WT, S>), dim3(h->B), dim3(64), 0, h->stream, view_of<S>(h), h->nx, h->nu, q);
+               return 0;
+             }); }))
     return rc;
   HIPCHK(hipGetLastError());
   return 0;

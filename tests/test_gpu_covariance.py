@@ -320,3 +320,20 @@ def test_the_handle_is_left_alone(which):
         assert np.array_equal(a, b)
     g.close()
     twin.close()
+
+
+# ---- every request through the staging buffer ---------------------------------------------------
+from tests import getter_vs_device as gd  # noqa: E402
+
+
+@pytest.mark.parametrize("case", gd.CASES)
+@pytest.mark.parametrize("which", ["generic", "tiled"])
+def test_getter_equals_the_device_form_request_by_request(which, case):
+    """ilqr_get_covariance against ilqr_copy_covariance_to_device, bit for bit: every pointer; expected_cost alone with Sigma0 and W null;
+    that, every pointer, that again on one handle."""
+
+    def args(g):
+        rng, n, m = np.random.default_rng(3), g.nx, g.nu
+        return [gd.Arg("Sigma0", "in", gd.spd(rng, n)), gd.Arg("W", "in", gd.spd(rng, n, 0.01)), gd.Arg("Sigma", "out", (gd.B * gd.NK * n * n,)),
+                gd.Arg("Su", "out", (gd.B * gd.NK * m * m,)), gd.Arg("expected_cost", "out", (gd.B,))]
+    gd.check(lambda: gd.handle(which), case, "ilqr_get_covariance", "ilqr_copy_covariance_to_device", (gd.T0, gd.NK), args)

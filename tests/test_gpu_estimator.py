@@ -477,3 +477,23 @@ def test_the_handle_is_left_alone(which):
         assert np.array_equal(a, b)
     g.close()
     twin.close()
+
+
+# ---- every request through the staging buffer ---------------------------------------------------
+from tests import getter_vs_device as gd  # noqa: E402
+
+
+@pytest.mark.parametrize("case", gd.CASES)
+@pytest.mark.parametrize("which", ["generic", "tiled"])
+def test_getter_equals_the_device_form_request_by_request(which, case):
+    """ilqr_get_estimator against ilqr_copy_estimator_to_device, bit for bit: every pointer; H and V in (required), P0 and W null,
+    expected_cost and info out (info alone is refused); that, every pointer, that again on one handle."""
+    ny = 2
+
+    def args(g):
+        rng, n, m, nn = np.random.default_rng(3), g.nx, g.nu, gd.B * g.nx * g.nx
+        return [gd.Arg("H", "req", rng.normal(size=(gd.B, ny, n))), gd.Arg("P0", "in", gd.spd(rng, n)), gd.Arg("W", "in", gd.spd(rng, n, 0.01)),
+                gd.Arg("V", "req", gd.spd(rng, ny, 0.1)), gd.Arg("Pp", "out", (nn * gd.NK,)), gd.Arg("Pf", "out", (nn * gd.NK,)),
+                gd.Arg("L", "out", (gd.B * gd.NK * n * ny,)), gd.Arg("Sigma", "out", (nn * gd.NK,)), gd.Arg("Su", "out", (gd.B * gd.NK * m * m,)),
+                gd.Arg("expected_cost", "out", (gd.B,)), gd.Arg("info", "info", (gd.B,))]
+    gd.check(lambda: gd.handle(which), case, "ilqr_get_estimator", "ilqr_copy_estimator_to_device", (gd.T0, gd.NK, ny), args)

@@ -574,3 +574,21 @@ def test_facade_caller_gets_the_python_answer(tmp_path):
     for got, ref, what in zip(parts[3:], want[:3], ("dxs", "dus", "dlam")):
         close(got.reshape(ref.shape), ref, what + " of the C++ caller", bound=1e-12)
     g.close()
+
+
+# ---- every request through the staging buffer ---------------------------------------------------
+from tests import getter_vs_device as gd  # noqa: E402
+
+
+@pytest.mark.parametrize("case", gd.CASES)
+@pytest.mark.parametrize("which", ["generic", "tiled"])
+def test_getter_equals_the_device_form_request_by_request(which, case):
+    """ilqr_solve_lq against ilqr_solve_lq_on_device, bit for bit: every pointer; gu in, dlam and info out (a call without inputs is
+    refused, and so is info alone); that, every pointer, that again on one handle."""
+
+    def args(g):
+        rng, per_x, per_u = np.random.default_rng(3), gd.B * gd.ND * g.nx, gd.B * gd.ND * g.nu
+        return [gd.Arg("dx0", "in", rng.normal(size=per_x)), gd.Arg("gx", "in", rng.normal(size=per_x * (gd.T + 1))), gd.Arg("gu", "in", rng.normal(size=per_u * gd.T)),
+                gd.Arg("dxs", "out", (per_x * (gd.T + 1),)), gd.Arg("dus", "out", (per_u * gd.T,)), gd.Arg("dlam", "out", (per_x * (gd.T + 1),)),
+                gd.Arg("info", "info", (gd.B,))]
+    gd.check(lambda: gd.handle(which), case, "ilqr_solve_lq", "ilqr_solve_lq_on_device", (gd.ND, 0, 0.0), args, needs_input=True)

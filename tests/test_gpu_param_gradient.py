@@ -296,3 +296,24 @@ def test_refusals_on_the_device(chain_lib):
     with pytest.raises(capi.ILQRError, match=r"error -5: .*ILQR_MODEL_USER"):
         g.param_gradient(dxs=z)
     g.close()
+
+
+# ---- every request through the staging buffer ---------------------------------------------------
+from tests import getter_vs_device as gd  # noqa: E402
+
+
+@pytest.mark.parametrize("case", gd.CASES)
+def test_getter_equals_the_device_form_request_by_request(chain_lib, case):
+    """ilqr_get_param_gradient against ilqr_param_gradient_on_device, bit for bit, on the build whose twin has NTP: every pointer; dlam in
+    and lam out alone (a call without inputs is refused); that, every pointer, that again on one handle."""
+
+    def make():
+        g = handle(chain_lib, gd.B, gd.T, 2.0)
+        nominal(g, gd.B, gd.T, 3, draw_params(gd.B, 41))
+        return g
+
+    def args(g):
+        rng, per_x, per_u = np.random.default_rng(3), gd.B * gd.ND * NX, gd.B * gd.ND * NU
+        return [gd.Arg("dxs", "in", rng.normal(size=per_x * (gd.T + 1))), gd.Arg("dus", "in", rng.normal(size=per_u * gd.T)),
+                gd.Arg("dlam", "in", rng.normal(size=per_x * (gd.T + 1))), gd.Arg("gp", "out", (gd.B * gd.ND * NTP,)), gd.Arg("lam", "out", (gd.B * (gd.T + 1) * NX,))]
+    gd.check(make, case, "ilqr_get_param_gradient", "ilqr_param_gradient_on_device", (gd.ND, 0, 0.0), args, needs_input=True)

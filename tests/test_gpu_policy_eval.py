@@ -397,3 +397,21 @@ def test_refusals(libs):
     with pytest.raises(capi.ILQRError, match="-5"):
         hm.evaluate_policy(x5)
     hm.close()
+
+
+# ---- every request through the staging buffer ---------------------------------------------------
+from tests import getter_vs_device as gd  # noqa: E402
+
+
+@pytest.mark.parametrize("case", gd.CASES)
+@pytest.mark.parametrize("which", ["generic", "tiled"])
+def test_getter_equals_the_device_form_request_by_request(which, case):
+    """ilqr_evaluate_policy against ilqr_evaluate_policy_on_device, bit for bit: every pointer; x in (required), u_first alone out; that,
+    every pointer, that again on one handle."""
+    n_samples = 2
+
+    def args(g):
+        R = gd.B * n_samples
+        return [gd.Arg("x", "req", 0.3 * np.random.default_rng(3).normal(size=(R, g.nx))), gd.Arg("cost", "out", (R,)), gd.Arg("x_end", "out", (R * g.nx,)),
+                gd.Arg("u_first", "out", (R * g.nu,))]
+    gd.check(lambda: gd.handle(which), case, "ilqr_evaluate_policy", "ilqr_evaluate_policy_on_device", (gd.T0, gd.NK, n_samples, 0), args)

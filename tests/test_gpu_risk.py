@@ -481,3 +481,22 @@ def test_the_handle_is_left_alone(which):
         assert np.array_equal(a, b)
     g.close()
     twin.close()
+
+
+# ---- 10. every request through the staging buffer -----------------------------------------------
+from tests import getter_vs_device as gd  # noqa: E402
+
+
+@pytest.mark.parametrize("case", gd.CASES)
+@pytest.mark.parametrize("which", ["generic", "tiled"])
+def test_getter_equals_the_device_form_request_by_request(which, case):
+    """ilqr_get_risk_sensitive against ilqr_copy_risk_sensitive_to_device, bit for bit: every pointer; C in (required), risk_cost and info
+    out (info alone is refused); that, every pointer, that again on one handle."""
+    nw = 2
+
+    def args(g):
+        n, m = g.nx, g.nu
+        return [gd.Arg("C", "req", 0.05 * np.random.default_rng(3).normal(size=(gd.B, n, nw))), gd.Arg("K", "out", (gd.B * gd.T * m * n,)),
+                gd.Arg("k", "out", (gd.B * gd.T * m,)), gd.Arg("Vx", "out", (gd.B * (gd.T + 1) * n,)), gd.Arg("Vxx", "out", (gd.B * (gd.T + 1) * n * n,)),
+                gd.Arg("risk_cost", "out", (gd.B,)), gd.Arg("info", "info", (gd.B,))]
+    gd.check(lambda: gd.handle(which), case, "ilqr_get_risk_sensitive", "ilqr_copy_risk_sensitive_to_device", (nw, 0.1, 0, 1.0), args)

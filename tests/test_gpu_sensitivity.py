@@ -606,3 +606,23 @@ def test_facade_sensitivity_members(tmp_path, which):
                            "-Wl,-rpath," + os.path.join(ROOT, "ilqr_amd", "lib"), "-Wl,-rpath,/opt/rocm/lib"])
     r = subprocess.run([exe], capture_output=True, text=True, cwd=tmp_path, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
+
+
+# ---- every request through the staging buffer ---------------------------------------------------
+from tests import getter_vs_device as gd  # noqa: E402
+
+
+@pytest.mark.parametrize("case", gd.CASES)
+@pytest.mark.parametrize("call", ["tangent", "adjoint"])
+@pytest.mark.parametrize("which", ["generic", "tiled"])
+def test_getter_equals_the_device_form_request_by_request(which, call, case):
+    """ilqr_get_tangent / ilqr_get_adjoint against their device forms, bit for bit: every pointer; the last input and the last output
+    alone (a call without inputs is refused); that, every pointer, that again on one handle."""
+
+    def args(g):
+        rng, per_x, per_u = np.random.default_rng(3), gd.B * gd.ND * g.nx, gd.B * gd.ND * g.nu
+        x_one, u_all, x_win, u_win = per_x, per_u * gd.T, per_x * gd.NK, per_u * (min(gd.T0 + gd.NK, gd.T) - gd.T0)
+        if call == "tangent":
+            return [gd.Arg("dx0", "in", rng.normal(size=x_one)), gd.Arg("dv", "in", rng.normal(size=u_all)), gd.Arg("dxs", "out", (x_win,)), gd.Arg("dus", "out", (u_win,))]
+        return [gd.Arg("gx", "in", rng.normal(size=x_win)), gd.Arg("gu", "in", rng.normal(size=u_win)), gd.Arg("g_x0", "out", (x_one,)), gd.Arg("g_v", "out", (u_all,))]
+    gd.check(lambda: gd.handle(which), case, "ilqr_get_%s" % call, "ilqr_copy_%s_to_device" % call, (gd.T0, gd.NK, gd.ND), args, needs_input=True)

@@ -334,3 +334,15 @@ def test_user_twin(chain_lib, dtype):
     got = g.value()
     against_reference(got, g.derivatives(), *g.gains())
     g.close()
+
+
+# ---- 8. every request through the staging buffer -----------------------------------------------
+from tests import getter_vs_device as gd  # noqa: E402
+
+
+@pytest.mark.parametrize("case", gd.CASES)
+@pytest.mark.parametrize("which", ["generic", "tiled"])
+def test_getter_equals_the_device_form_request_by_request(which, case):
+    """ilqr_get_value against ilqr_copy_value_to_device, bit for bit: both outputs; Vxx alone; Vxx alone, both, Vxx alone on one handle."""
+    args = lambda g: [gd.Arg("Vx", "out", (gd.B * gd.NK * g.nx,)), gd.Arg("Vxx", "out", (gd.B * gd.NK * g.nx * g.nx,))]
+    gd.check(lambda: gd.handle(which), case, "ilqr_get_value", "ilqr_copy_value_to_device", (gd.T0, gd.NK), args)
