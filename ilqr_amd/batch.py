@@ -267,8 +267,34 @@ class BatchILQR:
         return p
 
     def clear_trajectory_params(self):
-        """Every trajectory back to the handle-wide parameters of the constructor."""
+        """Every trajectory back to the handle-wide parameters of the constructor (per-trajectory rows and per-knot rows alike)."""
         self._check(self.lib.ilqr_clear_trajectory_params(self.h))
+
+    def set_knot_params(self, p=None, ptr=None, n_knots=None, k0=0):
+        """Per-knot model parameters: the handle takes the window of T + 1 rows starting at row k0 of a reference [B][n_knots][NTP] -- row
+        t of the handle is reference row min(k0 + t, n_knots - 1) -- and evaluates knot t of trajectory b under row (b, t) in every later
+        rollout, sweep and mpc_step.  p: numpy [B][n_knots][NTP]; ptr: a raw device pointer to such an array of float64 on the handle's
+        device (torch.Tensor.data_ptr()), with n_knots given.  Exactly one of them.  Enqueued on the handle's stream (the stream rule
+        above); the stored cost is not re-evaluated -- warm-start or mpc_step next.  set_trajectory_params switches back to one row per
+        trajectory, clear_trajectory_params to none."""
+        if (p is None) == (ptr is None):
+            raise ValueError("set_knot_params: exactly one of p and ptr")
+        n = self.lib.ilqr_trajectory_params_count()
+        if p is not None:
+            p = _c(p)
+            if p.ndim != 3 or p.shape[0] != self.B or (n_knots is not None and int(n_knots) != p.shape[1]):
+                raise ValueError("set_knot_params: p must be [B][n_knots][NTP], got %s" % (p.shape,))
+            n_knots, n = p.shape[1], p.shape[2]
+        elif n_knots is None:
+            raise ValueError("set_knot_params: ptr needs n_knots")
+        self._check(self.lib.ilqr_set_knot_params(self.h, _p(p), ptr, int(n), int(n_knots), int(k0)))
+
+    def knot_params(self):
+        """The handle's window of per-knot rows as the kernels see them, [B][T+1][NTP] (synchronises)."""
+        n = self.lib.ilqr_trajectory_params_count()
+        p = np.zeros((self.B, self.T + 1, max(n, 1)))
+        self._check(self.lib.ilqr_get_knot_params(self.h, _p(p), int(n)))
+        return p
 
     def param_gradient(self, dxs=None, dus=None, dlam=None, eps_p=0.0, want_lam=False):
         """dL/dp, the gradient of the caller's loss in the rows of set_trajectory_params (include/ilqr_amd.h, ilqr_get_param_gradient), from

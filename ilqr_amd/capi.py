@@ -91,6 +91,8 @@ SYMBOLS = {
     "ilqr_set_trajectory_params": (C.c_int, [_H, _dp, C.c_void_p, C.c_int]),
     "ilqr_get_trajectory_params": (C.c_int, [_H, _dp, C.c_int]),
     "ilqr_clear_trajectory_params": (C.c_int, [_H]),
+    "ilqr_set_knot_params": (C.c_int, [_H, _dp, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "ilqr_get_knot_params": (C.c_int, [_H, _dp, C.c_int]),
     "ilqr_get_param_gradient": (C.c_int, [_H, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     "ilqr_param_gradient_on_device": (C.c_int, [_H, C.c_int, C.c_int, C.c_double] + [C.c_void_p] * 5),
     "ilqr_compute_derivatives": (C.c_int, [_H]),

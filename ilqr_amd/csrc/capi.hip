@@ -97,6 +97,7 @@ void ilqr_destroy(ilqr_batch* h) {
   if (h->lq_scratch) (void)hipFree(h->lq_scratch);
   if (h->est_scratch) (void)hipFree(h->est_scratch);
   if (h->pg_scratch) (void)hipFree(h->pg_scratch);
+  if (h->knot_stage) (void)hipFree(h->knot_stage);
   if (h->d_perm) (void)hipFree(h->d_perm);
   if (h->perm_scratch) (void)hipFree(h->perm_scratch);
   (void)timers_drain(h);  // (every event back into the pool, each once)
@@ -1317,7 +1318,7 @@ int ilqr_set_trajectory_params(ilqr_batch* h, const double* p, const void* p_dev
   if (!h->traj_params)
     if (int rc = dev_alloc(h, &h->traj_params, elems)) return rc;
   HIPCHK(hipMemcpyAsync(h->traj_params, p ? (const void*)p : p_device, elems * sizeof(double), p ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
-  h->plan.traj_params = true;
+  h->plan.traj_params = ModelRows::per_trajectory;  // (out of knot mode, if the handle was in it: its window stays allocated)
   return 0;
 }
 
@@ -1326,7 +1327,10 @@ int ilqr_get_trajectory_params(ilqr_batch* h, double* p, int n) {
   if (int rc = check_trajectory_params(h, "ilqr_get_trajectory_params")) return rc;
   REQUIRE(p != nullptr, "ilqr_get_trajectory_params: null array");
   REQUIRE(n == kUserNTP, "ilqr_get_trajectory_params: n = %d, this build's user model takes NTP = %d parameters per trajectory", n, kUserNTP);
-  if (!h->plan.traj_params) return fail(ILQR_ERR_STATE, "ilqr_get_trajectory_params: no per-trajectory parameters are set (every trajectory uses ilqr_create's)");
+  if (h->plan.traj_params == ModelRows::per_knot)
+    return fail(ILQR_ERR_STATE, "ilqr_get_trajectory_params: per-knot rows are set (ilqr_set_knot_params): ilqr_get_knot_params returns them");
+  if (h->plan.traj_params != ModelRows::per_trajectory)
+    return fail(ILQR_ERR_STATE, "ilqr_get_trajectory_params: no per-trajectory parameters are set (every trajectory uses ilqr_create's)");
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipMemcpyAsync(p, h->traj_params, (size_t)h->B * kUserNTP * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -1336,7 +1340,47 @@ int ilqr_get_trajectory_params(ilqr_batch* h, double* p, int n) {
 int ilqr_clear_trajectory_params(ilqr_batch* h) {
   if (!h) return fail(ILQR_ERR_INVALID, "null handle");
   if (int rc = check_trajectory_params(h, "ilqr_clear_trajectory_params")) return rc;
-  h->plan.traj_params = false;  // (the rows stay allocated for the next set)
+  h->plan.traj_params = ModelRows::none;  // (either mode; the rows stay allocated for the next set)
+  return 0;
+}
+
+// ---- per-knot model parameters (additive under ABI 6) ---------------------------
+int ilqr_set_knot_params(ilqr_batch* h, const double* p, const void* p_device, int n, int n_knots, int k0) {
+  REQUIRE((p != nullptr) != (p_device != nullptr), "ilqr_set_knot_params: exactly one of p (host) and p_device");
+  REQUIRE(n_knots >= 1, "ilqr_set_knot_params: n_knots %d must be >= 1", n_knots);
+  REQUIRE(k0 >= 0 && k0 < n_knots, "ilqr_set_knot_params: k0 %d outside [0, n_knots = %d)", k0, n_knots);
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  if (int rc = check_trajectory_params(h, "ilqr_set_knot_params")) return rc;
+  REQUIRE(n == kUserNTP, "ilqr_set_knot_params: n = %d, this build's user model takes NTP = %d parameters per knot", n, kUserNTP);
+  const long long window = (long long)h->B * (h->T + 1) * kUserNTP;
+  REQUIRE(window <= (long long)INT_MAX, "ilqr_set_knot_params: B * (T + 1) * NTP = %lld elements do not fit an int", window);
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->knot_params)
+    if (int rc = dev_alloc(h, &h->knot_params, (size_t)window)) return rc;
+  const double* src = (const double*)p_device;
+  if (p) {  // the whole reference up into the handle's scratch, then the same gather
+    const size_t elems = (size_t)h->B * n_knots * kUserNTP;
+    if (int rc = ensure_knot_stage(h, elems)) return rc;
+    HIPCHK(hipMemcpyAsync(h->knot_stage, p, elems * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    src = h->knot_stage;
+  }
+  hipLaunchKernelGGL(k_gather_knot_params, dim3((unsigned)((window + 255) / 256)), dim3(256), 0, h->stream, h->knot_params, src, h->B, h->T + 1,
+                     kUserNTP, n_knots, k0);
+  HIPCHK(hipGetLastError());
+  h->plan.traj_params = ModelRows::per_knot;
+  return 0;
+}
+
+int ilqr_get_knot_params(ilqr_batch* h, double* p, int n) {
+  if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+  if (int rc = check_trajectory_params(h, "ilqr_get_knot_params")) return rc;
+  REQUIRE(p != nullptr, "ilqr_get_knot_params: null array");
+  REQUIRE(n == kUserNTP, "ilqr_get_knot_params: n = %d, this build's user model takes NTP = %d parameters per knot", n, kUserNTP);
+  if (h->plan.traj_params != ModelRows::per_knot)
+    return fail(ILQR_ERR_STATE, "ilqr_get_knot_params: no per-knot rows are set (ilqr_set_knot_params)");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipMemcpyAsync(p, h->knot_params, (size_t)h->B * (h->T + 1) * kUserNTP * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }
 
@@ -1355,7 +1399,9 @@ static int prepare_param_gradient(ilqr_batch* h, int n_dirs, int flags, double e
   const long long widest = (long long)h->B * (h->T + 1) * n_dirs * std::max(std::max(h->nx, h->nu), kUserNTP);
   REQUIRE(widest <= (long long)INT_MAX, "%s: B * (T + 1) * n_dirs * max(nx, nu, NTP) = %lld elements do not fit an int", who, widest);
   if (!h->initialised) return fail(ILQR_ERR_STATE, "%s before ilqr_init_traj/ilqr_set_trajectory: no trajectory is stored", who);
-  if (!h->plan.traj_params)
+  if (h->plan.traj_params == ModelRows::per_knot)  // (never the per-trajectory buffer of an earlier mode)
+    return fail(ILQR_ERR_UNSUPPORTED, "%s: per-knot rows are set (ilqr_set_knot_params); the gradient is defined for per-trajectory rows only", who);
+  if (h->plan.traj_params != ModelRows::per_trajectory)
     return fail(ILQR_ERR_STATE, "%s: no per-trajectory parameters are set (ilqr_create's user_params have no mapping onto the NTP fields)", who);
   HIPCHK(hipSetDevice(h->device));
   if (int rc = flush_commit(h)) return rc;

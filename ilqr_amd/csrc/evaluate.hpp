@@ -74,8 +74,9 @@ __global__ __launch_bounds__(64) void k_evaluate_t(BatchViewT<typename M::real> 
 }
 
 // trajectory-contiguous layout: the LQ twins, user twins on the generic kernels; M as k_rollout_g takes it (the float twin on an fp32
-// handle).  PT: every sample of trajectory b evaluates the model with row b of the handle's per-trajectory parameters.
-template <class M, bool PT = false>
+// handle).  PT: every sample of trajectory b evaluates the model with row b of the handle's per-trajectory parameters.  PK: with row
+// t0 + i of trajectory b's per-knot window at the window's knot i, row T for final_cost (KnotRows, as k_rollout_g walks them).
+template <class M, int PT = ROWS_NONE>
 __global__ __launch_bounds__(64) void k_evaluate_g(BatchViewT<typename M::real> v, model_arg_t<M, PT> model, EvalArgs e) {
   using real = typename M::real;
   constexpr int NX = M::NX, NU = M::NU;
@@ -84,7 +85,7 @@ __global__ __launch_bounds__(64) void k_evaluate_g(BatchViewT<typename M::real> 
   if (r >= (size_t)v.B * e.S) return;
   const int b = (int)(r / e.S);
   const real dt = (real)v.dt;
-  if constexpr (PT) {
+  if constexpr (PT == PT_ROWS) {
     double p[M::NTP];
 #pragma unroll
     for (int i = 0; i < M::NTP; i++) p[i] = model.traj_params[(size_t)b * M::NTP + i];
@@ -98,7 +99,9 @@ __global__ __launch_bounds__(64) void k_evaluate_g(BatchViewT<typename M::real> 
   const real* usb = v.us + (size_t)b * T * nu;
   const real* Kb = v.Kfb + (size_t)b * T * nu * nx;
   const int t1 = e.t0 + e.n;
+  KnotRows<M, PT> rows(model, b, T, e.t0);
   for (int t = e.t0; t < t1; t++) {
+    rows.next(model);
     real u[NU];
 #pragma unroll
     for (int j = 0; j < NU; j++) u[j] = (j < nu) ? usb[(size_t)t * nu + j] : (real)0;
@@ -132,7 +135,10 @@ __global__ __launch_bounds__(64) void k_evaluate_g(BatchViewT<typename M::real> 
 #pragma unroll
     for (int i = 0; i < NX; i++) x[i] = x1[i];
   }
-  if (t1 == T) total += model.final_cost(x);  // :335
+  if (t1 == T) {
+    rows.last(model);
+    total += model.final_cost(x);  // :335
+  }
   if (e.cost) e.cost[r] = total;
   if (e.x_end) {
 #pragma unroll

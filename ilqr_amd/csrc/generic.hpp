@@ -336,12 +336,59 @@ struct GenericModelOf : U {
 // kernels that touch the model take the handle's model with the handle's rows behind it, canonical double [B][NTP]; a kernel overwrites
 // ITS copy of the model (this by-value argument) from the row of its trajectory before the first evaluation.  The instantiations without
 // PT take the model itself, as they always did: not one argument, not one instruction of theirs changes.
+// Per-knot rows (ilqr_set_knot_params): the PK instantiations take the same argument with the handle's window behind it, canonical double
+// [B][T+1][NTP] (T is the view's), and set their copy from row (b, t) before anything is evaluated at knot t -- cost and dynamics of knot
+// t < T under row t, final_cost and the t = T cases of the record under row T.  The no-rows and PT instantiations keep their arguments and
+// their instructions: every PK branch is an `if constexpr` of its own.
 template <class M>
 struct PerTrajectory : M {
-  const double* traj_params = nullptr;
+  const double* traj_params = nullptr;  // PT: [B][NTP]; PK: [B][T+1][NTP]
 };
-template <class M, bool PT>
-using model_arg_t = std::conditional_t<PT, PerTrajectory<M>, M>;
+constexpr int ROWS_NONE = 0, PT_ROWS = 1, PK_ROWS = 2;  // the rows a kernel's model argument carries: none, one per trajectory, one per knot
+template <class M, int PT>
+using model_arg_t = std::conditional_t<PT != ROWS_NONE, PerTrajectory<M>, M>;
+
+// ilqr_set_knot_params' window: row t of the handle is row min(k0 + t, n_knots - 1) of the caller's reference [B][n_knots][ntp] (the
+// horizon's tail holds the last row of a reference that ends).  One thread per destination element: the stores are coalesced, the loads
+// are runs of ntp doubles.
+__global__ __launch_bounds__(256) void k_gather_knot_params(double* __restrict__ dst, const double* __restrict__ src, int B, int T1, int ntp,
+                                                            int n_knots, int k0) {
+  const int e = blockIdx.x * 256 + threadIdx.x;  // (B * T1 * ntp fits an int: the caller has checked)
+  if (e >= B * T1 * ntp) return;
+  const int i = e % ntp, bt = e / ntp, t = bt % T1, b = bt / T1;
+  const int row = (t < n_knots - k0) ? k0 + t : n_knots - 1;  // min(k0 + t, n_knots - 1) without the sum's overflow
+  dst[e] = src[((size_t)b * n_knots + row) * ntp + i];
+}
+
+// The per-knot rows of one thread's trajectory as a serial rollout walks them (k_rollout_g, k_evaluate_g): next() applies the row of the
+// knot the loop is entering and issues the load of the one behind it; last() applies the row already in flight (row T after the last
+// knot: final_cost's).  Empty, and no instruction, unless PT == PK_ROWS.
+template <class M, int PT>
+struct KnotRows {
+  __device__ __forceinline__ KnotRows(const M&, int, int, int) {}
+  __device__ __forceinline__ void next(M&) {}
+  __device__ __forceinline__ void last(M&) {}
+};
+template <class M>
+struct KnotRows<M, PK_ROWS> {
+  const double* row;  // the row in flight
+  double p[M::NTP];
+  __device__ __forceinline__ void load() {
+#pragma unroll
+    for (int i = 0; i < M::NTP; i++) p[i] = row[i];
+  }
+  // t0: the knot the walk starts at (its row goes first)
+  __device__ __forceinline__ KnotRows(const PerTrajectory<M>& model, int b, int T, int t0)
+      : row(model.traj_params + ((size_t)b * (T + 1) + t0) * M::NTP) {
+    load();
+  }
+  __device__ __forceinline__ void next(PerTrajectory<M>& model) {
+    model.set_trajectory_params(p);  // (a float twin casts: the float-rounded values on an fp32 handle)
+    row += M::NTP;  // in bounds: the walk enters knots t < T only, the window has T + 1 rows
+    load();
+  }
+  __device__ __forceinline__ void last(PerTrajectory<M>& model) { model.set_trajectory_params(p); }
+};
 
 enum { RG_INIT = 0, RG_SEARCH = 1, RG_COMMIT = 2 };
 constexpr int kSearchTraj = 64 / NALPHA;  // trajectories per wavefront in RG_SEARCH (5)
@@ -352,7 +399,9 @@ constexpr int kSearchTraj = 64 / NALPHA;  // trajectories per wavefront in RG_SE
 // fp32 handles (M::real = float: LqModelT<float>, GenericModelOf<UserModelT<float>>): float knots and registers, the cost summed in double.
 // PT: the model's parameters are this lane's trajectory's (RG_SEARCH: the 11 lanes of a trajectory read the same row; RG_INIT / RG_COMMIT:
 // lanes read consecutive rows).  The model's parameter fields then live in vector registers instead of scalar ones.
-template <class M, int MODE, bool PT = false>
+// PK: row (b, t) is loaded and applied at the top of knot t, row T before final_cost.  The loop is a serial latency chain, so the load of
+// row t + 1 is issued before the model evaluation of knot t (the rows are in bounds up to T: no clamp) and waits under it.
+template <class M, int MODE, int PT = ROWS_NONE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT ? ILQR_ROLLOUT_G_PT_WAVES : 0, PT ? ILQR_ROLLOUT_G_PT_WAVES : 0)))
 void k_rollout_g(BatchViewT<typename M::real> v, model_arg_t<M, PT> model, AlphaSet alphas, double* __restrict__ cost_out,
                  const int* __restrict__ commit_idx, int mode, int write_cost, int fixes) {
@@ -380,12 +429,13 @@ void k_rollout_g(BatchViewT<typename M::real> v, model_arg_t<M, PT> model, Alpha
   for (int q = 0; q < NALPHA; q++)
     if (a == q) alpha = (real)alphas.a[q];
   const real dt = (real)v.dt;
-  if constexpr (PT) {  // row b: the generic path never re-packs trajectories, a trajectory's slot is its index
+  if constexpr (PT == PT_ROWS) {  // row b: the generic path never re-packs trajectories, a trajectory's slot is its index
     double p[M::NTP];
 #pragma unroll
     for (int i = 0; i < M::NTP; i++) p[i] = model.traj_params[(size_t)b * M::NTP + i];
     model.set_trajectory_params(p);  // (a float twin casts: the float-rounded values on an fp32 handle)
   }
+  KnotRows<M, PT> rows(model, b, T, 0);
 
   real x[NX];
 #pragma unroll
@@ -396,6 +446,7 @@ void k_rollout_g(BatchViewT<typename M::real> v, model_arg_t<M, PT> model, Alpha
   const real* kb = v.kff + (size_t)b * T * nu;
   const real* Kb = v.Kfb + (size_t)b * T * nu * nx;
   for (int t = 0; t < T; t++) {
+    rows.next(model);
     real u[NU];
 #pragma unroll
     for (int j = 0; j < NU; j++) u[j] = (j < nu) ? usb[(size_t)t * nu + j] : (real)0;
@@ -440,6 +491,7 @@ void k_rollout_g(BatchViewT<typename M::real> v, model_arg_t<M, PT> model, Alpha
     for (int i = 0; i < NX; i++)
       if (i < nx) xsb[(size_t)T * nx + i] = x[i];
   }
+  rows.last(model);
   total += model.final_cost(x);  // :335
   if (MODE == RG_SEARCH)
     cost_out[(size_t)a * v.Bp + b] = total;
@@ -870,7 +922,7 @@ __global__ __launch_bounds__(256) void k_commit_lq(BatchView v, int nx, int nu, 
 //   cxu      (c(px,pu) - c(mx,pu) - c(px,mu) + c(mx,mu)) / 4eps^2               derivatives.cpp:114-144
 // including the t = T special cases (fx[T] = fu[T] = 0, cx/cxx from final_cost, cu[T] = 0, cuu[T]
 // from cost(x_T, 0), the cxu[T] formula the reference itself marks wrong).
-template <class M, class S = double, bool PT = false>
+template <class M, class S = double, int PT = ROWS_NONE>
 // t_only >= 0: one block per trajectory, knot t_only alone (the last knot behind k_derivatives_lq, which sweeps the knots t < T).
 #ifndef ILQR_FD_G_WAVES_SMALL
 // Wavefronts per SIMD of k_derivatives_g: two at NX > 16 (186 registers for the LQ model's 32-vectors); THREE for a model of NX <= 16 (168
@@ -884,6 +936,8 @@ template <class M, class S = double, bool PT = false>
 // address space (scalar loads, as the LQ model's matrices are) and the parameters stay in scalar registers, where the 880 cost evaluations
 // per knot find them today.  fp32 handles: the float-rounded values (the float rollouts' twin casts the same row), rounded by the vector
 // unit and handed back to scalar registers with v_readfirstlane.
+// PK: the same with row (b, t) of the handle's per-knot window -- (b, t) comes from blockIdx.x too, so nothing else differs: one scalar
+// load per wavefront in either mode.  Knot T's wavefront reads row T: final_cost and the t = T special cases are evaluated under it.
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((M::NX <= 16 ? ILQR_FD_G_WAVES_SMALL : 2), (M::NX <= 16 ? ILQR_FD_G_WAVES_SMALL : 2)))) void k_derivatives_g(BatchViewT<S> v, model_arg_t<M, PT> model, int force, int t_only) {
   constexpr int NX = M::NX, NU = M::NU;
   const int nx = model.nx, nu = model.nu, T = v.T;
@@ -895,8 +949,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((M::NX <= 16
             oCUU = oCU + nu, REC = oCUU + nu * nu;
   S* D = v.D + ((size_t)b * (T + 1) + t) * REC;
   const bool last = (t == T);
-  if constexpr (PT) {  // row b (see k_rollout_g)
-    cmem_d* row = (cmem_d*)model.traj_params + (size_t)b * M::NTP;
+  if constexpr (PT != ROWS_NONE) {  // row b (see k_rollout_g); PK: row (b, t), as wave-uniform as b is
+    cmem_d* row = (cmem_d*)model.traj_params + (PT == PK_ROWS ? (size_t)b * (T + 1) + t : (size_t)b) * M::NTP;
     double p[M::NTP];
 #pragma unroll
     for (int i = 0; i < M::NTP; i++) {

@@ -60,6 +60,12 @@ struct ilqr_batch {
   // whether the kernels read them.  Row b is the trajectory in slot b: the generic path never re-packs trajectories (ilqr_generate_trajectory
   // compacts on the persistent routes only) -- whoever brings compaction to this path must move these rows with the trajectories.
   double* traj_params = nullptr;
+  // per-knot model parameters (ilqr_set_knot_params): the handle's own window [B][T+1][NTP] of the caller's reference, canonical double,
+  // allocated on first use and kept; read while plan.traj_params is per_knot.  knot_stage: a host reference on its way through the gather
+  // kernel, [B][n_knots][NTP], allocated by the first host call, kept while the next call's fits (ensure_knot_stage), freed with the handle
+  double* knot_params = nullptr;
+  double* knot_stage = nullptr;
+  size_t knot_stage_elems = 0;
   // single trajectories starting over on the device (reset.hpp; ilqr_reset_trajectories, ilqr_mpc_step_reset): allocated by the first call
   // that needs them (dev_alloc: freed with the handle), nothing per call afterwards
   int* reset_ints = nullptr;         // [3][Bp]: a host mask's copy, the selection of the pass under way, the flags of the last call
@@ -349,6 +355,18 @@ static int ensure_est_scratch(ilqr_batch* h, size_t elems) {
   }
   HIPCHK(hipMalloc((void**)&h->est_scratch, elems * sizeof(double)));
   h->est_scratch_elems = elems;
+  return 0;
+}
+static int ensure_knot_stage(ilqr_batch* h, size_t elems) {
+  if (elems <= h->knot_stage_elems) return 0;
+  if (h->knot_stage) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipFree(h->knot_stage));
+    h->knot_stage = nullptr;
+    h->knot_stage_elems = 0;
+  }
+  HIPCHK(hipMalloc((void**)&h->knot_stage, elems * sizeof(double)));
+  h->knot_stage_elems = elems;
   return 0;
 }
 static int ensure_pg_scratch(ilqr_batch* h, size_t elems) {

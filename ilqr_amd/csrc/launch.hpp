@@ -55,21 +55,27 @@ static int with_rollout_model(ilqr_batch* h, F&& f) {
 #endif
   return fail(ILQR_ERR_UNSUPPORTED, "model %d has no fp32 generic device kernels", h->model);
 }
-// the model with the handle's per-trajectory rows behind it: what the PT instantiations of k_rollout_g / k_derivatives_g / k_evaluate_g take
+// the model with the handle's rows behind it: what the PT and PK instantiations of k_rollout_g / k_derivatives_g / k_evaluate_g take (the
+// per-trajectory rows, or the per-knot window while the handle is in knot mode)
 template <class M>
 static PerTrajectory<M> per_trajectory(const ilqr_batch* h, const M& m) {
   PerTrajectory<M> pm;
   static_cast<M&>(pm) = m;
-  pm.traj_params = h->traj_params;
+  pm.traj_params = h->plan.traj_params == ModelRows::per_knot ? h->knot_params : h->traj_params;
   return pm;
 }
-// f(model argument, PT) for a kernel with a PT instantiation: (per_trajectory(h, m), true) while the handle holds per-trajectory parameters
-// -- every lane's model copy is then set from its trajectory's row --, else (m, false)
+// f(model argument, PT) for a kernel with PT and PK instantiations: (per_trajectory(h, m), PT_ROWS) while the handle holds per-trajectory
+// parameters -- every lane's model copy is then set from its trajectory's row --, (per_trajectory(h, m), PK_ROWS) while it holds per-knot
+// rows -- set from row (b, t) before anything is evaluated at knot t --, else (m, ROWS_NONE)
+static_assert((int)ModelRows::none == ROWS_NONE && (int)ModelRows::per_trajectory == PT_ROWS && (int)ModelRows::per_knot == PK_ROWS,
+              "route.hpp's ModelRows are generic.hpp's template values");
 template <class M, class F>
 static int with_trajectory_params(const ilqr_batch* h, const M& m, F&& f) {
-  if constexpr (has_trajectory_params<M>::value)
-    if (h->plan.traj_params) return f(per_trajectory(h, m), std::true_type());
-  return f(m, std::false_type());
+  if constexpr (has_trajectory_params<M>::value) {
+    if (h->plan.traj_params == ModelRows::per_trajectory) return f(per_trajectory(h, m), std::integral_constant<int, PT_ROWS>());
+    if (h->plan.traj_params == ModelRows::per_knot) return f(per_trajectory(h, m), std::integral_constant<int, PK_ROWS>());
+  }
+  return f(m, std::integral_constant<int, ROWS_NONE>());
 }
 // generic path (generic.hpp): WHAT = RG_INIT / RG_SEARCH / RG_COMMIT.  The LQ model rolls out on the
 // matrix cores (k_rollout_lq, one wavefront per trajectory); ILQR_ROUTE_LQ_THREAD_ROLLOUT selects the
@@ -612,14 +618,14 @@ static int launch_evaluate(ilqr_batch* h, const EvalArgs& e, const char** name) 
   const dim3 grid((unsigned)(((size_t)h->B * e.S + 63) / 64)), block(64);
   if (!h->aos)
     return with_model(h, [&](auto& v, auto& m, auto&) {
-      *name = evaluate_kernel_name(false, false);
+      *name = evaluate_kernel_name(false, ModelRows::none);
       hipLaunchKernelGGL((k_evaluate_t<std::decay_t<decltype(m)>>), grid, block, 0, h->stream, v, m, e);
       HIPCHK(hipGetLastError());
       return 0;
     });
   return with_rollout_model(h, [&](auto& m) { return with_trajectory_params(h, m, [&](const auto& pm, auto pt) {
     using M = std::decay_t<decltype(m)>;
-    *name = evaluate_kernel_name(true, decltype(pt)::value);
+    *name = evaluate_kernel_name(true, (ModelRows) decltype(pt)::value);
     hipLaunchKernelGGL((k_evaluate_g<M, decltype(pt)::value>), grid, block, 0, h->stream, view_of<typename M::real>(h), pm, e);
     HIPCHK(hipGetLastError());
     return 0;

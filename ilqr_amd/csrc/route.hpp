@@ -19,6 +19,8 @@ enum class Backward { quad, thread, w3, w3_regv, w3_two_tiles, w2 };
 enum class Rollout { tiled, lq_accept, lq, generic };
 // k_commit from the alpha planes, k_commit_lq from the LQ search's kept rollouts, or the accepted rollout run again in place
 enum class Commit { tiled, lq_copy, rerun };
+// the model rows the generic kernels read: none (ilqr_create's parameters for all), one per trajectory, one per knot of every trajectory
+enum class ModelRows { none, per_trajectory, per_knot };
 
 struct RoutePlan {  // (the defaults: what ilqr_stage_kernel_name reports for a null handle)
   Solve solve = Solve::none;
@@ -27,10 +29,10 @@ struct RoutePlan {  // (the defaults: what ilqr_stage_kernel_name reports for a 
   Backward backward = Backward::thread;
   Rollout rollout = Rollout::tiled;
   Commit commit = Commit::tiled;
-  // per-trajectory model parameters are set (ilqr_set_trajectory_params ... ilqr_clear_trajectory_params): every launch that hands the
-  // user twin to k_rollout_g / k_derivatives_g / k_evaluate_g takes the PT instantiation (launch.hpp: with_trajectory_params).  The one
-  // part of the plan that changes after ilqr_create.
-  bool traj_params = false;
+  // the handle's model rows: none, one per trajectory (ilqr_set_trajectory_params) or one per knot (ilqr_set_knot_params), until
+  // ilqr_clear_trajectory_params.  Every launch that hands the user twin to k_rollout_g / k_derivatives_g / k_evaluate_g takes the PT or
+  // the PK instantiation accordingly (launch.hpp: with_trajectory_params).  The one part of the plan that changes after ilqr_create.
+  ModelRows traj_params = ModelRows::none;
 };
 
 // Which instantiation of a wavefront-per-trajectory kernel a handle of these sizes runs, as plain data (launch.hpp turns it into template
@@ -81,7 +83,10 @@ inline const char* risk_kernel_name(bool aos, const WaveVariant& w, int wt) {  /
                                              {{"k_risk_w<2, 1, 1>", "k_risk_w<2, 1, 2>"}, {"k_risk_w<2, 2, 1>", "k_risk_w<2, 2, 2>"}}};
   return aos ? kWave[w.nt - 1][w.mt - 1][wt - 1] : "k_risk_t";
 }
-inline const char* evaluate_kernel_name(bool aos, bool traj_params) { return !aos ? "k_evaluate_t" : traj_params ? "k_evaluate_g<PT>" : "k_evaluate_g"; }
+inline const char* evaluate_kernel_name(bool aos, ModelRows rows) {
+  static const char* const kRows[] = {"k_evaluate_g", "k_evaluate_g<PT>", "k_evaluate_g<PK>"};
+  return aos ? kRows[(int)rows] : "k_evaluate_t";
+}
 // k_pg_contract (param_gradient.hpp): how a wavefront's eight lane octets are shared out for a twin of ntp per-trajectory parameters, as
 // plain data -- dirs directions side by side (ntp <= 4), or passes rounds of eight parameters for one direction (ntp > 8)
 struct ParamGradientShape {

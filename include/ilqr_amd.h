@@ -662,9 +662,40 @@ int ilqr_trajectory_params_count(void); /* NTP of this build's user model, 0 = n
  * no synchronisation; a host array from page-locked memory must stay unchanged until the stream has passed the call (as x0 of
  * ilqr_mpc_step).  The first call on a handle allocates the rows. */
 int ilqr_set_trajectory_params(ilqr_batch* h, const double* p, const void* p_device, int n);
-int ilqr_get_trajectory_params(ilqr_batch* h, double* p, int n); /* the rows as they were set; synchronises; ILQR_ERR_STATE while none are set */
-/* back to the handle-wide parameters of ilqr_create for every trajectory */
+int ilqr_get_trajectory_params(ilqr_batch* h, double* p, int n); /* the rows as they were set; synchronises; ILQR_ERR_STATE while none are set (or per-knot rows are) */
+/* back to the handle-wide parameters of ilqr_create for every trajectory (clears per-knot rows as well) */
 int ilqr_clear_trajectory_params(ilqr_batch* h);
+
+/* ---- per-knot model parameters (additive under ABI 6) ------------------------------------------------------------------------------
+ * The same NTP parameters, one row per KNOT of every trajectory: reference tracking, gait and contact schedules, time-varying cost
+ * weights, a disturbance preview, a model that changes inside the horizon.  A handle's model rows are in one of three states: none, one
+ * row per trajectory (above), or one row per knot.  With knot rows P[b][t][0..NTP), t = 0..T, the model copy of trajectory b is set from row
+ * t through the twin's set_trajectory_params before anything is evaluated at knot t: cost(x_t, u_t) and dynamics(x_t, u_t) use row t;
+ * final_cost(x_T) and the t = T special cases of the derivative record use row T.  Fields the twin does not write keep ilqr_create's
+ * values; an fp32 handle uses the rows' float-rounded values in both of its twins.  The limits the backward pass's box-QP sees stay the
+ * handle's (u_min / u_max of ilqr_create), exactly as with per-trajectory rows: a twin whose set_trajectory_params writes its limit
+ * fields changes what an opt-in clamp of the rollouts sees, never the box-QP.  No twin changes: any header with NTP and
+ * set_trajectory_params takes knot rows.
+ * THE SOURCE ARRAY p / p_device is [B][n_knots][n] double with n == NTP, a reference of any length; exactly one of the two pointers is
+ * non-NULL.  THE WINDOW: the handle takes the T + 1 rows starting at k0 -- row t of the handle is source row min(k0 + t, n_knots - 1), so
+ * the horizon's tail holds the last row of a reference that ends.  Tracking MPC is two calls per step with no re-packing by the caller:
+ *     ilqr_set_knot_params(h, NULL, ref_device, NTP, L, k);   ilqr_mpc_step(..., shift = s, ...);   k += s;
+ * The handle owns a copy [B][T+1][NTP] double, allocated on first use and kept (B = 4096, T = 200, NTP = 8: 52 MB); a gather kernel fills
+ * it on the handle's stream and nothing is waited for.  A host p goes up whole into a scratch buffer of B * n_knots * NTP doubles the
+ * handle keeps while the next call's fits, then through the same gather; a host array from page-locked memory must stay unchanged until
+ * the stream has passed the call (as x0 of ilqr_mpc_step).
+ * The setter switches the handle to knot mode, ilqr_set_trajectory_params back to one row per trajectory, ilqr_clear_trajectory_params
+ * clears either.  As with per-trajectory rows, setting does NOT re-evaluate the stored cost or trajectory: the next ilqr_warm_start /
+ * ilqr_mpc_step does.  ilqr_shift_horizon does not move the rows -- the caller names the window --, and the ilqr_clone_* calls copy no
+ * rows of either kind.  In knot mode ilqr_get_trajectory_params answers ILQR_ERR_STATE, and ilqr_get_param_gradient /
+ * ilqr_param_gradient_on_device answer ILQR_ERR_UNSUPPORTED (the gradient is defined for per-trajectory rows; they never read rows of an
+ * earlier mode).
+ * Refusals, before anything is enqueued, in this order (ilqr_last_error() names each): ILQR_ERR_INVALID without needing a handle for not
+ * exactly one of p / p_device, n_knots < 1, k0 outside [0, n_knots); a null handle; ILQR_ERR_UNSUPPORTED for every handle
+ * ilqr_set_trajectory_params refuses; ILQR_ERR_INVALID for n != NTP and for B * (T + 1) * NTP beyond INT_MAX. */
+int ilqr_set_knot_params(ilqr_batch* h, const double* p, const void* p_device, int n, int n_knots, int k0);
+/* [B][T+1][NTP] as the kernels see them (the window, not the source); synchronises; ILQR_ERR_STATE outside knot mode */
+int ilqr_get_knot_params(ilqr_batch* h, double* p, int n);
 
 /* ---- the gradient of a caller's loss with respect to the per-trajectory parameters (additive under ABI 6) ----------------------------
  * ilqr_solve_lq turns gx = dL/dxs, gu = dL/dus into dxs, dus and the multipliers dlam; these calls turn those three into dL/dp, the

@@ -665,6 +665,25 @@ class BatchILQR {
     return p;
   }
   void clear_trajectory_params() { check(ilqr_clear_trajectory_params(h_), "ilqr_clear_trajectory_params"); }
+  // Per-knot model parameters (ilqr_set_knot_params): the handle takes the window of T + 1 rows starting at row k0 of a reference
+  // p [B][n_knots][NTP] -- row t of the handle is reference row min(k0 + t, n_knots - 1) -- and evaluates knot t of trajectory b under
+  // row (b, t).  set_trajectory_params switches back to one row per trajectory, clear_trajectory_params to none.
+  void set_knot_params(const std::vector<double>& p, int n_knots, int k0 = 0) {
+    const int n = ilqr_trajectory_params_count();
+    require(n > 0 && n_knots >= 1 && p.size() == (size_t)B_ * n_knots * n, "set_knot_params: p [B][n_knots][NTP]");
+    check(ilqr_set_knot_params(h_, p.data(), nullptr, n, n_knots, k0), "ilqr_set_knot_params");
+  }
+  // p_device: [B][n_knots][NTP] double in device memory of the handle's device; enqueued on the handle's stream, nothing waited for
+  void set_knot_params(const void* p_device, int n_knots, int k0 = 0) {
+    check(ilqr_set_knot_params(h_, nullptr, p_device, ilqr_trajectory_params_count(), n_knots, k0), "ilqr_set_knot_params");
+  }
+  // the window as the kernels see it, [B][T+1][NTP]
+  std::vector<double> knot_params() {
+    const int n = ilqr_trajectory_params_count();
+    std::vector<double> p((size_t)B_ * (T_ + 1) * (n > 0 ? n : 1));
+    check(ilqr_get_knot_params(h_, p.data(), n), "ilqr_get_knot_params");
+    return p;
+  }
   // dL/dp, the gradient of the caller's loss in those rows (ilqr_get_param_gradient), from what lq_solve returned for gx = dL/dxs, gu =
   // dL/dus: dxs, dlam [B][T+1][n_dirs][nx], dus [B][T][n_dirs][nu] (null = zero, not all three).  Returns gp [B][n_dirs][NTP]; lam, if asked
   // for, is the nominal costate [B][T+1][nx].  eps_p: the relative parameter step (0 = 1e-3).
